@@ -4,7 +4,7 @@
 N GPUs of one node, ONE RCCL all-gather of the per-shard packed (score, id) partial top-k + merge on
 the device).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 launches its own ranks (``python -m torch.distributed.run``, one per GPU, as a
 child process started before anything touches the GPU) unless it already runs under such a launcher
@@ -15,12 +15,20 @@ batch) -> K2 (fused MFMA similarity + top-k over this rank's rows) -> K4 (candid
 [N>1: all-gather + device merge] -> results on the host.  Corpus and query batch are resident in HBM
 before the timed region.  Total work is fixed as N grows ("scaling": "strong").
 
-Rank 0 prints ONE JSON line.  Besides the contract keys:
-  median_ms_per_step, value_incl_h2d (fp32 queries handed over in pinned HOST memory every step),
-  value_incl_h2d_pipelined (the same with the copy of batch i+1 on a second stream under the search of batch i)
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the contract keys and, read
+from the timed steps alone,
+  median_ms_per_step
+  step_phases_ms       per-phase device ms of a step (local search, pack, all-gather, merge, D2H)
   roofline             dominant kernel (K2) at the bench workload: algorithmic FLOP = 2*Q*N_local*D per
-                       launch over the kernel's hipEvent time measured inside the library on the launch
-                       stream; held_clock_ghz = in-kernel s_memtime / s_memrealtime reading
+                       launch over the kernel's hipEvent time measured inside the library on the launch stream
+``--dump-outputs DIR`` writes what the last timed step returned: DIR/scores.npy (float32) and DIR/ids.npy
+(float64), Q x k each; above 64 MB in all, a fixed seeded sample of query rows, listed in DIR/rows.npy.
+The inputs are seeded, so the same arguments give the same inputs on every run.
+
+``--full`` adds every other measurement (each after the timed steps; none of them touches `value`):
+  value_incl_h2d (fp32 queries handed over in pinned HOST memory every step),
+  value_incl_h2d_pipelined (the same with the copy of batch i+1 on a second stream under the search of batch i)
+  roofline.held_clock_ghz  in-kernel s_memtime / s_memrealtime reading over one more step
   north_star_roofline  the same kernel at BASELINE's north-star GEMM shape 1 000 x 1 000 000 x 768 (N=1)
   c2_roofline          ... and at config C2, 1 000 x 100 000 x 768 (N=1)
   online_roofline      1 query per call (the reference's own usage): streaming kernel, HBM-bound
@@ -30,7 +38,7 @@ Rank 0 prints ONE JSON line.  Besides the contract keys:
   ivf_roofline_5m      the same over the WHOLE 5 M x 768 corpus on one GPU (7.7 GB; C5's N = 1 point)
   ivf_skewed           recall@10 and search ms vs nprobe on Zipf-sized, overlapping clusters (not the best case)
   ingest_from_text     C3's 64 k passages, text -> tokens -> bge-base forward -> index, passages/s
-  step_phases_ms       per-phase device ms of a step (local search, pack, all-gather, merge, D2H); N > 1: two_half_pipeline
+  two_half_pipeline    N > 1: the step with the all-gather of half the batch under the local search of the other half
   encoder_roofline     config C3 shape (bge-base, 2048 passages x 128 tokens): device ms of the forward (N=1)
   cpu_baseline         N=1: the numpy restatement (oracle.dense_search.brute_force_topk_f32: sgemm + top-k on
                        the same fp16-rounded rows) timed on this host's cores on a bounded query sample
@@ -74,6 +82,24 @@ def build_shard(ix, lo: int, hi: int, dim: int, device):
         a, b = max(lo, c * CHUNK), min(hi, (c + 1) * CHUNK)
         ix.add(rows[a - c * CHUNK:b - c * CHUNK])
         c += 1
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, scores: np.ndarray, ids: np.ndarray) -> None:
+    """--dump-outputs: the last timed step's (scores, ids) as DIR/scores.npy (float32) and DIR/ids.npy (float64, exact for
+    any id below 2^53).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of query rows (sorted, in DIR/rows.npy)."""
+    arrays = {"scores": np.asarray(scores, dtype=np.float32), "ids": np.asarray(ids, dtype=np.float64)}
+    n_rows = arrays["scores"].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n_rows * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, DUMP_LIMIT_BYTES // (2 * row_bytes), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def self_launch(args) -> int:
@@ -336,10 +362,17 @@ def main():
     ap.add_argument("--n-corpus", type=int, default=N_CORPUS)
     ap.add_argument("--n-queries", type=int, default=N_QUERIES)
     ap.add_argument("--dim", type=int, default=DIM)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / recall legs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the north-star / C2 / IVF / encoder sub-objects")
-    ap.add_argument("--skip-legs", default="", help="comma list of sub-objects to skip (e.g. ivf_roofline_5m,ingest_from_text): counter passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/scores.npy (float32) and DIR/ids.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, run every other measurement (host-memory hand-over, clock, online, "
+                         "north-star / C2 / IVF / encoder / ingest legs, CPU baseline and recall)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline / recall legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the north-star / C2 / IVF / encoder sub-objects")
+    ap.add_argument("--skip-legs", default="", help="with --full: comma list of sub-objects to skip (e.g. ivf_roofline_5m,ingest_from_text): counter passes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -379,16 +412,10 @@ def main():
     build_shard(sh.index, sh.lo, sh.hi, d, device)
     gq = torch.Generator(device=device).manual_seed(5678)
     queries = torch.randn(nq, d, device=device, generator=gq, dtype=torch.float32)
-    q_host = queries.cpu().pin_memory()                 # the boundary's host-buffer form (value_incl_h2d)
-    q_stage = torch.empty_like(queries)
     torch.cuda.synchronize()
 
     def step():
         return sh.search(queries, k)
-
-    def step_h2d():
-        q_stage.copy_(q_host, non_blocking=True)         # 30.7 MB of fp32 queries over PCIe, same stream as the search
-        return sh.search(q_stage, k)
 
     def fence():
         if world > 1:
@@ -415,93 +442,105 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sc, ids)
 
-    # the same steps with the queries handed over in HOST memory (PCIe-inclusive rate; never `value`)
-    n_h2d = max(5, min(args.steps, 20))
-    for _ in range(2):
-        step_h2d()
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(n_h2d):
-        step_h2d()
-    fence()
-    elapsed_h2d = time.perf_counter() - t1
-    if world > 1:
-        tmax = torch.tensor([elapsed_h2d], dtype=torch.float64, device=device)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed_h2d = float(tmax.item())
-
-    # ... and pipelined, as a server would: the H2D copy of batch i + 1 runs on a second stream under the search of batch i
-    # (two staging buffers; every batch still crosses PCIe once)
-    copy_stream = torch.cuda.Stream(device=device)
-    q_stages = [torch.empty_like(queries), torch.empty_like(queries)]
-    ready = [torch.cuda.Event(), torch.cuda.Event()]
-
-    def enqueue_copy(j):
-        copy_stream.wait_stream(torch.cuda.current_stream(device))      # the search that last read this buffer is queued ahead
-        with torch.cuda.stream(copy_stream):
-            q_stages[j].copy_(q_host, non_blocking=True)
-            ready[j].record(copy_stream)
-
-    enqueue_copy(0)
-    for i in range(2):
-        enqueue_copy((i + 1) & 1)
-        torch.cuda.current_stream(device).wait_event(ready[i & 1])
-        sh.search(q_stages[i & 1], k)
-    fence()
-    t2 = time.perf_counter()
-    enqueue_copy(0)
-    for i in range(n_h2d):
-        if i + 1 < n_h2d:
-            enqueue_copy((i + 1) & 1)
-        torch.cuda.current_stream(device).wait_event(ready[i & 1])
-        sh.search(q_stages[i & 1], k)
-    fence()
-    elapsed_h2d_pipe = time.perf_counter() - t2
-    if world > 1:
-        tmax = torch.tensor([elapsed_h2d_pipe], dtype=torch.float64, device=device)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed_h2d_pipe = float(tmax.item())
-
-    # N > 1: the same steps with the batch cut in two halves, the all-gather of half A in flight under the local search of half B
-    elapsed_pipe, pipe_phase_ms = None, []
-    if world > 1:
-        for _ in range(2):
-            sh.search(queries, k, pipeline=True)
-        fence()
-        t3 = time.perf_counter()
-        for _ in range(n_h2d):
-            sh.search(queries, k, pipeline=True)
-            pipe_phase_ms.append(dict(sh.last_phases))
-        fence()
-        elapsed_pipe = time.perf_counter() - t3
-        tmax = torch.tensor([elapsed_pipe], dtype=torch.float64, device=device)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed_pipe = float(tmax.item())
-
-    # held clock under K2: one more step with the in-kernel stamps on
+    # --full: every other measurement, after the timed steps (none of them touches `value`)
     clock_ghz = None
-    try:
-        sh.index.measure_clock(True)
-        step()
-        clock_ghz = sh.index.last_clock_ghz()
-    except Exception:
-        clock_ghz = None
-    sh.index.measure_clock(False)
+    if args.full:
+        q_host = queries.cpu().pin_memory()                 # the boundary's host-buffer form (value_incl_h2d)
+        q_stage = torch.empty_like(queries)
 
-    # the online regime (one query per call = the reference's own usage): K2s, HBM-bound
-    online_ms, online_search_ms, online_pool_ms = [], [], []
-    for i in range(8):
-        sh.index.search(queries[:1], k)
-        if i > 1:
-            g_ms, t_ms = sh.index.last_timing_ms()
-            online_ms.append(g_ms)
-            online_search_ms.append(t_ms)
-    for i in range(6):                      # the reference's dense pool: 200 candidates per question (settings.yaml:101-102)
-        sh.index.search(queries[:1], 200)
-        if i > 1:
-            online_pool_ms.append(sh.index.last_timing_ms()[1])
-    fence()
+        def step_h2d():
+            q_stage.copy_(q_host, non_blocking=True)         # 30.7 MB of fp32 queries over PCIe, same stream as the search
+            return sh.search(q_stage, k)
+
+        # the same steps with the queries handed over in HOST memory (PCIe-inclusive rate; never `value`)
+        n_h2d = max(5, min(args.steps, 20))
+        for _ in range(2):
+            step_h2d()
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(n_h2d):
+            step_h2d()
+        fence()
+        elapsed_h2d = time.perf_counter() - t1
+        if world > 1:
+            tmax = torch.tensor([elapsed_h2d], dtype=torch.float64, device=device)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed_h2d = float(tmax.item())
+
+        # ... and pipelined, as a server would: the H2D copy of batch i + 1 runs on a second stream under the search of batch i
+        # (two staging buffers; every batch still crosses PCIe once)
+        copy_stream = torch.cuda.Stream(device=device)
+        q_stages = [torch.empty_like(queries), torch.empty_like(queries)]
+        ready = [torch.cuda.Event(), torch.cuda.Event()]
+
+        def enqueue_copy(j):
+            copy_stream.wait_stream(torch.cuda.current_stream(device))      # the search that last read this buffer is queued ahead
+            with torch.cuda.stream(copy_stream):
+                q_stages[j].copy_(q_host, non_blocking=True)
+                ready[j].record(copy_stream)
+
+        enqueue_copy(0)
+        for i in range(2):
+            enqueue_copy((i + 1) & 1)
+            torch.cuda.current_stream(device).wait_event(ready[i & 1])
+            sh.search(q_stages[i & 1], k)
+        fence()
+        t2 = time.perf_counter()
+        enqueue_copy(0)
+        for i in range(n_h2d):
+            if i + 1 < n_h2d:
+                enqueue_copy((i + 1) & 1)
+            torch.cuda.current_stream(device).wait_event(ready[i & 1])
+            sh.search(q_stages[i & 1], k)
+        fence()
+        elapsed_h2d_pipe = time.perf_counter() - t2
+        if world > 1:
+            tmax = torch.tensor([elapsed_h2d_pipe], dtype=torch.float64, device=device)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed_h2d_pipe = float(tmax.item())
+
+        # N > 1: the same steps with the batch cut in two halves, the all-gather of half A in flight under the local search of half B
+        elapsed_pipe, pipe_phase_ms = None, []
+        if world > 1:
+            for _ in range(2):
+                sh.search(queries, k, pipeline=True)
+            fence()
+            t3 = time.perf_counter()
+            for _ in range(n_h2d):
+                sh.search(queries, k, pipeline=True)
+                pipe_phase_ms.append(dict(sh.last_phases))
+            fence()
+            elapsed_pipe = time.perf_counter() - t3
+            tmax = torch.tensor([elapsed_pipe], dtype=torch.float64, device=device)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed_pipe = float(tmax.item())
+
+        # held clock under K2: one more step with the in-kernel stamps on
+        clock_ghz = None
+        try:
+            sh.index.measure_clock(True)
+            step()
+            clock_ghz = sh.index.last_clock_ghz()
+        except Exception:
+            clock_ghz = None
+        sh.index.measure_clock(False)
+
+        # the online regime (one query per call = the reference's own usage): K2s, HBM-bound
+        online_ms, online_search_ms, online_pool_ms = [], [], []
+        for i in range(8):
+            sh.index.search(queries[:1], k)
+            if i > 1:
+                g_ms, t_ms = sh.index.last_timing_ms()
+                online_ms.append(g_ms)
+                online_search_ms.append(t_ms)
+        for i in range(6):                      # the reference's dense pool: 200 candidates per question (settings.yaml:101-102)
+            sh.index.search(queries[:1], 200)
+            if i > 1:
+                online_pool_ms.append(sh.index.last_timing_ms()[1])
+        fence()
 
     out = None
     if rank == 0:
@@ -528,10 +567,6 @@ def main():
                        "rows_per_gpu": n_local, "parallelism": f"row-shard x{world}",
                        **({"rehearsal": "all ranks on ONE GPU, exchange over gloo: exercises the N > 1 code path, not a scaling number"} if rehearse else {})},
             "median_ms_per_step": float(np.median(step_ms)),
-            "value_incl_h2d": nq * n_h2d / elapsed_h2d,
-            "value_incl_h2d_pipelined": nq * n_h2d / elapsed_h2d_pipe,
-            "value_incl_h2d_note": f"{n_h2d} steps with the fp32 query batch in pinned host memory (H2D {nq * d * 4 / 1e6:.1f} MB "
-                                   "per step on the search stream) and results on the host; `value` has the batch resident in HBM",
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS_F16, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_TFLOPS_F16, "traffic": None,
                          "kernel": "bf_gemm_topk_kernel", "kernel_ms": k2_ms, "kernel_ms_median": float(np.median(gemm_ms)),
@@ -544,20 +579,25 @@ def main():
             "step_phases_ms": {kk_: float(np.median([p_.get(kk_, 0.0) for p_ in phase_ms])) for kk_ in
                                ("local_ms", "pack_ms", "gather_ms", "merge_ms", "d2h_ms")},
         }
-        if elapsed_pipe is not None:
-            out["two_half_pipeline"] = {"ms_per_step": elapsed_pipe / n_h2d * 1e3, "value": nq * n_h2d / elapsed_pipe,
-                                        "phases_ms": {kk_: float(np.median([p_.get(kk_, 0.0) for p_ in pipe_phase_ms])) for kk_ in
-                                                      ("local_ms", "pack_ms", "gather_ms", "merge_ms", "d2h_ms")},
-                                        "note": "batch cut in two halves, all-gather of half A (async_op) under the local search of half B; "
-                                                "gather_ms = the part of the collectives the local search did not cover; `value` above is the one-shot step"}
-        on_ms = float(np.median(online_ms))
-        on_bytes = (sh.hi - sh.lo) * d * 2.0 + d * 2.0
-        out["online_roofline"] = {"bound": "hbm", "kernel": "bf_stream_topk_kernel", "workload": "1 query x this rank's rows, k=10",
-                                  "kernel_ms": on_ms, "achieved": on_bytes / (on_ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                  "frac": on_bytes / (on_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "bytes_per_launch": on_bytes,
-                                  "search_ms": float(np.median(online_search_ms)),
-                                  "search_ms_k200": float(np.median(online_pool_ms)),
-                                  "note": "search_ms = K1 + streaming kernel + merge on the device, one question; k200 = the reference's 200-candidate pool"}
+        if args.full:
+            out["value_incl_h2d"] = nq * n_h2d / elapsed_h2d
+            out["value_incl_h2d_pipelined"] = nq * n_h2d / elapsed_h2d_pipe
+            out["value_incl_h2d_note"] = (f"{n_h2d} steps with the fp32 query batch in pinned host memory (H2D {nq * d * 4 / 1e6:.1f} MB "
+                                          "per step on the search stream) and results on the host; `value` has the batch resident in HBM")
+            if elapsed_pipe is not None:
+                out["two_half_pipeline"] = {"ms_per_step": elapsed_pipe / n_h2d * 1e3, "value": nq * n_h2d / elapsed_pipe,
+                                            "phases_ms": {kk_: float(np.median([p_.get(kk_, 0.0) for p_ in pipe_phase_ms])) for kk_ in
+                                                          ("local_ms", "pack_ms", "gather_ms", "merge_ms", "d2h_ms")},
+                                            "note": "batch cut in two halves, all-gather of half A (async_op) under the local search of half B; "
+                                                    "gather_ms = the part of the collectives the local search did not cover; `value` above is the one-shot step"}
+            on_ms = float(np.median(online_ms))
+            on_bytes = (sh.hi - sh.lo) * d * 2.0 + d * 2.0
+            out["online_roofline"] = {"bound": "hbm", "kernel": "bf_stream_topk_kernel", "workload": "1 query x this rank's rows, k=10",
+                                      "kernel_ms": on_ms, "achieved": on_bytes / (on_ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                      "frac": on_bytes / (on_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "bytes_per_launch": on_bytes,
+                                      "search_ms": float(np.median(online_search_ms)),
+                                      "search_ms_k200": float(np.median(online_pool_ms)),
+                                      "note": "search_ms = K1 + streaming kernel + merge on the device, one question; k200 = the reference's 200-candidate pool"}
         # HBM-side traffic of K2 comes from separate rocprofv3 --pmc passes of this same command
         # (FETCH_SIZE / WRITE_SIZE, gfx950 correction applied; profiles/r*_pmc_traffic.json, tools/profile_round.sh)
         pmcs = sorted((ROOT / "profiles").glob("r*_pmc_traffic.json"))
@@ -568,7 +608,7 @@ def main():
                 out["roofline"]["traffic_note"] = f"bytes/launch, L2<->fabric requests (Infinity-Cache hits included); profiles/{pmc.name}"
             except Exception:
                 pass
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # BASELINE's north-star GEMM shape and config C2 on the same kernel
             out["north_star_roofline"] = k2_roofline(sh.index, queries[:1000], k, n_local, d,
                                                      label=f"north star: 1 000 x {n_local} x {d} fp16, k={k}")
@@ -577,7 +617,7 @@ def main():
             build_shard(c2, 0, 100_000, d, device)
             out["c2_roofline"] = k2_roofline(c2, queries[:1000], k, 100_000, d, label=f"C2: 1 000 x 100 000 x {d} fp16, k={k}")
             c2.close()
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             from oracle import dense_search as ods
             c32 = sh.index.rows()                                  # the stored fp16 bits, as fp32
             q16 = ods.normalize_round(queries.cpu().numpy())       # same arithmetic as K1
@@ -616,7 +656,7 @@ def main():
                                              f"(numpy sgemm + argpartition top-{k}, {cpu_s:.1f} s)",
                                    "reference_style_python": ref_style}
             del c32
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             sh.index.close()                                       # free the 1.5 GB corpus before the other configs
             for name, leg in (("ivf_roofline", lambda: ivf_leg(device, k, with_cpu=not args.no_cpu)),
                               ("ivf_roofline_5m", lambda: ivf_leg(device, k, n=5_000_000)),

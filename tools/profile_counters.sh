@@ -11,7 +11,7 @@ o=$PWD/gpurun_out
 rocprofv3 -L > $o/${tag}_counter_list.txt 2>&1 || true
 pass() {  # name, counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $o/${tag}_pmc_$name -o ${tag} -- python3 bench.py --steps 3 --warmup 1 --no-cpu --skip-legs ivf_roofline_5m,ivf_skewed,ingest_from_text > $o/${tag}_pmc_$name.log 2>&1 \
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $o/${tag}_pmc_$name -o ${tag} -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --skip-legs ivf_roofline_5m,ivf_skewed,ingest_from_text > $o/${tag}_pmc_$name.log 2>&1 \
     || { echo "pass $name failed"; tail -5 $o/${tag}_pmc_$name.log; }
 }
 pass busy   SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE
