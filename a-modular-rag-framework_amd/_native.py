@@ -9,6 +9,8 @@ from pathlib import Path
 MRAG_F32, MRAG_F16, MRAG_BF16, MRAG_F64 = 0, 1, 2, 3
 METRIC_COSINE, METRIC_IP = 0, 1
 POOL_MEAN, POOL_CLS = 0, 1
+FILTER_AUTO, FILTER_MASK, FILTER_COMPACT = 0, 1, 2
+ALLOW_BITS32, ALLOW_BYTES = 0, 1
 
 ERR_NAMES = {-1: "MRAG_ERR_INVALID", -2: "MRAG_ERR_NO_DEVICE", -3: "MRAG_ERR_HIP", -4: "MRAG_ERR_OOM",
              -5: "MRAG_ERR_UNSUPPORTED"}
@@ -62,6 +64,8 @@ SIGNATURES = {
     "mrag_index_get_rows": [_h, _i64, _i64, _vp, _i, _vp],
     "mrag_index_search": [_h, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp],
     "mrag_index_score_rows": [_h, _vp, _i, _i, _vp, _i64, _vp, _vp],
+    "mrag_index_search_filtered": [_h, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp],
+    "mrag_index_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64)],
     "mrag_index_last_timing": [_h, _fp, _fp],
     "mrag_index_measure_clock": [_h, _i],
     "mrag_index_last_clock": [_h, _fp],

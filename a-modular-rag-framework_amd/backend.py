@@ -152,7 +152,8 @@ class DenseRetrievalBackend:
                  text_search: Optional[Callable[..., List[Dict[str, Any]]]] = None,
                  graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None,
                  text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
-                 fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096):
+                 fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
+                 dense_row_filter: Optional[Any] = None):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -168,6 +169,15 @@ class DenseRetrievalBackend:
         # builds its index from the file in one go); the router path below stays as the fallback / error-policy reference
         self.bulk_ingest, self.bulk_batch = bool(bulk_ingest), int(bulk_batch)
         self.last_build: Dict[str, Any] = {}
+        # dense_row_filter(req, rows) -> None | bool mask over the corpus rows | row positions: the dense channel then
+        # searches only those rows (DenseIndex.search(allow=...)); a "pkg.mod:func" string (settings.yaml impl_kwargs)
+        # is resolved like the reference's impl strings
+        if isinstance(dense_row_filter, str):
+            from .adapter import import_from_string
+            dense_row_filter = import_from_string(dense_row_filter)
+        if dense_row_filter is not None and not callable(dense_row_filter):
+            raise TypeError(f"dense_row_filter must be callable or a 'pkg.mod:func' string, got {type(dense_row_filter)}")
+        self.dense_row_filter = dense_row_filter
         if text_channel not in (None, "bm25"):
             raise ValueError(f"unknown text_channel {text_channel!r} (supported: 'bm25')")
         self._state = None
@@ -346,6 +356,7 @@ class DenseRetrievalBackend:
 
         dense_hits: List[Dict[str, Any]] = []
         dense_error = None
+        dense_filter = None
         k_eff = 0
         with span("Backend/DenseRerank", self.sink, trace_id):      # same span name as :332
             try:
@@ -359,7 +370,12 @@ class DenseRetrievalBackend:
                     # k up to max_k() (256) -- anything beyond is reported, never silently dropped
                     k = min(pool, len(state["rows"]))
                     k_eff = min(k, state["index"].max_k(1))
-                    sc, ids = state["index"].search(qv[None, :], k_eff)
+                    allow = self.dense_row_filter(req, state["rows"]) if self.dense_row_filter is not None else None
+                    if allow is None:
+                        sc, ids = state["index"].search(qv[None, :], k_eff)
+                    else:
+                        sc, ids = state["index"].search(qv[None, :], k_eff, allow=allow)
+                        dense_filter = state["index"].last_filter()
                     for s, i in zip(sc[0], ids[0]):
                         if i < 0:
                             continue
@@ -396,6 +412,8 @@ class DenseRetrievalBackend:
             "dense_error": dense_error,
             "text_error": text_error,
         }
+        if dense_filter is not None:
+            diagnostics["dense_filter"] = dense_filter
         return {"hits": fused, "diagnostics": diagnostics}
 
     def retrieve(self, req) -> RetrievalOut:

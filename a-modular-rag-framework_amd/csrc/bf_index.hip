@@ -64,6 +64,7 @@ namespace mrag {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef const __attribute__((address_space(1))) void* glb_vptr;
 
@@ -114,6 +115,7 @@ struct BfParams {
   long long* clock;         // 4 words or NULL: workgroup 0's s_memtime / s_memrealtime at entry and exit
   uint2* list;              // [T*S][256][QCAP]  {score bits, local row}: one 8-byte store per push
   int* counts;              // [T*S][256] entries left in the kept area
+  const uint32_t* allow;    // FILT instances: allow-set bitset (bit r%32 of word r/32), padded with zero words to whole tiles
 };
 
 __device__ __forceinline__ uint32_t f32_ord(float f) {
@@ -448,8 +450,11 @@ __device__ __forceinline__ void compact_owned(uint2* __restrict__ wg_list, int w
 //                                        8 -> 4 waves (2 x 2) of 128 x 128, ONE per SIMD, 512 VGPRs each
 // DESC: descriptor mode (IVF list scan) -- its block decoding and its partial-query-tile loads exist only in that
 // instance, the dense (t, s) instance carries neither.
-template <int DT, int NF, bool DESC>
+// FILT: filtered search (path M, dense instances only): rows whose bit in p.allow is clear score -inf in the epilogue,
+// exactly like the rows past the corpus in a partial last tile, so they are never listed and the certificates stay sound.
+template <int DT, int NF, bool DESC, bool FILT = false>
 __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_topk_kernel(BfParams p) {
+  static_assert(!(FILT && DESC), "filtered search runs the dense instance only");
   constexpr int WN = 16 / NF;            // waves along the query dimension
   constexpr int NW = 2 * WN;             // waves per workgroup
   constexpr int NT = 64 * NW;            // threads per workgroup
@@ -704,6 +709,11 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     stamp_on = DESC || (ti >= 60 && ti < 66);   // descriptor mode (IVF): one or two tiles per workgroup, stamp them all
     MRAG_STAMP(2);
 #endif
+    // allow-set words of this wave's 128 rows of the tile (wave-uniform: one scalar load, issued before the K loop so
+    // that its latency hides under the tile's MFMAs)
+    u32x4 allow_w = {~0u, ~0u, ~0u, ~0u};
+    if constexpr (FILT)
+      allow_w = *(const __attribute__((address_space(4))) u32x4*)(p.allow + ((size_t)(tile_lo + ti) * TM + wm * 128) / 32);
     kstep(std::false_type{});
     for (int kk = 1; kk < ksteps; ++kk) {
       kstep_sync();
@@ -748,6 +758,24 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 #pragma unroll
               for (int nf = 0; nf < NF; ++nf) acc[mf][nf][j] = -INFINITY;
             }
+      }
+      if constexpr (FILT) {
+        // rows row0 + mf*16 + j: word mf/2 of the wave's four, bit (mf&1)*16 + (lane>>4)*4 + j; an all-allowed half-tile
+        // skips the selects (wave-uniform branch)
+        if ((allow_w.x & allow_w.y & allow_w.z & allow_w.w) != ~0u) {
+          const uint32_t aw[4] = {allow_w.x, allow_w.y, allow_w.z, allow_w.w};
+          const int lsh = (elane >> 4) * 4;
+#pragma unroll
+          for (int mf = 0; mf < 8; ++mf) {
+            const uint32_t nib = aw[mf >> 1] >> ((mf & 1) * 16 + lsh);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (!((nib >> j) & 1u)) {
+#pragma unroll
+                for (int nf = 0; nf < NF; ++nf) acc[mf][nf][j] = -INFINITY;
+              }
+          }
+        }
       }
       float thr[NF];
       uint32_t* stat_cur = stat + (ti & 1) * TQ;        // certificate built from tiles <= ti
@@ -1125,6 +1153,7 @@ struct StreamParams {
   int ld, ksteps, n_rows, n_ctiles, nq, S, k;
   uint2* list;               // K4 layout: [(wg*256 + q)*QCAP + i]
   int* counts;               // [wg*256 + q]
+  const uint32_t* allow;     // FILT instances: allow-set bitset, as BfParams::allow
 };
 
 // one wave: cut query q's LDS list (<= 64*R entries) to its k best (sorted), raise tau
@@ -1159,7 +1188,7 @@ __device__ __forceinline__ void stream_compact(uint2* __restrict__ lst, int* __r
   if (lane == 0) cnt[q] = min(c, k);
 }
 
-template <int DT, int QPW, int LCAP>
+template <int DT, int QPW, int LCAP, bool FILT = false>
 __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p) {
   typedef typename Mfma<DT>::frag frag;
   typedef StreamLds<QPW, LCAP> L;
@@ -1220,6 +1249,9 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
   const int total = n_tiles * ksteps;
   int step = 0;
   for (int ti = 0; ti < n_tiles; ++ti) {
+    // FILT: the wave stages rows w*32 .. w*32+31 of the tile = allow-set word tile*8 + w (one scalar load, ahead of the K loop)
+    uint32_t allow_w = ~0u;
+    if constexpr (FILT) allow_w = *(const __attribute__((address_space(4))) uint32_t*)(p.allow + (size_t)(tile_lo + ti) * (TM / 32) + w);
     for (int kk = 0; kk < ksteps; ++kk, ++step) {
       if (step + 1 < total) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");   // the next stage may stay in flight
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1250,7 +1282,9 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = w * 32 + mf * 16 + (lane >> 4) * 4 + j;
-        sc[q * S_SC_LD + r] = (tile * TM + r < p.n_rows) ? acc[mf][j] : -INFINITY;
+        bool keep = tile * TM + r < p.n_rows;
+        if constexpr (FILT) keep = keep && ((allow_w >> (r & 31)) & 1u);
+        sc[q * S_SC_LD + r] = keep ? acc[mf][j] : -INFINITY;
       }
     acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
     acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1687,11 +1721,133 @@ __global__ void bf_wide_verify_kernel(const uint2* __restrict__ list, const int*
   need[q] = bad;
 }
 
+// ------------------------------------------------------------------------------------------
+// Filtered search (mrag_index_search_filtered): top-k over an allow-set of corpus rows.
+//   path M (mask):    the FILT instances of K2 / K2s score every row and drop the disallowed ones in the epilogue.
+//   path C (compact): the allowed rows are gathered into a scratch corpus (ascending, so the row-ascending tie-break
+//                     carries over), the unchanged search runs over them, and the ids are mapped back.
+// The allow-set lives on the device as a bitset (bit r%32 of word r/32) padded with zero words to whole 256-row tiles.
+// ------------------------------------------------------------------------------------------
+constexpr int FW_PER_THREAD = 4;                    // bitset words per thread of the count / emit kernels
+constexpr int FW_BLOCK = 256 * FW_PER_THREAD;       // words per block
+
+// byte mask (nonzero = allowed) -> bitset, one ballot per 64 rows; the grid covers every padded word
+__global__ void allow_pack_bytes_kernel(const uint8_t* __restrict__ bytes, int64_t n, uint32_t* __restrict__ bits) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long b = __ballot(r < n && bytes[r] != 0);
+  const int lane = threadIdx.x & 63;
+  if (lane == 0) bits[r >> 5] = (uint32_t)b;
+  if (lane == 32) bits[r >> 5] = (uint32_t)(b >> 32);
+}
+
+// word w of the bitset with the bits of rows >= n cleared
+__device__ __forceinline__ uint32_t allow_word(const uint32_t* __restrict__ bits, int64_t w, int64_t n) {
+  const int64_t rem = n - w * 32;
+  if (rem <= 0) return 0u;
+  const uint32_t x = bits[w];
+  return rem < 32 ? (x & ((1u << rem) - 1u)) : x;
+}
+
+// block-wide exclusive scan of one int per thread (256 threads); returns the block total through *total
+__device__ __forceinline__ int block_excl_scan256(int v, int* ws, int* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(incl, off);
+    if (lane >= off) incl += o;
+  }
+  if (lane == 63) ws[wv] = incl;
+  __syncthreads();
+  int before = 0;
+  for (int i = 0; i < wv; ++i) before += ws[i];
+  *total = ws[0] + ws[1] + ws[2] + ws[3];
+  __syncthreads();
+  return before + incl - v;
+}
+
+// allowed rows per block of FW_BLOCK words
+__global__ void allow_count_kernel(const uint32_t* __restrict__ bits, int64_t n, int64_t nwords, int* __restrict__ blk) {
+  __shared__ int ws[4];
+  const int64_t w0 = (int64_t)blockIdx.x * FW_BLOCK + threadIdx.x * FW_PER_THREAD;
+  int c = 0;
+#pragma unroll
+  for (int u = 0; u < FW_PER_THREAD; ++u)
+    if (w0 + u < nwords) c += __popc(allow_word(bits, w0 + u, n));
+  int tot;
+  (void)block_excl_scan256(c, ws, &tot);
+  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+}
+
+// one block: blk[] -> exclusive prefix, *total = allowed rows
+__global__ void allow_scan_kernel(int* __restrict__ blk, int nblk, int* __restrict__ total) {
+  __shared__ int ws[4];
+  int carry = 0;
+  for (int b0 = 0; b0 < nblk; b0 += 256) {
+    const int i = b0 + threadIdx.x;
+    const int v = i < nblk ? blk[i] : 0;
+    int tot;
+    const int ex = block_excl_scan256(v, ws, &tot);
+    if (i < nblk) blk[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+// ascending list of the allowed rows: thread t of block b owns words b*FW_BLOCK + t*FW_PER_THREAD .. + FW_PER_THREAD-1
+__global__ void allow_emit_kernel(const uint32_t* __restrict__ bits, int64_t n, int64_t nwords, const int* __restrict__ blk_excl,
+                                  int* __restrict__ rows) {
+  __shared__ int ws[4];
+  const int64_t w0 = (int64_t)blockIdx.x * FW_BLOCK + threadIdx.x * FW_PER_THREAD;
+  uint32_t x[FW_PER_THREAD];
+  int c = 0;
+#pragma unroll
+  for (int u = 0; u < FW_PER_THREAD; ++u) {
+    x[u] = w0 + u < nwords ? allow_word(bits, w0 + u, n) : 0u;
+    c += __popc(x[u]);
+  }
+  int tot;
+  int o = blk_excl[blockIdx.x] + block_excl_scan256(c, ws, &tot);
+#pragma unroll
+  for (int u = 0; u < FW_PER_THREAD; ++u)
+    for (uint32_t b = x[u]; b; b &= b - 1u) rows[o++] = (int)((w0 + u) * 32 + __builtin_ctz(b));
+}
+
+// compacted corpus: row i = stored row rows[i] for i < m, zeros up to m_pad (one wave per row, 16 B per lane)
+__global__ void gather_rows_kernel(const uint16_t* __restrict__ src, int ld, const int* __restrict__ rows, int64_t m,
+                                   int64_t m_pad, uint16_t* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= m_pad) return;
+  const int lane = threadIdx.x & 63, nv = ld / 8;
+  uint4* d = (uint4*)(dst + (size_t)i * ld);
+  if (i < m) {
+    const uint4* s = (const uint4*)(src + (size_t)rows[i] * ld);
+    for (int c = lane; c < nv; c += 64) d[c] = s[c];
+  } else {
+    for (int c = lane; c < nv; c += 64) d[c] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+// compacted position -> id_base + stored row; empty slots stay -1
+__global__ void remap_ids_kernel(int64_t* __restrict__ ids, int64_t tot, const int* __restrict__ rows, int64_t id_base) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < tot) {
+    const int64_t v = ids[i];
+    ids[i] = v < 0 ? -1 : (int64_t)rows[v] + id_base;
+  }
+}
+
 struct BfIndex : Object {
   int dim = 0, ld = 0, metric = 0, dtype = MRAG_F16;
   int64_t n = 0, cap_rows = 0, id_base = 0;
   uint16_t* rows = nullptr;
   DevBuf qbuf, lists, counts, stage_in, out_sc, out_id, clock;
+  DevBuf fbits, fwork, fcomp;               // filtered search: allow bitset | block counts, allowed count, row list | compacted rows
+  int last_fpath = -1;                      // path of the last filtered search (MRAG_FILTER_MASK / _COMPACT), -1 = none
+  int64_t last_fallowed = -1;               // its allowed-row count; -1 = still on the device (fwork word 0, read on demand)
+  uint32_t* h_fbits = nullptr;              // pinned staging of a host allow-set (pageable copies cost ~25 us per 1M rows)
+  size_t h_fbits_words = 0;
+  hipEvent_t ev_fbits = nullptr;            // recorded after the last copy out of h_fbits (it is rewritten only after it)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool timed = false, want_clock = false;
   void* q_cleared_buf = nullptr;            // query buffer bookkeeping: rows [q_dirty_rows, q_cleared_rows) are known to be zero
@@ -1699,6 +1855,9 @@ struct BfIndex : Object {
   ~BfIndex() override {
     if (rows) (void)hipFree(rows);
     qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
+    fbits.release(); fwork.release(); fcomp.release();
+    if (ev_fbits) (void)hipEventDestroy(ev_fbits);   // (the destroy path synchronised the device)
+    if (h_fbits) (void)hipHostFree(h_fbits);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
@@ -1779,12 +1938,15 @@ constexpr int MAX_QTILES_PER_LAUNCH = 64;
 // K2 launcher.  The kernel is templated on the wave tiling; only the 8-wave form (NF = 4) is built:
 // the 4-wave / one-wave-per-SIMD form (NF = 8, 256 accumulator registers per lane) is correct but
 // hipcc's allocation of the 256-AGPR tile spills into the K loop (98 ms vs 13.6 ms, round-1 measurement).
+// Column 2 = the filtered dense instance (FILT), picked only when p.allow is set.
 static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams& p) {
   typedef void (*K2Fn)(BfParams);
-  static const K2Fn fns[2][2] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>},
-                                 {bf_gemm_topk_kernel<MRAG_BF16, 4, false>, bf_gemm_topk_kernel<MRAG_BF16, 4, true>}};
-  static bool attr_done[2][2] = {};
-  const int di = dtype == MRAG_F16 ? 0 : 1, de = p.wg_desc ? 1 : 0;
+  static const K2Fn fns[2][3] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>,
+                                  bf_gemm_topk_kernel<MRAG_F16, 4, false, true>},
+                                 {bf_gemm_topk_kernel<MRAG_BF16, 4, false>, bf_gemm_topk_kernel<MRAG_BF16, 4, true>,
+                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>}};
+  static bool attr_done[2][3] = {};
+  const int di = dtype == MRAG_F16 ? 0 : 1, de = p.wg_desc ? 1 : (p.allow ? 2 : 0);
   if (!attr_done[di][de]) {
     MRAG_HIP(hipFuncSetAttribute((const void*)fns[di][de], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
     attr_done[di][de] = true;
@@ -1807,6 +1969,7 @@ int bf_launch(const BfLaunch& a) {
   p.dbg = 0;
   p.stamps = nullptr;
   p.clock = a.clock;
+  p.allow = a.wg_desc ? nullptr : a.allow;
 #ifdef MRAG_DIAG
   {
     p.dbg = MRAG_DIAG;
@@ -1852,17 +2015,20 @@ int bf_launch(const BfLaunch& a) {
   auto run_stream = [&](const uint16_t* queries, int64_t nq_s, float* out_scores, int64_t* out_ids, bool record_end,
                         size_t extra_counts) -> int {
     typedef void (*SFn)(StreamParams);
-    static const SFn sfns[2][2] = {{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
-                                   {bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>}};
+    static const SFn sfns[2][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
+                                       {bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>}},
+                                      {{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
+                                       {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}}};
     static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
-    static bool s_attr[2][2] = {};
+    static bool s_attr[2][2][2] = {};
     // the 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
     // 64-row chunk (1 x 1M x 768: 0.431 ms at k = 64 against 0.332 ms at k = 100 on the wide instance)
     const int wi = (a.k > 32) ? 1 : 0;
+    const int fi = a.allow ? 1 : 0;   // filtered instance (path M)
     const int grp = wi ? 8 : SQ;
-    if (!s_attr[di][wi]) {
-      MRAG_HIP(hipFuncSetAttribute((const void*)sfns[di][wi], hipFuncAttributeMaxDynamicSharedMemorySize, slds[wi]));
-      s_attr[di][wi] = true;
+    if (!s_attr[di][fi][wi]) {
+      MRAG_HIP(hipFuncSetAttribute((const void*)sfns[di][fi][wi], hipFuncAttributeMaxDynamicSharedMemorySize, slds[wi]));
+      s_attr[di][fi][wi] = true;
     }
     const int S = std::max(1, std::min(n_ctiles, 256));
     if (!extra_counts) {    // (a caller with extra_counts has sized both workspaces itself: ensure() does not keep contents)
@@ -1875,7 +2041,8 @@ int bf_launch(const BfLaunch& a) {
       sp.corpus = a.corpus; sp.queries = queries + (size_t)g0 * a.ld; sp.ld = a.ld; sp.ksteps = a.ld / BK;
       sp.n_rows = (int)a.n_rows; sp.n_ctiles = n_ctiles; sp.nq = (int)gq; sp.S = S; sp.k = a.k;
       sp.list = (uint2*)a.lists->p; sp.counts = (int*)a.counts->p;
-      hipLaunchKernelGGL(sfns[di][wi], dim3((unsigned)S), dim3(NTHR), slds[wi], stream, sp);
+      sp.allow = a.allow;
+      hipLaunchKernelGGL(sfns[di][fi][wi], dim3((unsigned)S), dim3(NTHR), slds[wi], stream, sp);
       MRAG_HIP(hipGetLastError());
       if (record_end && g0 + grp >= nq_s && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
       MergeParams mp;
@@ -2021,6 +2188,101 @@ int bf_launch(const BfLaunch& a) {
 }  // namespace mrag
 
 using namespace mrag;
+
+namespace mrag {
+// Search plumbing shared by mrag_index_search and mrag_index_search_filtered.
+// An empty result: every slot (-inf, -1); the K2 events bracket nothing.
+static int fill_empty(BfIndex* ix, float* d_sc, int64_t* d_id, int64_t tot, hipStream_t stream) {
+  hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_sc, d_id, tot);
+  MRAG_HIP(hipGetLastError());
+  MRAG_HIP(hipEventRecord(ix->ev[1], stream));
+  MRAG_HIP(hipEventRecord(ix->ev[2], stream));
+  return MRAG_OK;
+}
+
+// queries -> storage dtype in ix->qbuf, zero padded to a multiple of 256 rows
+static int prep_queries(BfIndex* ix, const void* queries, int64_t nq, int q_dtype, size_t esz, int normalize,
+                        int queries_is_device, hipStream_t stream) {
+  const int64_t nq_pad = round_up(nq, TQ) + SQ;   // + 16 zero rows: the last 8-query group of the k > 64 path reads a 16-row block
+  const size_t qbytes = (size_t)nq_pad * ix->ld * 2;
+  MRAG_TRY(ix->qbuf.ensure(qbytes));
+  const void* qsrc = queries;
+  if (!queries_is_device) {
+    const size_t bytes = (size_t)nq * ix->dim * esz;
+    MRAG_TRY(ix->stage_in.ensure(bytes));
+    MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, queries, bytes, hipMemcpyHostToDevice, stream));
+    qsrc = ix->stage_in.p;
+  }
+  // rows [nq, nq_pad) must be zero; only rows an earlier (larger) batch wrote need clearing again, so a stream of
+  // equal-sized searches (the online regime: one question per call) pays the fill launch once
+  if (ix->qbuf.p != ix->q_cleared_buf || nq_pad > ix->q_cleared_rows) {
+    MRAG_HIP(hipMemsetAsync(ix->qbuf.p, 0, qbytes, stream));
+    ix->q_cleared_buf = ix->qbuf.p; ix->q_cleared_rows = nq_pad; ix->q_dirty_rows = 0;
+  } else if (ix->q_dirty_rows > nq) {
+    MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(ix->q_dirty_rows - nq) * ix->ld * 2, stream));
+    ix->q_dirty_rows = nq;
+  }
+  ix->q_dirty_rows = std::max<int64_t>(ix->q_dirty_rows, nq);
+  return launch_prep_rows(qsrc, q_dtype, nq, ix->dim, ix->qbuf.p, ix->ld, ix->dtype,
+                          normalize && ix->metric == MRAG_METRIC_COSINE, stream);
+}
+
+// the launch of a search over all stored rows (prepared queries in ix->qbuf)
+static BfLaunch search_launch(BfIndex* ix, int64_t nq, int k, float* d_sc, int64_t* d_id, hipStream_t stream) {
+  BfLaunch a;
+  a.corpus = ix->rows;
+  a.queries = (const uint16_t*)ix->qbuf.p;
+  a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
+  a.nq = nq; a.n_rows = ix->n;
+  a.id_base = ix->id_base;
+  a.out_scores = d_sc; a.out_ids = d_id;
+  a.lists = &ix->lists; a.counts = &ix->counts;
+  a.stream = stream;
+  a.ev_k2_begin = ix->ev[1]; a.ev_k2_end = ix->ev[2];
+  return a;
+}
+
+// ---- filtered search: AUTO's choice between path M and path C ------------------------------------------------------
+// Path C pays a gather of the m allowed rows (read + write of m x ld x 2 B) and searches m rows; path M searches all n.
+// In the streaming regime (a handful of queries, HBM-bound) a search costs ~ its corpus bytes, so C costs ~ 3m against n;
+// the batch regime is MFMA-bound and C's gather is small next to the search.  Fractions from tools/perf_filter.py
+// (DESIGN.md "Filtered search"); env overrides for experiments: MRAG_FILTER_PATH=mask|compact (AUTO only),
+// MRAG_FILTER_STREAM_FRAC, MRAG_FILTER_BATCH_FRAC, MRAG_FILTER_SCRATCH_MB (cap on path C's compacted corpus).
+struct FilterRule {
+  int force = MRAG_FILTER_AUTO;
+  double stream_frac = 0.25;     // streaming regime: C when m <= stream_frac * n
+  double batch_frac = 0.80;      // batch regime: C when m <= batch_frac * n
+  double scratch_mb = 4096.0;    // C only when the compacted corpus fits this many MiB
+};
+static const FilterRule& filter_rule() {
+  static const FilterRule r = [] {
+    FilterRule f;
+    if (const char* e = getenv("MRAG_FILTER_PATH")) {
+      if (!strcmp(e, "mask")) f.force = MRAG_FILTER_MASK;
+      else if (!strcmp(e, "compact")) f.force = MRAG_FILTER_COMPACT;
+    }
+    if (const char* e = getenv("MRAG_FILTER_STREAM_FRAC")) f.stream_frac = atof(e);
+    if (const char* e = getenv("MRAG_FILTER_BATCH_FRAC")) f.batch_frac = atof(e);
+    if (const char* e = getenv("MRAG_FILTER_SCRATCH_MB")) f.scratch_mb = atof(e);
+    return f;
+  }();
+  return r;
+}
+static int choose_filter_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
+  const FilterRule& r = filter_rule();
+  if (r.force != MRAG_FILTER_AUTO) return r.force;
+  if ((double)round_up(m, TM) * ld * 2 > r.scratch_mb * 1048576.0) return MRAG_FILTER_MASK;
+  // the regime bf_launch picks for the unfiltered search over n rows
+  const int n_ctiles = (int)((n + TM - 1) / TM), m_ctiles = (int)((m + TM - 1) / TM);
+  const bool wide_batch = k > KMAX && nq > 32 && n_ctiles >= 64;
+  // k > 64 over fewer than 64 compacted tiles leaves the wide-batch path for the streaming kernel, 8 queries per launch:
+  // 1 000 queries x 1M x 768 at k = 200 and 1 % of the rows measured 6.0 ms compacted against 2.4 ms masked
+  if (wide_batch && m_ctiles < 64) return MRAG_FILTER_MASK;
+  const bool streaming = !wide_batch && (k > KMAX || (nq <= (k > 32 ? 8 : SQ) && n_ctiles >= 8));
+  return (double)m <= (streaming ? r.stream_frac : r.batch_frac) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
+}
+
+}  // namespace mrag
 
 extern "C" {
 
@@ -2177,45 +2439,10 @@ int mrag_index_search(mrag_handle h, const void* queries, int64_t nq, int q_dtyp
   }
   MRAG_HIP(hipEventRecord(ix->ev[0], stream));
   if (ix->n == 0) {
-    const int64_t tot = nq * k;
-    hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_sc, d_id, tot);
-    MRAG_HIP(hipGetLastError());
-    MRAG_HIP(hipEventRecord(ix->ev[1], stream));
-    MRAG_HIP(hipEventRecord(ix->ev[2], stream));
+    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));
   } else {
-    // queries -> storage dtype, zero padded to a multiple of 256 rows
-    const int64_t nq_pad = round_up(nq, TQ) + SQ;   // + 16 zero rows: the last 8-query group of the k > 64 path reads a 16-row block
-    const size_t qbytes = (size_t)nq_pad * ix->ld * 2;
-    MRAG_TRY(ix->qbuf.ensure(qbytes));
-    const void* qsrc = queries;
-    if (!queries_is_device) {
-      const size_t bytes = (size_t)nq * ix->dim * esz;
-      MRAG_TRY(ix->stage_in.ensure(bytes));
-      MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, queries, bytes, hipMemcpyHostToDevice, stream));
-      qsrc = ix->stage_in.p;
-    }
-    // rows [nq, nq_pad) must be zero; only rows an earlier (larger) batch wrote need clearing again, so a stream of
-    // equal-sized searches (the online regime: one question per call) pays the fill launch once
-    if (ix->qbuf.p != ix->q_cleared_buf || nq_pad > ix->q_cleared_rows) {
-      MRAG_HIP(hipMemsetAsync(ix->qbuf.p, 0, qbytes, stream));
-      ix->q_cleared_buf = ix->qbuf.p; ix->q_cleared_rows = nq_pad; ix->q_dirty_rows = 0;
-    } else if (ix->q_dirty_rows > nq) {
-      MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(ix->q_dirty_rows - nq) * ix->ld * 2, stream));
-      ix->q_dirty_rows = nq;
-    }
-    ix->q_dirty_rows = std::max<int64_t>(ix->q_dirty_rows, nq);
-    MRAG_TRY(launch_prep_rows(qsrc, q_dtype, nq, ix->dim, ix->qbuf.p, ix->ld, ix->dtype,
-                              normalize && ix->metric == MRAG_METRIC_COSINE, stream));
-    BfLaunch a;
-    a.corpus = ix->rows;
-    a.queries = (const uint16_t*)ix->qbuf.p;
-    a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
-    a.nq = nq; a.n_rows = ix->n;
-    a.id_base = ix->id_base;
-    a.out_scores = d_sc; a.out_ids = d_id;
-    a.lists = &ix->lists; a.counts = &ix->counts;
-    a.stream = stream;
-    a.ev_k2_begin = ix->ev[1]; a.ev_k2_end = ix->ev[2];
+    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
+    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
     if (ix->want_clock) {
       MRAG_TRY(ix->clock.ensure(64));
       MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
@@ -2230,6 +2457,170 @@ int mrag_index_search(mrag_handle h, const void* queries, int64_t nq, int q_dtyp
     MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
     MRAG_HIP(hipStreamSynchronize(stream));
   }
+  return MRAG_OK;
+}
+
+int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize,
+                               int queries_is_device, int k, const void* allow, int64_t allow_rows, int allow_format,
+                               int allow_is_device, int path, float* out_scores, int64_t* out_ids, int out_is_device,
+                               void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
+  if (k <= 0) return fail(MRAG_ERR_INVALID, "k must be positive");
+  if (k > KMAX_WIDE) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the top-k limit %d (see mrag_index_max_k)", k, KMAX_WIDE);
+  if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
+  if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
+  if (path != MRAG_FILTER_AUTO && path != MRAG_FILTER_MASK && path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown filter path %d", path);
+  if (nq == 0) return MRAG_OK;
+  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  if (!allow && ix->n > 0) return fail(MRAG_ERR_INVALID, "allow is NULL");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  ix->timed = false;
+  ix->last_fpath = -1;
+
+  float* d_sc = out_scores;
+  int64_t* d_id = out_ids;
+  if (!out_is_device) {
+    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
+    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
+    d_sc = (float*)ix->out_sc.p;
+    d_id = (int64_t*)ix->out_id.p;
+  }
+  const int64_t n = ix->n;
+  const int64_t nwords = round_up(std::max<int64_t>(n, 1), TM) / 32;   // bitset padded to whole tiles (the kernels read 8 words per tile)
+  const int64_t in_words = (n + 31) / 32;
+  const int nblk = (int)((nwords + FW_BLOCK - 1) / FW_BLOCK);
+  const size_t off_blk = 256, off_rows = (size_t)round_up(256 + (int64_t)nblk * 4, 256);
+  MRAG_TRY(ix->fbits.ensure((size_t)nwords * 4));
+  MRAG_TRY(ix->fwork.ensure(off_rows + (size_t)std::max<int64_t>(n, 1) * 4));
+  uint32_t* bits = (uint32_t*)ix->fbits.p;
+  int* d_total = (int*)ix->fwork.p;
+  int* d_blk = (int*)((char*)ix->fwork.p + off_blk);
+  int* d_rows = (int*)((char*)ix->fwork.p + off_rows);
+  int64_t m = -1;                     // allowed rows, when known on the host
+  bool counted = false;               // d_blk / d_total hold this call's counts
+  auto count_on_device = [&]() -> int {
+    hipLaunchKernelGGL(allow_count_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)bits, n, nwords, d_blk);
+    hipLaunchKernelGGL(allow_scan_kernel, dim3(1), dim3(256), 0, stream, d_blk, nblk, d_total);
+    MRAG_HIP(hipGetLastError());
+    counted = true;
+    return MRAG_OK;
+  };
+  // the whole-search figure (ev[0] .. ev[3]) covers the device work: with a host allow-set it starts after the
+  // host-side packing and count, at the bitset's upload
+  if (n == 0 || allow_is_device) MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  if (n == 0) {
+    m = 0;
+  } else if (!allow_is_device) {
+    // host allow-set: packed and counted here, no read-back
+    if (!ix->ev_fbits) MRAG_HIP(hipEventCreateWithFlags(&ix->ev_fbits, hipEventDisableTiming));
+    else MRAG_HIP(hipEventSynchronize(ix->ev_fbits));       // the previous copy out of the staging buffer is done
+    if (ix->h_fbits_words < (size_t)nwords) {
+      if (ix->h_fbits) MRAG_HIP(hipHostFree(ix->h_fbits));
+      ix->h_fbits = nullptr;
+      ix->h_fbits_words = 0;
+      MRAG_HIP(hipHostMalloc((void**)&ix->h_fbits, (size_t)nwords * 4, hipHostMallocDefault));
+      ix->h_fbits_words = (size_t)nwords;
+    }
+    uint32_t* hb = ix->h_fbits;
+    memset(hb, 0, (size_t)nwords * 4);
+    if (allow_format == MRAG_ALLOW_BITS32) {
+      memcpy(hb, allow, (size_t)in_words * 4);
+    } else {
+      const uint8_t* b = (const uint8_t*)allow;
+      for (int64_t r = 0; r < n; ++r) if (b[r]) hb[r >> 5] |= 1u << (r & 31);
+    }
+    if (n & 31) hb[in_words - 1] &= (1u << (n & 31)) - 1u;
+    m = 0;
+    for (int64_t w = 0; w < in_words; ++w) m += __builtin_popcount(hb[w]);
+    MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+    MRAG_HIP(hipMemcpyAsync(bits, hb, (size_t)nwords * 4, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipEventRecord(ix->ev_fbits, stream));
+  } else {
+    if (allow_format == MRAG_ALLOW_BITS32) {
+      MRAG_HIP(hipMemsetAsync(bits, 0, (size_t)nwords * 4, stream));
+      MRAG_HIP(hipMemcpyAsync(bits, allow, (size_t)in_words * 4, hipMemcpyDeviceToDevice, stream));
+    } else {
+      hipLaunchKernelGGL(allow_pack_bytes_kernel, dim3((unsigned)(nwords * 32 / 256)), dim3(256), 0, stream, (const uint8_t*)allow, n, bits);
+      MRAG_HIP(hipGetLastError());
+    }
+    MRAG_TRY(count_on_device());
+    if (path != MRAG_FILTER_MASK) {   // AUTO and path C need the count on the host: one read-back
+      int hm = 0;
+      MRAG_HIP(hipMemcpyAsync(&hm, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
+      MRAG_HIP(hipStreamSynchronize(stream));
+      m = hm;
+    }
+  }
+  const int chosen = path != MRAG_FILTER_AUTO ? path : choose_filter_path(nq, k, n, m, ix->ld);
+  if (m == 0) {
+    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));       // nothing allowed: no search kernel
+  } else if (chosen == MRAG_FILTER_MASK) {
+    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
+    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
+    a.allow = bits;
+    if (ix->want_clock) {
+      MRAG_TRY(ix->clock.ensure(64));
+      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
+      a.clock = (long long*)ix->clock.p;
+    }
+    MRAG_TRY(bf_launch(a));
+  } else {
+    // path C: ascending allowed rows -> compacted corpus (zero padded to a whole tile) -> the unchanged search -> ids
+    if (!counted) MRAG_TRY(count_on_device());
+    hipLaunchKernelGGL(allow_emit_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)bits, n, nwords,
+                       (const int*)d_blk, d_rows);
+    const int64_t m_pad = round_up(m, TM);
+    MRAG_TRY(ix->fcomp.ensure((size_t)m_pad * ix->ld * 2));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((m_pad + 3) / 4)), dim3(256), 0, stream, (const uint16_t*)ix->rows,
+                       ix->ld, (const int*)d_rows, m, m_pad, (uint16_t*)ix->fcomp.p);
+    MRAG_HIP(hipGetLastError());
+    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
+    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
+    a.corpus = (const uint16_t*)ix->fcomp.p;
+    a.n_rows = m;
+    a.id_base = 0;
+    if (ix->want_clock) {
+      MRAG_TRY(ix->clock.ensure(64));
+      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
+      a.clock = (long long*)ix->clock.p;
+    }
+    MRAG_TRY(bf_launch(a));
+    const int64_t tot = nq * k;
+    hipLaunchKernelGGL(remap_ids_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_id, tot, (const int*)d_rows,
+                       ix->id_base);
+    MRAG_HIP(hipGetLastError());
+  }
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->timed = true;
+  ix->last_fpath = chosen;
+  ix->last_fallowed = m;
+  if (!out_is_device) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+  }
+  return MRAG_OK;
+}
+
+int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_fpath < 0) return fail(MRAG_ERR_INVALID, "no completed filtered search on this index");
+  if (ix->last_fallowed < 0) {        // device allow-set, path M: the count is still on the device
+    MRAG_TRY(use_device(ix->device));
+    MRAG_HIP(hipEventSynchronize(ix->ev[3]));
+    int hm = 0;
+    MRAG_HIP(hipMemcpy(&hm, ix->fwork.p, sizeof(int), hipMemcpyDeviceToHost));
+    ix->last_fallowed = hm;
+  }
+  if (out_path) *out_path = ix->last_fpath;
+  if (out_allowed) *out_allowed = ix->last_fallowed;
   return MRAG_OK;
 }
 

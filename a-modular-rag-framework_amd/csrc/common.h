@@ -86,6 +86,8 @@ struct BfLaunch {
   hipStream_t stream = nullptr;
   hipEvent_t ev_k2_begin = nullptr, ev_k2_end = nullptr;   // optional
   long long* clock = nullptr;         // optional device long long[4]: batch kernel workgroup 0's clock stamps
+  const uint32_t* allow = nullptr;    // dense mode, optional: allow-set bitset over the corpus rows (bit r%32 of word r/32),
+                                      // padded with zero words to whole 256-row tiles; runs the filtered (FILT) instances
 };
 int bf_launch(const BfLaunch& a);
 int bf_max_k();

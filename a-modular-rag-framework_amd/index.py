@@ -47,6 +47,55 @@ def _as_buffer(x, dim: int):
     return a, a.ctypes.data, a.shape[0], _NP_DT[a.dtype], 0
 
 
+FILTER_PATHS = {"auto": N.FILTER_AUTO, "mask": N.FILTER_MASK, "compact": N.FILTER_COMPACT}
+_FILTER_NAMES = {N.FILTER_MASK: "mask", N.FILTER_COMPACT: "compact"}
+
+
+def allow_bits(allow, n: int) -> np.ndarray:
+    """Host allow-set -> the ABI's MRAG_ALLOW_BITS32 words (uint32 [ceil(n/32)], bit r%32 of word r/32).
+
+    ``allow`` is a bool / uint8 mask of length ``n`` (nonzero = allowed) or a 1-D array of row positions
+    ``0 .. n-1`` (any other integer dtype).  A wrong length, a position outside the rows or an input that is not
+    1-D raises ``ValueError``; nothing is clamped."""
+    if _is_torch(allow):
+        allow = allow.cpu().numpy()
+    a = np.asarray(allow)
+    if a.ndim != 1:
+        raise ValueError(f"allow must be 1-D, got shape {a.shape}")
+    if a.dtype == np.bool_ or a.dtype == np.uint8:
+        if a.shape[0] != n:
+            raise ValueError(f"allow mask has {a.shape[0]} entries, the index holds {n} rows")
+        mask = a.astype(np.bool_, copy=False)
+    elif np.issubdtype(a.dtype, np.integer):
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= n):
+            raise ValueError(f"allow row positions must lie in [0, {n}), got [{int(a.min())}, {int(a.max())}]")
+        mask = np.zeros(n, dtype=np.bool_)
+        mask[a] = True
+    else:
+        raise ValueError(f"allow must be a bool/uint8 mask or integer row positions, got dtype {a.dtype}")
+    words = (n + 31) // 32
+    packed = np.zeros(words * 4, dtype=np.uint8)
+    packed[:(n + 7) // 8] = np.packbits(mask, bitorder="little")
+    return packed.view("<u4")
+
+
+def _allow_buffer(allow, n: int, device: int):
+    """-> (keepalive, pointer, allow_format, is_device).  Device tensors (bool / uint8, on the index's device) go to the
+    ABI as a byte mask, packed on the device; everything else is packed here."""
+    if _is_torch(allow) and allow.is_cuda:
+        import torch
+        if allow.dim() != 1 or allow.shape[0] != n:
+            raise ValueError(f"device allow mask must be 1-D with {n} entries, got {tuple(allow.shape)}")
+        if allow.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"device allow must be a bool/uint8 mask (row positions: pass a host array), got {allow.dtype}")
+        if allow.device.index != device:
+            raise ValueError(f"allow mask is on {allow.device}, the index on cuda:{device}")
+        t = allow.contiguous()
+        return t, t.data_ptr(), N.ALLOW_BYTES, 1
+    bits = np.ascontiguousarray(allow_bits(allow, n))
+    return bits, bits.ctypes.data, N.ALLOW_BITS32, 0
+
+
 def _stream_ptr(stream) -> Optional[int]:
     if stream is None:
         return None
@@ -108,15 +157,23 @@ class DenseIndex:
         return out
 
     # -- search ---------------------------------------------------------------------------
-    def search(self, queries, k: int, normalize: Optional[bool] = None, stream=None, out=None
-               ) -> Tuple["np.ndarray", "np.ndarray"]:
+    def search(self, queries, k: int, normalize: Optional[bool] = None, stream=None, out=None, allow=None,
+               filter_path: str = "auto") -> Tuple["np.ndarray", "np.ndarray"]:
         """-> (scores [nq,k] fp32 descending, ids [nq,k] int64; (-inf, -1) past the corpus).
 
         Host queries give numpy results (the call returns when they have landed); CUDA
         tensors give CUDA tensors, written asynchronously on ``stream`` (default: torch's
-        current stream).  ``out=(scores, ids)`` reuses caller tensors."""
+        current stream).  ``out=(scores, ids)`` reuses caller tensors.
+
+        ``allow`` restricts the search to some rows (``mrag_index_search_filtered``): a bool / uint8 mask over the
+        ``len(self)`` local rows (numpy, or a torch tensor on the host or on this index's device) or a host array of
+        row positions.  Slots past the number of allowed rows are (-inf, -1).  ``filter_path``: "auto", "mask" (the
+        search kernels drop disallowed rows) or "compact" (the allowed rows are gathered and searched alone); see
+        :meth:`last_filter`.  ``allow=None`` is the plain search."""
         if normalize is None:
             normalize = self.metric == "cosine"
+        if allow is not None:
+            return self._search_filtered(queries, k, normalize, stream, out, allow, filter_path)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         if is_dev:
             import torch
@@ -135,6 +192,40 @@ class DenseIndex:
         N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k),
                                             sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
         return sc, ids
+
+    def _search_filtered(self, queries, k, normalize, stream, out, allow, filter_path):
+        if filter_path not in FILTER_PATHS:
+            raise ValueError(f"filter_path must be one of {sorted(FILTER_PATHS)}, got {filter_path!r}")
+        n = len(self)
+        akeep, aptr, afmt, adev = _allow_buffer(allow, n, self.device)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        path = FILTER_PATHS[filter_path]
+        if is_dev or adev:
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
+        if is_dev:
+            if out is None:
+                sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
+                ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
+            else:
+                sc, ids = out
+            N.check(self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k), aptr, n, afmt,
+                                                         adev, path, sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
+            return sc, ids
+        sc = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        N.check(self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k), aptr, n, afmt,
+                                                     adev, path, sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+        del akeep
+        return sc, ids
+
+    def last_filter(self) -> dict:
+        """Path and allowed-row count of the last filtered search on this index (``mrag_index_last_filter``):
+        ``{"path": "mask" | "compact", "allowed": m}``."""
+        p, m = C.c_int(0), C.c_int64(0)
+        N.check(self._lib.mrag_index_last_filter(self._h, C.byref(p), C.byref(m)))
+        return {"path": _FILTER_NAMES[p.value], "allowed": m.value}
 
     def max_k(self, nq: int = 1) -> int:
         """Largest ``k`` :meth:`search` serves (``mrag_index_max_k``); above it the library raises

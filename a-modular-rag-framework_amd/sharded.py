@@ -281,20 +281,32 @@ class ShardedDenseIndex:
         if len(self.index) > self.hi - self.lo:
             raise ValueError("more rows than this shard owns")
 
+    def local_allow(self, allow):
+        """Global allow-set (bool / uint8 mask over the ``n_total`` rows, or global row positions) -> this rank's
+        local mask over rows ``[lo, hi)`` (numpy bool), as :meth:`DenseIndex.search` takes it."""
+        from .index import allow_bits
+        words = allow_bits(allow, self.n_total)        # validates length / range / shape like the single index
+        mask = np.unpackbits(words.view(np.uint8), bitorder="little")[:self.n_total].astype(np.bool_)
+        return mask[self.lo:self.hi]
+
     def search(self, queries, k: int, nthreads: int = 0, merge: str = "auto", force_collective: bool = False,
-               pipeline: bool = False, **kw) -> Tuple[np.ndarray, np.ndarray]:
+               pipeline: bool = False, allow=None, **kw) -> Tuple[np.ndarray, np.ndarray]:
         """Local search over this rank's rows, then the exchange + merge; every rank returns the full result.
         ``pipeline=True`` cuts the batch in two halves: the all-gather of half A is in flight (``async_op``, on the
         process group's own stream) while the local search of half B runs -- same result, bit for bit (every query's
         answer depends on its own rows of the batch only).  ``self.last_phases`` holds the call's per-phase
         milliseconds: local_ms, pack_ms, gather_ms (in pipeline mode: the part of the collective the local search
-        did NOT cover), merge_ms, d2h_ms."""
+        did NOT cover), merge_ms, d2h_ms.
+        ``allow`` (global rows: a mask over ``n_total`` or global row positions) restricts the search to those rows:
+        every rank searches the allowed rows of its own shard; a rank with none contributes (-inf, -1) slots."""
         import torch
         import torch.distributed as dist
         world = dist.get_world_size(self.group) if dist.is_initialized() else 1
         is_cuda = torch.is_tensor(queries) and queries.is_cuda
         id_bases = [shard_bounds(self.n_total, self.world, r)[0] for r in range(self.world)]
         nq = int(queries.shape[0])
+        if allow is not None:
+            kw = dict(kw, allow=self.local_allow(allow))
         if self.index is not None and is_cuda and "out" not in kw:
             # reuse the device result tensors across calls (they are consumed by the exchange below)
             key = (nq, int(k), queries.device)

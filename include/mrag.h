@@ -105,6 +105,30 @@ int mrag_index_last_wide_redone(int64_t* out_queries);
 int mrag_index_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize,
                       int queries_is_device, int k, float* out_scores, int64_t* out_ids,
                       int out_is_device, void* stream);
+/* Filtered search: the top-k of the ALLOWED rows only (restrict to a set of documents, a tenant or a date range, leave
+ * out passages already shown; the reference's DenseReranker.score scores a candidate pool, retrieval_backend.py:215-247).
+ * `allow` is an allow-set over the local rows 0 .. size-1 (before id_base): MRAG_ALLOW_BITS32 = uint32 words, bit r%32
+ * of word r/32 (ceil(size/32) words); MRAG_ALLOW_BYTES = one byte per row, nonzero = allowed (packed to bits on the
+ * device).  allow_rows must equal the index size.  Order, k limits and the (-inf, -1) tail as mrag_index_search: slots
+ * past the number of allowed rows are (-inf, -1); no allowed row gives an all-(-inf, -1) result.  An all-allowed set
+ * returns exactly what mrag_index_search returns.
+ * path: MRAG_FILTER_MASK scores every row and drops the disallowed ones inside the search kernels (no extra memory);
+ * MRAG_FILTER_COMPACT gathers the allowed rows into an index-owned scratch corpus and searches only those (work
+ * proportional to the allowed rows); MRAG_FILTER_AUTO picks one from (nq, k, size, allowed rows, dim).
+ * Sync behaviour with device outputs: a HOST allow-set is counted on the host, so AUTO and both paths stay
+ * asynchronous on `stream` (the mask itself is copied to the device before the call returns).  With a DEVICE allow-set,
+ * MRAG_FILTER_MASK is fully asynchronous (capturable); AUTO and MRAG_FILTER_COMPACT read the allowed-row count back
+ * once (one stream synchronisation).  The wide path (64 < k <= 256, more than 32 queries) synchronises once as in
+ * mrag_index_search.  Host outputs: the call returns after the results have landed. */
+enum mrag_filter_path { MRAG_FILTER_AUTO = 0, MRAG_FILTER_MASK = 1, MRAG_FILTER_COMPACT = 2 };
+enum mrag_allow_format { MRAG_ALLOW_BITS32 = 0, MRAG_ALLOW_BYTES = 1 };
+int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize,
+                               int queries_is_device, int k, const void* allow, int64_t allow_rows, int allow_format,
+                               int allow_is_device, int path, float* out_scores, int64_t* out_ids, int out_is_device,
+                               void* stream);
+/* path the LAST filtered search on this handle took (MRAG_FILTER_MASK / MRAG_FILTER_COMPACT) and its allowed-row count.
+ * Blocks until that search is done when the count is still on the device (device allow-set, MRAG_FILTER_MASK). */
+int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed);
 /* the re-ranker's candidate lookup by row id.  Replaces the 1 + ceil(N/bs) embed calls +
  * N x _cosine of DenseReranker.score (retrieval_backend.py:227-245) for candidates whose rows are already
  * in the index: out_scores[i] = <query, stored row row_ids[i]> (the cosine when rows and query are
