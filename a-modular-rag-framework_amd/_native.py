@@ -11,6 +11,7 @@ METRIC_COSINE, METRIC_IP = 0, 1
 POOL_MEAN, POOL_CLS = 0, 1
 FILTER_AUTO, FILTER_MASK, FILTER_COMPACT = 0, 1, 2
 ALLOW_BITS32, ALLOW_BYTES = 0, 1
+IVF_FILTER_AUTO, IVF_FILTER_PROBE, IVF_FILTER_EXACT = 0, 1, 2
 
 ERR_NAMES = {-1: "MRAG_ERR_INVALID", -2: "MRAG_ERR_NO_DEVICE", -3: "MRAG_ERR_HIP", -4: "MRAG_ERR_OOM",
              -5: "MRAG_ERR_UNSUPPORTED"}
@@ -83,6 +84,10 @@ SIGNATURES = {
     "mrag_ivf_set_id_base": [_h, _i64],
     "mrag_ivf_get_assignments": [_h, _vp, _i, _vp],
     "mrag_ivf_search": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "mrag_ivf_search_filtered": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i, _vp],
+    "mrag_ivf_allowed_per_list": [_h, _vp, _i64, _i, _i, _vp, _i, _vp],
+    "mrag_ivf_choose_filter_path": [_i64, _i, _i, _i, _i64, _i64, _i, C.POINTER(_i)],
+    "mrag_ivf_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i)],
     "mrag_ivf_last_timing": [_h, _fp, _fp, C.POINTER(_i64), C.POINTER(_i)],
     "mrag_bm25_create": [_i, _i64, _i64, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(_h)],
     "mrag_bm25_destroy": [_h],

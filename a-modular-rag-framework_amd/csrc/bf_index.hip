@@ -1842,12 +1842,9 @@ struct BfIndex : Object {
   int64_t n = 0, cap_rows = 0, id_base = 0;
   uint16_t* rows = nullptr;
   DevBuf qbuf, lists, counts, stage_in, out_sc, out_id, clock;
-  DevBuf fbits, fwork, fcomp;               // filtered search: allow bitset | block counts, allowed count, row list | compacted rows
+  FilterWork fw;                            // filtered search: allow bitset, counts, compacted rows
   int last_fpath = -1;                      // path of the last filtered search (MRAG_FILTER_MASK / _COMPACT), -1 = none
   int64_t last_fallowed = -1;               // its allowed-row count; -1 = still on the device (fwork word 0, read on demand)
-  uint32_t* h_fbits = nullptr;              // pinned staging of a host allow-set (pageable copies cost ~25 us per 1M rows)
-  size_t h_fbits_words = 0;
-  hipEvent_t ev_fbits = nullptr;            // recorded after the last copy out of h_fbits (it is rewritten only after it)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool timed = false, want_clock = false;
   void* q_cleared_buf = nullptr;            // query buffer bookkeeping: rows [q_dirty_rows, q_cleared_rows) are known to be zero
@@ -1855,9 +1852,7 @@ struct BfIndex : Object {
   ~BfIndex() override {
     if (rows) (void)hipFree(rows);
     qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
-    fbits.release(); fwork.release(); fcomp.release();
-    if (ev_fbits) (void)hipEventDestroy(ev_fbits);   // (the destroy path synchronised the device)
-    if (h_fbits) (void)hipHostFree(h_fbits);
+    fw.release();   // (the destroy path synchronised the device)
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
@@ -2268,7 +2263,7 @@ static const FilterRule& filter_rule() {
   }();
   return r;
 }
-static int choose_filter_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
+int filter_choose_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
   const FilterRule& r = filter_rule();
   if (r.force != MRAG_FILTER_AUTO) return r.force;
   if ((double)round_up(m, TM) * ld * 2 > r.scratch_mb * 1048576.0) return MRAG_FILTER_MASK;
@@ -2280,6 +2275,117 @@ static int choose_filter_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
   if (wide_batch && m_ctiles < 64) return MRAG_FILTER_MASK;
   const bool streaming = !wide_batch && (k > KMAX || (nq <= (k > 32 ? 8 : SQ) && n_ctiles >= 8));
   return (double)m <= (streaming ? r.stream_frac : r.batch_frac) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
+}
+
+// ---- filtered search over prepared operands (mrag_index_search_filtered, and the exact path of mrag_ivf_search_filtered)
+void FilterWork::release() {
+  fbits.release(); fwork.release(); fcomp.release();
+  if (ev_fbits) (void)hipEventDestroy(ev_fbits);
+  if (h_fbits) (void)hipHostFree(h_fbits);
+  ev_fbits = nullptr; h_fbits = nullptr; h_fbits_words = 0;
+}
+
+// layout of FilterWork::fwork: allowed count (word 0) | per-block counts at byte 256 | ascending allowed rows
+static int64_t filter_nwords(int64_t n) { return round_up(std::max<int64_t>(n, 1), TM) / 32; }   // bitset padded to whole tiles (the kernels read 8 words per tile)
+static int filter_nblk(int64_t n) { return (int)((filter_nwords(n) + FW_BLOCK - 1) / FW_BLOCK); }
+static size_t filter_off_rows(int64_t n) { return (size_t)round_up(256 + (int64_t)filter_nblk(n) * 4, 256); }
+
+static int filter_count_on_device(FilterWork& w, int64_t n, hipStream_t stream) {
+  const int64_t nwords = filter_nwords(n);
+  const int nblk = filter_nblk(n);
+  int* d_blk = (int*)((char*)w.fwork.p + 256);
+  hipLaunchKernelGGL(allow_count_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)w.fbits.p, n, nwords, d_blk);
+  hipLaunchKernelGGL(allow_scan_kernel, dim3(1), dim3(256), 0, stream, d_blk, nblk, (int*)w.fwork.p);
+  MRAG_HIP(hipGetLastError());
+  w.counted = true;
+  return MRAG_OK;
+}
+
+int filter_upload(FilterWork& w, const void* allow, int64_t n, int allow_format, int allow_is_device, bool want_count, int64_t* m_out,
+                  hipEvent_t ev_begin, hipStream_t stream) {
+  const int64_t nwords = filter_nwords(n);
+  const int64_t in_words = (n + 31) / 32;
+  MRAG_TRY(w.fbits.ensure((size_t)nwords * 4));
+  MRAG_TRY(w.fwork.ensure(filter_off_rows(n) + (size_t)std::max<int64_t>(n, 1) * 4));
+  uint32_t* bits = (uint32_t*)w.fbits.p;
+  w.counted = false;                  // d_blk / the allowed count hold this call's counts
+  int64_t m = -1;
+  if (n == 0 || allow_is_device) MRAG_HIP(hipEventRecord(ev_begin, stream));
+  if (n == 0) {
+    m = 0;
+  } else if (!allow_is_device) {
+    // host allow-set: packed and counted here, no read-back
+    if (!w.ev_fbits) MRAG_HIP(hipEventCreateWithFlags(&w.ev_fbits, hipEventDisableTiming));
+    else MRAG_HIP(hipEventSynchronize(w.ev_fbits));       // the previous copy out of the staging buffer is done
+    if (w.h_fbits_words < (size_t)nwords) {
+      if (w.h_fbits) MRAG_HIP(hipHostFree(w.h_fbits));
+      w.h_fbits = nullptr;
+      w.h_fbits_words = 0;
+      MRAG_HIP(hipHostMalloc((void**)&w.h_fbits, (size_t)nwords * 4, hipHostMallocDefault));
+      w.h_fbits_words = (size_t)nwords;
+    }
+    uint32_t* hb = w.h_fbits;
+    memset(hb, 0, (size_t)nwords * 4);
+    if (allow_format == MRAG_ALLOW_BITS32) {
+      memcpy(hb, allow, (size_t)in_words * 4);
+    } else {
+      const uint8_t* b = (const uint8_t*)allow;
+      for (int64_t r = 0; r < n; ++r) if (b[r]) hb[r >> 5] |= 1u << (r & 31);
+    }
+    if (n & 31) hb[in_words - 1] &= (1u << (n & 31)) - 1u;
+    m = 0;
+    for (int64_t i = 0; i < in_words; ++i) m += __builtin_popcount(hb[i]);
+    MRAG_HIP(hipEventRecord(ev_begin, stream));
+    MRAG_HIP(hipMemcpyAsync(bits, hb, (size_t)nwords * 4, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipEventRecord(w.ev_fbits, stream));
+  } else {
+    if (allow_format == MRAG_ALLOW_BITS32) {
+      MRAG_HIP(hipMemsetAsync(bits, 0, (size_t)nwords * 4, stream));
+      MRAG_HIP(hipMemcpyAsync(bits, allow, (size_t)in_words * 4, hipMemcpyDeviceToDevice, stream));
+    } else {
+      hipLaunchKernelGGL(allow_pack_bytes_kernel, dim3((unsigned)(nwords * 32 / 256)), dim3(256), 0, stream, (const uint8_t*)allow, n, bits);
+      MRAG_HIP(hipGetLastError());
+    }
+    MRAG_TRY(filter_count_on_device(w, n, stream));
+    if (want_count) {                 // the caller needs the count on the host: one read-back
+      int hm = 0;
+      MRAG_HIP(hipMemcpyAsync(&hm, w.fwork.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+      MRAG_HIP(hipStreamSynchronize(stream));
+      m = hm;
+    }
+  }
+  *m_out = m;
+  return MRAG_OK;
+}
+
+int filter_search(FilterWork& w, BfLaunch a, int path, int64_t m, hipStream_t stream) {
+  const int64_t n = a.n_rows;
+  if (path == MRAG_FILTER_MASK) {
+    a.allow = (const uint32_t*)w.fbits.p;
+    return bf_launch(a);
+  }
+  // path C: ascending allowed rows -> compacted corpus (zero padded to a whole tile) -> the unchanged search -> ids
+  if (!w.counted) MRAG_TRY(filter_count_on_device(w, n, stream));
+  const int nblk = filter_nblk(n);
+  const int* d_blk = (const int*)((char*)w.fwork.p + 256);
+  int* d_rows = (int*)((char*)w.fwork.p + filter_off_rows(n));
+  hipLaunchKernelGGL(allow_emit_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)w.fbits.p, n, filter_nwords(n),
+                     d_blk, d_rows);
+  const int64_t m_pad = round_up(m, TM);
+  MRAG_TRY(w.fcomp.ensure((size_t)m_pad * a.ld * 2));
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((m_pad + 3) / 4)), dim3(256), 0, stream, a.corpus, a.ld, (const int*)d_rows,
+                     m, m_pad, (uint16_t*)w.fcomp.p);
+  MRAG_HIP(hipGetLastError());
+  const int64_t id_base = a.id_base;
+  a.corpus = (const uint16_t*)w.fcomp.p;
+  a.n_rows = m;
+  a.id_base = 0;
+  MRAG_TRY(bf_launch(a));
+  const int64_t tot = a.nq * a.k;
+  hipLaunchKernelGGL(remap_ids_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, a.out_ids, tot, (const int*)d_rows,
+                     id_base);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
 }
 
 }  // namespace mrag
@@ -2492,109 +2598,22 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
     d_id = (int64_t*)ix->out_id.p;
   }
   const int64_t n = ix->n;
-  const int64_t nwords = round_up(std::max<int64_t>(n, 1), TM) / 32;   // bitset padded to whole tiles (the kernels read 8 words per tile)
-  const int64_t in_words = (n + 31) / 32;
-  const int nblk = (int)((nwords + FW_BLOCK - 1) / FW_BLOCK);
-  const size_t off_blk = 256, off_rows = (size_t)round_up(256 + (int64_t)nblk * 4, 256);
-  MRAG_TRY(ix->fbits.ensure((size_t)nwords * 4));
-  MRAG_TRY(ix->fwork.ensure(off_rows + (size_t)std::max<int64_t>(n, 1) * 4));
-  uint32_t* bits = (uint32_t*)ix->fbits.p;
-  int* d_total = (int*)ix->fwork.p;
-  int* d_blk = (int*)((char*)ix->fwork.p + off_blk);
-  int* d_rows = (int*)((char*)ix->fwork.p + off_rows);
   int64_t m = -1;                     // allowed rows, when known on the host
-  bool counted = false;               // d_blk / d_total hold this call's counts
-  auto count_on_device = [&]() -> int {
-    hipLaunchKernelGGL(allow_count_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)bits, n, nwords, d_blk);
-    hipLaunchKernelGGL(allow_scan_kernel, dim3(1), dim3(256), 0, stream, d_blk, nblk, d_total);
-    MRAG_HIP(hipGetLastError());
-    counted = true;
-    return MRAG_OK;
-  };
   // the whole-search figure (ev[0] .. ev[3]) covers the device work: with a host allow-set it starts after the
   // host-side packing and count, at the bitset's upload
-  if (n == 0 || allow_is_device) MRAG_HIP(hipEventRecord(ix->ev[0], stream));
-  if (n == 0) {
-    m = 0;
-  } else if (!allow_is_device) {
-    // host allow-set: packed and counted here, no read-back
-    if (!ix->ev_fbits) MRAG_HIP(hipEventCreateWithFlags(&ix->ev_fbits, hipEventDisableTiming));
-    else MRAG_HIP(hipEventSynchronize(ix->ev_fbits));       // the previous copy out of the staging buffer is done
-    if (ix->h_fbits_words < (size_t)nwords) {
-      if (ix->h_fbits) MRAG_HIP(hipHostFree(ix->h_fbits));
-      ix->h_fbits = nullptr;
-      ix->h_fbits_words = 0;
-      MRAG_HIP(hipHostMalloc((void**)&ix->h_fbits, (size_t)nwords * 4, hipHostMallocDefault));
-      ix->h_fbits_words = (size_t)nwords;
-    }
-    uint32_t* hb = ix->h_fbits;
-    memset(hb, 0, (size_t)nwords * 4);
-    if (allow_format == MRAG_ALLOW_BITS32) {
-      memcpy(hb, allow, (size_t)in_words * 4);
-    } else {
-      const uint8_t* b = (const uint8_t*)allow;
-      for (int64_t r = 0; r < n; ++r) if (b[r]) hb[r >> 5] |= 1u << (r & 31);
-    }
-    if (n & 31) hb[in_words - 1] &= (1u << (n & 31)) - 1u;
-    m = 0;
-    for (int64_t w = 0; w < in_words; ++w) m += __builtin_popcount(hb[w]);
-    MRAG_HIP(hipEventRecord(ix->ev[0], stream));
-    MRAG_HIP(hipMemcpyAsync(bits, hb, (size_t)nwords * 4, hipMemcpyHostToDevice, stream));
-    MRAG_HIP(hipEventRecord(ix->ev_fbits, stream));
-  } else {
-    if (allow_format == MRAG_ALLOW_BITS32) {
-      MRAG_HIP(hipMemsetAsync(bits, 0, (size_t)nwords * 4, stream));
-      MRAG_HIP(hipMemcpyAsync(bits, allow, (size_t)in_words * 4, hipMemcpyDeviceToDevice, stream));
-    } else {
-      hipLaunchKernelGGL(allow_pack_bytes_kernel, dim3((unsigned)(nwords * 32 / 256)), dim3(256), 0, stream, (const uint8_t*)allow, n, bits);
-      MRAG_HIP(hipGetLastError());
-    }
-    MRAG_TRY(count_on_device());
-    if (path != MRAG_FILTER_MASK) {   // AUTO and path C need the count on the host: one read-back
-      int hm = 0;
-      MRAG_HIP(hipMemcpyAsync(&hm, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
-      MRAG_HIP(hipStreamSynchronize(stream));
-      m = hm;
-    }
-  }
-  const int chosen = path != MRAG_FILTER_AUTO ? path : choose_filter_path(nq, k, n, m, ix->ld);
+  MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_FILTER_MASK, &m, ix->ev[0], stream));
+  const int chosen = path != MRAG_FILTER_AUTO ? path : filter_choose_path(nq, k, n, m, ix->ld);
   if (m == 0) {
     MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));       // nothing allowed: no search kernel
-  } else if (chosen == MRAG_FILTER_MASK) {
-    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
-    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
-    a.allow = bits;
-    if (ix->want_clock) {
-      MRAG_TRY(ix->clock.ensure(64));
-      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
-      a.clock = (long long*)ix->clock.p;
-    }
-    MRAG_TRY(bf_launch(a));
   } else {
-    // path C: ascending allowed rows -> compacted corpus (zero padded to a whole tile) -> the unchanged search -> ids
-    if (!counted) MRAG_TRY(count_on_device());
-    hipLaunchKernelGGL(allow_emit_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, (const uint32_t*)bits, n, nwords,
-                       (const int*)d_blk, d_rows);
-    const int64_t m_pad = round_up(m, TM);
-    MRAG_TRY(ix->fcomp.ensure((size_t)m_pad * ix->ld * 2));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((m_pad + 3) / 4)), dim3(256), 0, stream, (const uint16_t*)ix->rows,
-                       ix->ld, (const int*)d_rows, m, m_pad, (uint16_t*)ix->fcomp.p);
-    MRAG_HIP(hipGetLastError());
     MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
     BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
-    a.corpus = (const uint16_t*)ix->fcomp.p;
-    a.n_rows = m;
-    a.id_base = 0;
     if (ix->want_clock) {
       MRAG_TRY(ix->clock.ensure(64));
       MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
       a.clock = (long long*)ix->clock.p;
     }
-    MRAG_TRY(bf_launch(a));
-    const int64_t tot = nq * k;
-    hipLaunchKernelGGL(remap_ids_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_id, tot, (const int*)d_rows,
-                       ix->id_base);
-    MRAG_HIP(hipGetLastError());
+    MRAG_TRY(filter_search(ix->fw, a, chosen, m, stream));
   }
   MRAG_HIP(hipEventRecord(ix->ev[3], stream));
   ix->timed = true;
@@ -2616,7 +2635,7 @@ int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed) {
     MRAG_TRY(use_device(ix->device));
     MRAG_HIP(hipEventSynchronize(ix->ev[3]));
     int hm = 0;
-    MRAG_HIP(hipMemcpy(&hm, ix->fwork.p, sizeof(int), hipMemcpyDeviceToHost));
+    MRAG_HIP(hipMemcpy(&hm, ix->fw.fwork.p, sizeof(int), hipMemcpyDeviceToHost));
     ix->last_fallowed = hm;
   }
   if (out_path) *out_path = ix->last_fpath;

@@ -90,6 +90,28 @@ struct BfLaunch {
                                       // padded with zero words to whole 256-row tiles; runs the filtered (FILT) instances
 };
 int bf_launch(const BfLaunch& a);
+
+// Filtered dense search over prepared operands (bf_index.hip), shared by mrag_index_search_filtered and the exact path
+// of mrag_ivf_search_filtered.
+struct FilterWork {
+  DevBuf fbits;                       // allow-set bitset over the corpus rows, padded with zero words to whole 256-row tiles
+  DevBuf fwork;                       // allowed count (int, word 0) | per-block counts | ascending allowed rows
+  DevBuf fcomp;                       // path C: the compacted corpus
+  uint32_t* h_fbits = nullptr;        // pinned staging of a host allow-set (pageable copies cost ~25 us per 1M rows)
+  size_t h_fbits_words = 0;
+  hipEvent_t ev_fbits = nullptr;      // recorded after the last copy out of h_fbits (it is rewritten only after it)
+  bool counted = false;               // fwork holds the counts of the current allow-set
+  void release();
+};
+// allow-set (host or device, MRAG_ALLOW_BITS32 / _BYTES) over n rows -> w.fbits.  *m_out = allowed rows when known on
+// the host (host allow-set; device allow-set with want_count: one read-back), else -1 (the count is in fwork word 0).
+// ev_begin is recorded where the device work of the search starts.
+int filter_upload(FilterWork& w, const void* allow, int64_t n, int allow_format, int allow_is_device, bool want_count, int64_t* m_out,
+                  hipEvent_t ev_begin, hipStream_t stream);
+// AUTO's choice between MRAG_FILTER_MASK and MRAG_FILTER_COMPACT for m allowed rows of n (m >= 0)
+int filter_choose_path(int64_t nq, int k, int64_t n, int64_t m, int ld);
+// the search restricted to the uploaded allow-set: `a` is the unfiltered dense launch over a.n_rows rows (m > 0 for path C)
+int filter_search(FilterWork& w, BfLaunch a, int path, int64_t m, hipStream_t stream);
 int bf_max_k();
 int bf_max_k_wide();
 int64_t bf_round_rows(int64_t n);     // rows rounded up to the kernel's tile (256)
@@ -112,13 +134,15 @@ constexpr int IVFS_DENSE_ROWS = 128;    // corpus rows per descriptor of the den
 int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype, int64_t zero_row, const int* desc, int n_desc,
               const int* n_desc_dev, const int64_t* gq, float* S, hipStream_t stream, long long* dbg = nullptr);
 // pinfo: int4 per (query, probe) = (float offset of the pair's score segment: low, high; its rows; its first stored row)
+// stored_bits != nullptr: filtered selection, a stored position whose bit is clear is never selected
 int ivfs_select_lists(const float* S, const void* pinfo, int nprobe, int64_t nq, int k, const int64_t* row_ids,
-                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream);
+                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits = nullptr);
 int ivfs_dense_n_desc(int64_t nq, int n_rows);
 // count_out != nullptr: every selected row r with row_weight[r] > 0 also bumps count_out[r] (the IVF search's
 // "queries per list" histogram, otherwise a kernel of its own)
 int ivfs_dense_topk(const uint16_t* corpus, int n_rows, const uint16_t* queries, int64_t nq, int ld, int dtype, int k, int* desc,
                     float* S, float* out_scores, int64_t* out_ids, hipStream_t stream, int* count_out = nullptr,
-                    const int* row_weight = nullptr);
+                    const int* row_weight = nullptr, const uint32_t* row_bits = nullptr);
+// (row_bits != nullptr: only rows whose bit is set are selected; missing slots are (-inf, -1))
 
 }  // namespace mrag

@@ -44,7 +44,21 @@ struct IvfIndex : Object {
   int n_chunks = 0;               // chunks of the last search (mrag_ivf_last_timing sums their scan brackets)
   DevBuf stats;                   // device accumulators of the last search: int64 rows streamed by the list scans, int64 workgroups
   bool timed = false, end_recorded = false;
+  // filtered search (mrag_ivf_search_filtered): the allow-set over the original rows (fw.fbits), its image over the stored
+  // positions, the per-list allowed counts and the live-list bitset
+  FilterWork fw;
+  DevBuf fstored;                 // uint32 bitset over the n_sorted stored positions
+  DevBuf flist;                   // int counts [nlist] | int live-list count | uint32 live bits [round256(nlist) / 32] | int caller counts [nlist]
+  DevBuf flast;                   // int allowed rows, int live lists of the last path-P search (copied at its end, read on demand)
+  int32_t* h_lallow = nullptr;    // pinned staging of a host list_allowed
+  hipEvent_t ev_lallow = nullptr; // recorded after the last copy out of h_lallow
+  int last_fpath = -1;            // MRAG_IVF_FILTER_PROBE / _EXACT of the last filtered search, -1 = none
+  int64_t last_fallowed = -1;     // its allowed rows (-1: still on the device, flast word 0)
+  int last_flive = -1;            // its live lists (-1: on the device, flast word 1; -2: not computed, path E)
   ~IvfIndex() override {
+    fw.release(); fstored.release(); flist.release(); flast.release();
+    if (ev_lallow) (void)hipEventDestroy(ev_lallow);
+    if (h_lallow) (void)hipHostFree(h_lallow);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : cev) if (e) (void)hipEventDestroy(e);
     for (void* p : {(void*)cen, (void*)raw, (void*)assign, (void*)sorted, (void*)row_ids}) if (p) (void)hipFree(p);
@@ -247,6 +261,46 @@ __global__ __launch_bounds__(1024) void ivf_plan_scores_kernel(const int* __rest
 __global__ void ivf_all_lists_kernel(int64_t* __restrict__ probes, int64_t npairs, int nlist) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < npairs) probes[i] = i % nlist;
+}
+
+// ---- filtered search (path P) -------------------------------------------------------------------------------------
+// allow-set over the original rows -> bitset over the stored positions (bit p = row_ids[p] >= 0 && allowed, one ballot per
+// 64 positions) + allowed rows per list.  One workgroup per list: a list's positions start on a whole tile and its tiles are
+// its own, so it writes only its own words and its count needs no atomics (the same count every run).
+__global__ __launch_bounds__(256) void ivf_allow_stored_kernel(const uint32_t* __restrict__ allow, const int64_t* __restrict__ row_ids,
+                                                               const int* __restrict__ list_count, const int* __restrict__ list_tile_lo,
+                                                               uint32_t* __restrict__ stored, int* __restrict__ counts) {
+  __shared__ int part[4];
+  const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int lc = list_count[l];
+  const int64_t p0 = (int64_t)list_tile_lo[l] * 256;
+  int c = 0;
+  for (int base = 0; base < lc; base += 256) {          // (covers the list's padding positions too: their bits are 0)
+    const int64_t pos = p0 + base + tid;
+    const int64_t r = base + tid < lc ? row_ids[pos] : -1;
+    const bool a = r >= 0 && ((allow[r >> 5] >> (r & 31)) & 1u);
+    const unsigned long long b = __ballot(a);
+    if (lane == 0) stored[pos >> 5] = (uint32_t)b;
+    if (lane == 32) stored[pos >> 5] = (uint32_t)(b >> 32);
+    if (lane == 0) c += __popcll(b);
+  }
+  if (lane == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) counts[l] = part[0] + part[1] + part[2] + part[3];
+}
+
+// per-list allowed counts -> live-list bitset (bit l = counts[l] > 0), zero words up to whole 256-list tiles (the dense
+// kernels over the centroids read whole tiles); *n_live (zeroed by the caller) += live lists
+__global__ void ivf_live_bits_kernel(const int* __restrict__ counts, int nlist, uint32_t* __restrict__ live, int* __restrict__ n_live) {
+  const int l = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const unsigned long long b = __ballot(l < nlist && counts[l] > 0);
+  if (lane == 0) { live[l >> 5] = (uint32_t)b; if (b) atomicAdd(n_live, (int)__popcll(b)); }
+  if (lane == 32) live[l >> 5] = (uint32_t)(b >> 32);
+}
+
+__global__ void ivf_fill_empty_kernel(float* __restrict__ sc, int64_t* __restrict__ ids, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { sc[i] = -INFINITY; ids[i] = -1; }
 }
 
 __global__ void ids_to_i32_kernel(const int64_t* __restrict__ ids, int64_t n, int32_t* __restrict__ out) {
@@ -559,9 +613,31 @@ int mrag_ivf_get_assignments(mrag_handle h, int32_t* out, int out_is_device, voi
   return MRAG_OK;
 }
 
+// The score buffer of the "score segments + select" regime: MRAG_IVF_SCORES_MB, default 16 GiB, 0 = always the fused kernel.
+static int64_t ivf_scores_cap() {
+  static const int64_t cap = [] { const char* e = getenv("MRAG_IVF_SCORES_MB"); return (int64_t)(e ? atoll(e) : 16384) << 20; }();
+  return cap;
+}
+
+// Large batches are cut so that a chunk's score segments fit the score buffer even if every pair probes the longest
+// list (ivf_scan.hip's regime, without a host round trip); results are per query, so the chunks are independent.
+// Every chunk streams the probed lists again, so the default buffer is generous (16 GiB of the 288: C5's 10 000 x 32
+// pairs over 5 M rows need 1.6 GB, their no-round-trip bound ~5 GB); MRAG_IVF_SCORES_MB sets it, 0 = fused regime.
+// -> queries per chunk (the last chunk may be shorter)
+static int64_t ivf_chunk_queries(const IvfIndex* ix, int64_t nq, int nprobe) {
+  const int64_t cap = ivf_scores_cap();
+  const int64_t per_query = std::max<int64_t>((int64_t)std::min(nprobe, 256) * ivfs_pitch(ix->max_list_rows), ivfs_pitch(ix->nlist)) * 4;
+  int64_t chunk = std::max<int64_t>(1024, cap / std::max<int64_t>(per_query, 1) / IVFS_QUERIES * IVFS_QUERIES);
+  if (!(cap > 0 && nprobe <= 256 && nq > chunk)) chunk = nq;
+  else chunk = round_up((nq + (nq + chunk - 1) / chunk - 1) / ((nq + chunk - 1) / chunk), IVFS_QUERIES);   // equal chunks
+  return chunk;
+}
+
 // one chunk of a search (<= 2^20 queries whose score segments fit the buffer): probe selection, plan, list scan, selection
+// live_bits / stored_bits (filtered search, path P): probe only live lists, select only allowed stored positions
 static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
-                            int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx) {
+                            int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx,
+                            const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr) {
   hipEvent_t ev_scan0 = ix->cev[2 * chunk_idx], ev_scan1 = ix->cev[2 * chunk_idx + 1];
   unsigned long long* d_stats = (unsigned long long*)ix->stats.p;
 
@@ -583,7 +659,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
   // The list scan (and the probe selection before it) runs as "score segments + select" (ivf_scan.hip) whenever the
   // fp32 segments of this search fit the score buffer; otherwise (exhaustive probing of a big index) as the fused
   // GEMM + top-k kernel in descriptor mode.  MRAG_IVF_SCORES_MB = 0 forces the fused path (tests).
-  static const int64_t scores_cap = [] { const char* e = getenv("MRAG_IVF_SCORES_MB"); return (int64_t)(e ? atoll(e) : 16384) << 20; }();
+  const int64_t scores_cap = ivf_scores_cap();
   const int nl = ix->nlist;
   MRAG_TRY(ix->plan.ensure((size_t)(4 * nl + 4) * 4 + (size_t)nl * 8));
   int* d_lcount = (int*)ix->plan.p;      // queries per list | first group of the list | cursor | first descriptor | descriptor count, score floats | float offset of the list's score blocks
@@ -603,7 +679,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     MRAG_TRY(ix->scores.ensure((size_t)(round_up(nq, IVFS_QUERIES) * ivfs_pitch(ix->nlist) * 4)));
     MRAG_TRY(ivfs_dense_topk(ix->cen, ix->nlist, (const uint16_t*)ix->qbuf.p, nq, ix->ld, ix->dtype, nprobe, (int*)ix->sdesc.p,
                              (float*)ix->scores.p, (float*)ix->tmp_sc.p, (int64_t*)ix->tmp_id.p, stream, d_lcount,
-                             (const int*)ix->d_list_count.p));
+                             (const int*)ix->d_list_count.p, live_bits));
     counted = true;
   } else {
     BfLaunch a;
@@ -611,6 +687,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     a.nq = nq; a.n_rows = ix->nlist;
     a.out_scores = (float*)ix->tmp_sc.p; a.out_ids = (int64_t*)ix->tmp_id.p;
     a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
+    a.allow = live_bits;                 // (filtered: dead lists are never probed; a pair without a list gets probe id -1)
     MRAG_TRY(bf_launch(a));
   }
   // 2) device: list -> the queries that probe it, cut into workgroups of <= 128 (score segments) or <= 256 (fused
@@ -632,6 +709,8 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
   // scan is launched over the BOUND of the workgroup count and reads the real one from device memory.
   const int64_t max_pitch = ivfs_pitch(ix->max_list_rows);
   const bool no_sync = use_scores && (int64_t)npairs * max_pitch * 4 <= scores_cap;
+  // (a filtered search only comes here when it fits: mrag_ivf_search_filtered runs path E otherwise)
+  if (stored_bits && !no_sync) return fail(MRAG_ERR_INVALID, "filtered IVF chunk does not fit the score buffer");
   int plan_out[3] = {0, 0, 0};
   const bool planned_scores = use_scores;
   if (use_scores) {
@@ -675,7 +754,8 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
       MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p, n_wg, nullptr,
                          (const int64_t*)ix->gq.p, (float*)ix->scores.p, stream));
     }
-    MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream));
+    MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
+                               stored_bits));
     MRAG_HIP(hipEventRecord(ev_scan1, stream));
   } else {
     MRAG_HIP(hipMemsetAsync(ix->gq.p, 0xFF, (size_t)wg_bound * 256 * 8, stream));   // (the gather below reads whole 256-slot slabs)
@@ -736,15 +816,7 @@ int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype,
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
   MRAG_TRY(ivf_finalize(ix, stream));
-  // Large batches are cut so that a chunk's score segments fit the score buffer even if every pair probes the longest
-  // list (ivf_scan.hip's regime, without a host round trip); results are per query, so the chunks are independent.
-  // Every chunk streams the probed lists again, so the default buffer is generous (16 GiB of the 288: C5's 10 000 x 32
-  // pairs over 5 M rows need 1.6 GB, their no-round-trip bound ~5 GB); MRAG_IVF_SCORES_MB sets it, 0 = fused regime.
-  static const int64_t cap = [] { const char* e = getenv("MRAG_IVF_SCORES_MB"); return (int64_t)(e ? atoll(e) : 16384) << 20; }();
-  const int64_t per_query = std::max<int64_t>((int64_t)std::min(nprobe, 256) * ivfs_pitch(ix->max_list_rows), ivfs_pitch(ix->nlist)) * 4;
-  int64_t chunk = std::max<int64_t>(1024, cap / std::max<int64_t>(per_query, 1) / IVFS_QUERIES * IVFS_QUERIES);
-  if (!(cap > 0 && nprobe <= 256 && nq > chunk)) chunk = nq;
-  else chunk = round_up((nq + (nq + chunk - 1) / chunk - 1) / ((nq + chunk - 1) / chunk), IVFS_QUERIES);   // equal chunks
+  const int64_t chunk = ivf_chunk_queries(ix, nq, nprobe);
   if (chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
   const int n_chunks = (int)((nq + chunk - 1) / chunk);
   while ((int)ix->cev.size() < 2 * n_chunks) {
@@ -773,6 +845,253 @@ int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype,
   // host buffers (pageable query / result memory) must not be touched by the caller before the copies are done; with
   // queries and results in device memory the search is fully asynchronous on `stream`
   if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+}  // extern "C"
+
+namespace mrag {
+
+// ---- filtered search: AUTO's choice between path P (probe the live lists) and path E (filtered brute force) ------------
+// P scans ~ nprobe * n / nlist rows per query whatever the allow-set; E scans the m allowed rows (the dense filtered search
+// over ix->raw, itself masked or compacted).  E when m <= c * nprobe * n / nlist: c_batch for batches, c_stream for a few
+// queries (the streaming regime, HBM-bound).  Constants from tools/perf_ivf_filter.py (DESIGN.md "Filtered IVF search");
+// env overrides for experiments: MRAG_IVF_FILTER_PATH=probe|exact (AUTO only), MRAG_IVF_FILTER_C, MRAG_IVF_FILTER_C_STREAM.
+struct IvfFilterRule {
+  int force = MRAG_IVF_FILTER_AUTO;
+  double c_batch = 8.0;          // 10 000 queries: E and P cross at 5-10 % of the rows (c ~ 9)
+  double c_stream = 24.0;        // 1 and 16 queries: they cross at ~20-25 % (c ~ 25)
+  int64_t stream_nq = 16;        // batches up to this many queries count as the streaming regime
+};
+static const IvfFilterRule& ivf_filter_rule() {
+  static const IvfFilterRule r = [] {
+    IvfFilterRule f;
+    if (const char* e = getenv("MRAG_IVF_FILTER_PATH")) {
+      if (!strcmp(e, "probe")) f.force = MRAG_IVF_FILTER_PROBE;
+      else if (!strcmp(e, "exact")) f.force = MRAG_IVF_FILTER_EXACT;
+    }
+    if (const char* e = getenv("MRAG_IVF_FILTER_C")) f.c_batch = atof(e);
+    if (const char* e = getenv("MRAG_IVF_FILTER_C_STREAM")) f.c_stream = atof(e);
+    return f;
+  }();
+  return r;
+}
+static int ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t n, int64_t m, int dim) {
+  (void)k; (void)dim;            // (both paths pay them alike: the dot products per row, the top-k per query)
+  if (nprobe >= nlist) return MRAG_IVF_FILTER_EXACT;
+  const IvfFilterRule& r = ivf_filter_rule();
+  if (r.force != MRAG_IVF_FILTER_AUTO) return r.force;
+  const double probed = (double)nprobe * (double)n / (double)nlist;
+  return (double)m <= (nq <= r.stream_nq ? r.c_stream : r.c_batch) * probed ? MRAG_IVF_FILTER_EXACT : MRAG_IVF_FILTER_PROBE;
+}
+
+// flist layout (ints): counts [nlist] | live-list count (+ 3 pad) | live bits [round256(nlist) / 32] | caller counts [nlist]
+static int* flist_counts(IvfIndex* ix) { return (int*)ix->flist.p; }
+static int* flist_nlive(IvfIndex* ix) { return (int*)ix->flist.p + ix->nlist; }
+static uint32_t* flist_live(IvfIndex* ix) { return (uint32_t*)ix->flist.p + ix->nlist + 4; }
+static int* flist_caller(IvfIndex* ix) { return (int*)ix->flist.p + ix->nlist + 4 + bf_round_rows(ix->nlist) / 32; }
+
+// (after filter_upload) the allow-set's image over the stored positions and the allowed rows per list
+static int ivf_filter_stored(IvfIndex* ix, hipStream_t stream) {
+  MRAG_TRY(ix->fstored.ensure((size_t)(ix->n_sorted / 32) * 4));
+  MRAG_TRY(ix->flist.ensure(((size_t)2 * ix->nlist + 4 + (size_t)bf_round_rows(ix->nlist) / 32) * 4));
+  hipLaunchKernelGGL(ivf_allow_stored_kernel, dim3((unsigned)ix->nlist), dim3(256), 0, stream, (const uint32_t*)ix->fw.fbits.p,
+                     (const int64_t*)ix->row_ids, (const int*)ix->d_list_count.p, (const int*)ix->d_list_tile_lo.p,
+                     (uint32_t*)ix->fstored.p, flist_counts(ix));
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
+
+static int check_allow_args(IvfIndex* ix, const void* allow, int64_t allow_rows, int allow_format) {
+  if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
+  if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
+  if (!allow && ix->n > 0) return fail(MRAG_ERR_INVALID, "allow is NULL");
+  return MRAG_OK;
+}
+
+}  // namespace mrag
+
+extern "C" {
+
+int mrag_ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t total_rows, int64_t allowed_rows, int dim, int* out_path) {
+  if (!out_path) return fail(MRAG_ERR_INVALID, "out_path is NULL");
+  if (nq < 0 || k <= 0 || nprobe <= 0 || nlist <= 0 || total_rows < 0 || allowed_rows < 0 || allowed_rows > total_rows || dim <= 0)
+    return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe / nlist / rows / dim");
+  *out_path = ivf_choose_filter_path(nq, k, nprobe, nlist, total_rows, allowed_rows, dim);
+  return MRAG_OK;
+}
+
+int mrag_ivf_allowed_per_list(mrag_handle h, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                              int32_t* out_counts, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_allow_args(ix, allow, allow_rows, allow_format));
+  if (!out_counts) return fail(MRAG_ERR_INVALID, "out_counts is NULL");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  MRAG_TRY(ivf_finalize(ix, stream));
+  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  int64_t m = -1;
+  MRAG_TRY(filter_upload(ix->fw, allow, ix->n, allow_format, allow_is_device, false, &m, ix->ev[1], stream));
+  MRAG_TRY(ivf_filter_stored(ix, stream));
+  MRAG_HIP(hipMemcpyAsync(out_counts, flist_counts(ix), (size_t)ix->nlist * 4, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  // (the handle's buffers are in use on `stream` until here: a later search on another stream waits for it)
+  ix->timed = false;
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->end_recorded = true;
+  if (!out_is_device || !allow_is_device) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
+                             int k, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                             const int32_t* list_allowed, int path, float* out_scores, int64_t* out_ids, int out_is_device,
+                             void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
+  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
+  MRAG_TRY(check_allow_args(ix, allow, allow_rows, allow_format));
+  if (path != MRAG_IVF_FILTER_AUTO && path != MRAG_IVF_FILTER_PROBE && path != MRAG_IVF_FILTER_EXACT)
+    return fail(MRAG_ERR_INVALID, "unknown IVF filter path %d", path);
+  nprobe = std::min(nprobe, ix->nlist);
+  if (nprobe > bf_max_k_wide() && nprobe < ix->nlist)
+    return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", nprobe, bf_max_k_wide(), ix->nlist);
+  if (nq == 0) return MRAG_OK;
+  if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
+  if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  MRAG_TRY(ivf_finalize(ix, stream));
+  // path P runs the score-segment regime only, every chunk without a host round trip (ivf_search_chunk's no_sync case);
+  // where that does not hold (nprobe == nlist, MRAG_IVF_SCORES_MB = 0, segments too big) the search runs path E
+  const int64_t cap = ivf_scores_cap();
+  const int64_t chunk = ivf_chunk_queries(ix, nq, nprobe);
+  if (chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
+  const bool probe_fits = cap > 0 && nprobe < ix->nlist && chunk * nprobe * ivfs_pitch(ix->max_list_rows) * 4 <= cap;
+  ix->timed = false;
+  ix->last_fpath = -1;
+  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  const int64_t n = ix->n;
+  int64_t m = -1;
+  MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_IVF_FILTER_PROBE, &m, ix->ev[0], stream));
+  int chosen = path != MRAG_IVF_FILTER_AUTO ? path : ivf_choose_filter_path(nq, k, nprobe, ix->nlist, n, m, ix->dim);
+  if (!probe_fits) chosen = MRAG_IVF_FILTER_EXACT;
+  if (chosen == MRAG_IVF_FILTER_EXACT && m < 0) {   // (forced P that cannot run as P, device allow-set: E needs the count)
+    int hm = 0;
+    MRAG_HIP(hipMemcpyAsync(&hm, ix->fw.fwork.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+    m = hm;
+  }
+  MRAG_TRY(ix->stats.ensure(16));
+  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
+  while ((int)ix->cev.size() < 2) {
+    hipEvent_t e = nullptr;
+    MRAG_HIP(hipEventCreate(&e));
+    ix->cev.push_back(e);
+  }
+  int live = -2;
+  if (chosen == MRAG_IVF_FILTER_EXACT || m == 0) {
+    float* d_sc = out_scores;
+    int64_t* d_id = out_ids;
+    if (!out_is_device) {
+      MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
+      MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
+      d_sc = (float*)ix->out_sc.p;
+      d_id = (int64_t*)ix->out_id.p;
+    }
+    if (m == 0) {                      // nothing allowed: no search kernel
+      MRAG_HIP(hipEventRecord(ix->cev[0], stream));
+      hipLaunchKernelGGL(ivf_fill_empty_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, stream, d_sc, d_id, nq * k);
+      MRAG_HIP(hipGetLastError());
+      MRAG_HIP(hipEventRecord(ix->cev[1], stream));
+    } else {
+      // path E: the dense filtered search over the rows in arrival order (ix->raw: whole zeroed 256-row tiles), ids = row + id_base
+      const int64_t nq_pad = bf_round_rows(nq) + 16;   // + 16 zero rows: the streaming kernel's last 8-query group reads a 16-row block
+      MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
+      MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));
+      MRAG_TRY(ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream));
+      BfLaunch a;
+      a.corpus = ix->raw; a.queries = (const uint16_t*)ix->qbuf.p; a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
+      a.nq = nq; a.n_rows = n; a.id_base = ix->id_base;
+      a.out_scores = d_sc; a.out_ids = d_id;
+      a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
+      a.ev_k2_begin = ix->cev[0]; a.ev_k2_end = ix->cev[1];
+      MRAG_TRY(filter_search(ix->fw, a, filter_choose_path(nq, k, n, m, ix->ld), m, stream));
+    }
+    ix->n_chunks = 1;
+    if (!out_is_device) {
+      MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
+      MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+    }
+    if (m == 0) live = 0;
+  } else {
+    // path P: allow-set -> stored positions + per-list counts; liveness from those counts or the caller's (sharded: global)
+    MRAG_TRY(ivf_filter_stored(ix, stream));
+    const int* cnt = flist_counts(ix);
+    if (list_allowed && allow_is_device) {        // (list_allowed lives where the allow-set does)
+      cnt = list_allowed;
+    } else if (list_allowed) {
+      if (!ix->ev_lallow) {
+        MRAG_HIP(hipEventCreateWithFlags(&ix->ev_lallow, hipEventDisableTiming));
+        MRAG_HIP(hipHostMalloc((void**)&ix->h_lallow, (size_t)ix->nlist * 4, hipHostMallocDefault));
+      } else {
+        MRAG_HIP(hipEventSynchronize(ix->ev_lallow));   // the previous copy out of the staging buffer is done
+      }
+      memcpy(ix->h_lallow, list_allowed, (size_t)ix->nlist * 4);
+      MRAG_HIP(hipMemcpyAsync(flist_caller(ix), ix->h_lallow, (size_t)ix->nlist * 4, hipMemcpyHostToDevice, stream));
+      MRAG_HIP(hipEventRecord(ix->ev_lallow, stream));
+      cnt = flist_caller(ix);
+    }
+    MRAG_HIP(hipMemsetAsync(flist_nlive(ix), 0, 4, stream));
+    hipLaunchKernelGGL(ivf_live_bits_kernel, dim3((unsigned)(bf_round_rows(ix->nlist) / 256)), dim3(256), 0, stream, cnt, ix->nlist,
+                       flist_live(ix), flist_nlive(ix));
+    MRAG_HIP(hipGetLastError());
+    const int n_chunks = (int)((nq + chunk - 1) / chunk);
+    while ((int)ix->cev.size() < 2 * n_chunks) {
+      hipEvent_t e = nullptr;
+      MRAG_HIP(hipEventCreate(&e));
+      ix->cev.push_back(e);
+    }
+    const size_t qrow = (size_t)ix->dim * esize(q_dtype);
+    for (int c = 0; c < n_chunks; ++c) {
+      const int64_t off = (int64_t)c * chunk, mq = std::min(chunk, nq - off);
+      MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, mq, q_dtype, normalize, queries_is_device, nprobe, k,
+                                out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c,
+                                (const uint32_t*)flist_live(ix), (const uint32_t*)ix->fstored.p));
+    }
+    ix->n_chunks = n_chunks;
+    // the figures last_filter reports, kept apart from the words the next call overwrites (no sync here)
+    MRAG_TRY(ix->flast.ensure(8));
+    MRAG_HIP(hipMemcpyAsync(ix->flast.p, ix->fw.fwork.p, 4, hipMemcpyDeviceToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync((int*)ix->flast.p + 1, flist_nlive(ix), 4, hipMemcpyDeviceToDevice, stream));
+    live = -1;
+  }
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->end_recorded = true;
+  ix->timed = true;
+  ix->last_fpath = chosen;
+  ix->last_fallowed = m;
+  ix->last_flive = live;
+  if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_ivf_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed, int* out_live_lists) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_fpath < 0) return fail(MRAG_ERR_INVALID, "no completed filtered search on this index");
+  MRAG_TRY(use_device(ix->device));
+  if (ix->last_fallowed < 0 || ix->last_flive == -1) {   // path P: still on the device
+    MRAG_HIP(hipEventSynchronize(ix->ev[3]));
+    int h[2] = {0, 0};
+    MRAG_HIP(hipMemcpy(h, ix->flast.p, 8, hipMemcpyDeviceToHost));
+    if (ix->last_fallowed < 0) ix->last_fallowed = h[0];
+    if (ix->last_flive == -1) ix->last_flive = h[1];
+  }
+  if (out_path) *out_path = ix->last_fpath;
+  if (out_allowed) *out_allowed = ix->last_fallowed;
+  if (out_live_lists) *out_live_lists = ix->last_flive;
   return MRAG_OK;
 }
 

@@ -519,6 +519,13 @@ struct SelParams {
   int* count_out;             // dense, optional: histogram of the selected rows ...
   const int* row_weight;      // ... counting only rows with row_weight > 0
 };
+// the filtered (FILT) instances: SelParams + a bitset over the rows (dense: over the segment's rows = the lists of the
+// probe selection; lists: over the STORED positions).  A row whose bit is clear is never selected.  (A struct of its own:
+// the unfiltered instances keep their kernel arguments.)
+struct SelParamsF {
+  SelParams p;
+  const uint32_t* bits;
+};
 
 // Selection = (score desc, original row asc), exact.
 //   fast path  every thread keeps its <= 32 scores in registers (entry e = tid + 256 i).  The k-th largest of the 256
@@ -528,8 +535,10 @@ struct SelParams {
 //              The bound comes from a bitwise bisection (2 bits per step) with ballot counts -- 16 light steps.
 //   serial path (more than 8192 candidates, or a shortlist overflow = degenerate ties): k rounds of a workgroup-wide
 //              arg-max over the segments, rows looked up only for entries tied with the current score.
-template <bool DENSE>
-__device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
+// FILT: entries whose bit in `bits` is clear get the "empty" key 0 and never enter a shortlist or an arg-max round; fewer
+// selectable entries than k leave the tail (-inf, -1).
+template <bool DENSE, bool FILT = false>
+__device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint32_t* __restrict__ bits = nullptr) {
   __shared__ const float* seg_ptr[SEL_MAXP];
   __shared__ int seg_cnt[SEL_MAXP];
   __shared__ int seg_pre[SEL_MAXP + 1];
@@ -594,12 +603,17 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
   __syncthreads();
   const int total = seg_pre[np];
   auto row_at = [&](int j, int t) -> int64_t { return DENSE ? (int64_t)t : p.row_ids[seg_row0[j] + t]; };
+  auto selectable = [&](int j, int t) -> bool {   // FILT: the entry's bit (dense: row t; lists: stored position)
+    const int64_t pos = DENSE ? (int64_t)t : seg_row0[j] + t;
+    return (bits[pos >> 5] >> (pos & 31)) & 1u;
+  };
   auto emit = [&](int rank, uint32_t key, int64_t row) {
     if (p.out_scores) p.out_scores[q * k + rank] = s_ord_f32(key);
     p.out_ids[q * k + rank] = row + p.id_base;
     if (DENSE && p.count_out && p.row_weight[row] > 0) atomicAdd(&p.count_out[row], 1);
   };
   const int kk = total < k ? total : k;
+  int n_out = kk;                                  // slots written by the selection (FILT: the selectable entries, at most k)
   bool serial = total <= k;                        // (fewer candidates than k: all of them, in order -- the serial path does that)
   const bool streamed = !serial && total > SEL_CAP;   // more candidates than the register path holds: two streaming passes
 
@@ -668,6 +682,7 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
     {
       // all loads first (no use of a loaded value inside this loop: the <= 32 loads of a thread are in flight together)
       float raw[SEL_EPT];
+      uint32_t okm = 0u;                                         // FILT: bit i = entry i is selectable
       int j = 0;
 #pragma unroll
       for (int i = 0; i < SEL_EPT; ++i) {
@@ -676,12 +691,14 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
         if (e < total) {
           if (!DENSE) while (seg_pre[j + 1] <= e) ++j;
           raw[i] = seg_ptr[j][e - seg_pre[j]];
+          if constexpr (FILT) okm |= (uint32_t)selectable(j, e - seg_pre[j]) << i;
         }
       }
 #pragma unroll
       for (int i = 0; i < SEL_EPT; ++i) {
         const int e = tid + i * SEL_THR;
-        const uint32_t key = e < total ? s_f32_ord(raw[i]) : 0u;   // 0: below every real key (s_f32_ord never returns 0 for a non-NaN score)
+        const bool ok = e < total && (!FILT || ((okm >> i) & 1u));
+        const uint32_t key = ok ? s_f32_ord(raw[i]) : 0u;   // 0: below every real key (s_f32_ord never returns 0 for a non-NaN score)
         kr[i] = key;
         tmax = key > tmax ? key : tmax;
       }
@@ -695,9 +712,10 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
 #pragma unroll
     for (int i = 0; i < SEL_EPT; ++i) {
       const int e = tid + i * SEL_THR;
-      shortlist_append(e < total && kr[i] >= P, kr[i], e);
+      shortlist_append(e < total && kr[i] >= P && (!FILT || kr[i] != 0u), kr[i], e);
     }
     if (!rank_shortlist()) serial = true;
+    else if (FILT) n_out = n_cand < k ? n_cand : k;
   }
   if (streamed) {
     // ---- more than 8192 candidates (long lists: C5's whole 5 M rows on one GPU give ~39 000 per query): the same
@@ -717,7 +735,7 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
       seen += cnt;
 #pragma unroll 8
       for (int t = tid; t < cnt; t += SEL_THR) {
-        const uint32_t key = s_f32_ord(sp[t]);
+        const uint32_t key = (!FILT || selectable(j, t)) ? s_f32_ord(sp[t]) : 0u;
         tmax = key > tmax ? key : tmax;
       }
     }
@@ -732,12 +750,13 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int t = t0 + u * SEL_THR + tid;
-          const uint32_t key = t < cnt ? s_f32_ord(raw[u]) : 0u;
-          shortlist_append(t < cnt && key >= P, key, pre + t);
+          const uint32_t key = (t < cnt && (!FILT || selectable(j, t))) ? s_f32_ord(raw[u]) : 0u;
+          shortlist_append(t < cnt && key >= P && (!FILT || key != 0u), key, pre + t);
         }
       }
     }
     if (!rank_shortlist()) serial = true;
+    else if (FILT) n_out = n_cand < k ? n_cand : k;
   }
   if (serial) {
     // ---- serial path: kk rounds of arg-max in (score desc, row asc) order, strictly after the previous winner
@@ -756,16 +775,19 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
     for (int it = 0; it < kk; ++it) {
       unsigned long long best = 0ull;                                   // key + 1 (0 = none)
       for_each([&](int j, int t) {
+        if (FILT && !selectable(j, t)) return;
         const uint32_t key = s_f32_ord(seg_ptr[j][t]);
         bool ok = it == 0 || key < last_key;
         if (!ok && key == last_key) ok = row_at(j, t) > last_row;
         if (ok && (unsigned long long)key + 1ull > best) best = (unsigned long long)key + 1ull;
       });
       best = block_reduce(best, true);
+      if (FILT && best == 0ull) { n_out = it; break; }                 // (workgroup-uniform) no selectable entry left
       const uint32_t kmax = (uint32_t)(best - 1ull);
       unsigned long long br = ~0ull;                                    // row << 32 | position inside the workgroup's walk is not needed: rows are distinct
       for_each([&](int j, int t) {
         if (s_f32_ord(seg_ptr[j][t]) != kmax) return;
+        if (FILT && !selectable(j, t)) return;
         const int64_t r = row_at(j, t);
         if (it == 0 || kmax < last_key || r > last_row) br = (unsigned long long)r < br ? (unsigned long long)r : br;
       });
@@ -775,7 +797,7 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
       last_row = (int64_t)br;
     }
   }
-  for (int i = kk + tid; i < k; i += SEL_THR) {
+  for (int i = n_out + tid; i < k; i += SEL_THR) {
     if (p.out_scores) p.out_scores[q * k + i] = -INFINITY;
     p.out_ids[q * k + i] = -1;
   }
@@ -785,6 +807,10 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p) {
 // selections --, the multi-segment form spills at that budget and is faster left alone)
 __global__ __launch_bounds__(SEL_THR) __attribute__((amdgpu_waves_per_eu(8, 8))) void ivfs_select_dense_kernel(SelParams p) { ivfs_select_body<true>(p); }
 __global__ __launch_bounds__(SEL_THR) void ivfs_select_lists_kernel(SelParams p) { ivfs_select_body<false>(p); }
+// filtered instances (mrag_ivf_search_filtered, path P): dense = probe selection over the live lists only, lists = the
+// allowed stored rows only
+__global__ __launch_bounds__(SEL_THR) __attribute__((amdgpu_waves_per_eu(8, 8))) void ivfs_select_dense_filt_kernel(SelParamsF f) { ivfs_select_body<true, true>(f.p, f.bits); }
+__global__ __launch_bounds__(SEL_THR) void ivfs_select_lists_filt_kernel(SelParamsF f) { ivfs_select_body<false, true>(f.p, f.bits); }
 
 // ------------------------------------------------------------------ descriptors of the dense (probe selection) case
 __global__ void ivfs_dense_desc_kernel(int* __restrict__ desc, int n_qt, int n_chunks, int64_t nq, int n_rows, int rows_per_wg, int pitch) {
@@ -834,13 +860,14 @@ int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype
 }
 
 int ivfs_select_lists(const float* S, const void* pinfo, int nprobe, int64_t nq, int k, const int64_t* row_ids,
-                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream) {
+                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits) {
   if (nq <= 0) return MRAG_OK;
   if (nprobe > SEL_MAXP || k > SEL_MAXK) return fail(MRAG_ERR_UNSUPPORTED, "ivfs_select: nprobe %d / k %d above %d / %d", nprobe, k, SEL_MAXP, SEL_MAXK);
   SelParams p{};
   p.S = S; p.pinfo = (const int4*)pinfo; p.row_ids = row_ids; p.nprobe = nprobe; p.k = k;
   p.id_base = id_base; p.out_scores = out_scores; p.out_ids = out_ids;
-  hipLaunchKernelGGL(ivfs_select_lists_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, p);
+  if (stored_bits) hipLaunchKernelGGL(ivfs_select_lists_filt_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, SelParamsF{p, stored_bits});
+  else hipLaunchKernelGGL(ivfs_select_lists_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, p);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
@@ -852,7 +879,8 @@ int ivfs_dense_n_desc(int64_t nq, int n_rows) {
 }
 
 int ivfs_dense_topk(const uint16_t* corpus, int n_rows, const uint16_t* queries, int64_t nq, int ld, int dtype, int k, int* desc,
-                    float* S, float* out_scores, int64_t* out_ids, hipStream_t stream, int* count_out, const int* row_weight) {
+                    float* S, float* out_scores, int64_t* out_ids, hipStream_t stream, int* count_out, const int* row_weight,
+                    const uint32_t* row_bits) {
   if (nq <= 0) return MRAG_OK;
   if (k > SEL_MAXK) return fail(MRAG_ERR_UNSUPPORTED, "ivfs_dense_topk: k %d above %d", k, SEL_MAXK);
   const int n_qt = (int)((nq + ST - 1) / ST), n_chunks = (n_rows + IVFS_DENSE_ROWS - 1) / IVFS_DENSE_ROWS;
@@ -865,7 +893,8 @@ int ivfs_dense_topk(const uint16_t* corpus, int n_rows, const uint16_t* queries,
   SelParams p{};
   p.S = S; p.nprobe = 1; p.k = k; p.dense_rows = n_rows; p.dense_pitch = pitch; p.out_scores = out_scores; p.out_ids = out_ids;
   p.count_out = count_out; p.row_weight = row_weight;
-  hipLaunchKernelGGL(ivfs_select_dense_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, p);
+  if (row_bits) hipLaunchKernelGGL(ivfs_select_dense_filt_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, SelParamsF{p, row_bits});
+  else hipLaunchKernelGGL(ivfs_select_dense_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, p);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }

@@ -96,6 +96,20 @@ def _allow_buffer(allow, n: int, device: int):
     return bits, bits.ctypes.data, N.ALLOW_BITS32, 0
 
 
+IVF_FILTER_PATHS = {"auto": N.IVF_FILTER_AUTO, "probe": N.IVF_FILTER_PROBE, "exact": N.IVF_FILTER_EXACT}
+_IVF_FILTER_NAMES = {N.IVF_FILTER_PROBE: "probe", N.IVF_FILTER_EXACT: "exact"}
+
+
+def ivf_choose_filter_path(nq: int, k: int, nprobe: int, nlist: int, total_rows: int, allowed_rows: int, dim: int) -> str:
+    """AUTO's rule of the filtered IVF search (``mrag_ivf_choose_filter_path``, pure arithmetic: no GPU needed):
+    "exact" (filtered brute force) when ``nprobe >= nlist`` or the allowed rows are few next to the rows the probes
+    scan, else "probe".  Sharded callers apply it to the global counts."""
+    out = C.c_int(0)
+    N.check(N.load().mrag_ivf_choose_filter_path(int(nq), int(k), int(nprobe), int(nlist), int(total_rows), int(allowed_rows),
+                                                 int(dim), C.byref(out)))
+    return _IVF_FILTER_NAMES[out.value]
+
+
 def _stream_ptr(stream) -> Optional[int]:
     if stream is None:
         return None
@@ -435,16 +449,28 @@ class IVFFlatIndex:
         N.check(self._lib.mrag_ivf_last_timing(self._h, C.byref(g), C.byref(t), C.byref(rows), C.byref(nwg)))
         return {"scan_ms": g.value, "total_ms": t.value, "scanned_rows": rows.value, "n_wg": nwg.value}
 
-    def search(self, queries, k: int, nprobe: int, normalize: Optional[bool] = None):
+    def search(self, queries, k: int, nprobe: int, normalize: Optional[bool] = None, allow=None, filter_path: str = "auto",
+               list_allowed=None, stream=None):
         """-> (scores [nq,k], ids [nq,k]); host queries give numpy arrays (complete on return), CUDA tensors give CUDA
-        tensors filled asynchronously on the current torch stream, like any torch op.  ``nprobe``: 1..256, or ``nlist``
-        (exhaustive)."""
+        tensors filled asynchronously on ``stream`` (default: the current torch stream), like any torch op.  ``nprobe``:
+        1..256, or ``nlist`` (exhaustive).
+
+        ``allow`` restricts the search to some rows (``mrag_ivf_search_filtered``), in the forms
+        :meth:`DenseIndex.search` takes: a bool / uint8 mask over the ``len(self)`` local rows (numpy, or a torch tensor
+        on the host or this index's device) or a host array of row positions.  ``filter_path``: "probe" (every query
+        probes its ``nprobe`` best lists among those holding an allowed row), "exact" (filtered brute force) or "auto".
+        ``list_allowed``: allowed rows per list (int32 [nlist], on the host for a host ``allow``, on the device for a
+        device one) deciding which lists are live instead of this index's own counts (sharded search: the global
+        counts).  See :meth:`last_filter`."""
+        if allow is not None:
+            return self._search_filtered(queries, k, nprobe, normalize, allow, filter_path, list_allowed, stream)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         if is_dev:
             import torch
             sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
             ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
-            stream = torch.cuda.current_stream(self.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
             N.check(self._lib.mrag_ivf_search(self._h, ptr, nq, dt, self._norm(normalize), 1, int(nprobe), int(k),
                                               sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
             return sc, ids
@@ -453,3 +479,72 @@ class IVFFlatIndex:
         N.check(self._lib.mrag_ivf_search(self._h, ptr, nq, dt, self._norm(normalize), is_dev, int(nprobe), int(k),
                                           sc.ctypes.data, ids.ctypes.data, 0, None))
         return sc, ids
+
+    def _list_allowed_buffer(self, list_allowed, adev: int):
+        if list_allowed is None:
+            return None, None
+        if _is_torch(list_allowed) and list_allowed.is_cuda:
+            import torch
+            if not adev:
+                raise ValueError("list_allowed is on the device, allow on the host: pass both in the same memory space")
+            if list_allowed.dtype != torch.int32 or tuple(list_allowed.shape) != (self.nlist,):
+                raise ValueError(f"list_allowed must be int32 [{self.nlist}], got {list_allowed.dtype} {tuple(list_allowed.shape)}")
+            t = list_allowed.contiguous()
+            return t, t.data_ptr()
+        if adev:
+            raise ValueError("list_allowed is on the host, allow on the device: pass both in the same memory space")
+        a = list_allowed.cpu().numpy() if _is_torch(list_allowed) else np.asarray(list_allowed)
+        if a.shape != (self.nlist,):
+            raise ValueError(f"list_allowed must have {self.nlist} entries, got shape {a.shape}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > np.iinfo(np.int32).max):
+            raise ValueError("list_allowed counts must lie in [0, 2^31)")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        return a, a.ctypes.data
+
+    def _search_filtered(self, queries, k, nprobe, normalize, allow, filter_path, list_allowed, stream):
+        if filter_path not in IVF_FILTER_PATHS:
+            raise ValueError(f"filter_path must be one of {sorted(IVF_FILTER_PATHS)}, got {filter_path!r}")
+        n = len(self)
+        akeep, aptr, afmt, adev = _allow_buffer(allow, n, self.device)
+        lkeep, lptr = self._list_allowed_buffer(list_allowed, adev)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        path = IVF_FILTER_PATHS[filter_path]
+        if is_dev or adev:
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
+        if is_dev:
+            sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
+            ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
+            N.check(self._lib.mrag_ivf_search_filtered(self._h, ptr, nq, dt, self._norm(normalize), 1, int(nprobe), int(k), aptr, n,
+                                                       afmt, adev, lptr, path, sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
+            return sc, ids
+        sc = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        N.check(self._lib.mrag_ivf_search_filtered(self._h, ptr, nq, dt, self._norm(normalize), 0, int(nprobe), int(k), aptr, n,
+                                                   afmt, adev, lptr, path, sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+        del akeep, lkeep
+        return sc, ids
+
+    def allowed_per_list(self, allow, stream=None):
+        """Allowed rows per list of an allow-set (``mrag_ivf_allowed_per_list``): int32 [nlist], a numpy array for a
+        host ``allow``, a CUDA tensor (written on ``stream``) for a device one."""
+        n = len(self)
+        akeep, aptr, afmt, adev = _allow_buffer(allow, n, self.device)
+        if adev:
+            import torch
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device)
+            out = torch.empty(self.nlist, dtype=torch.int32, device=akeep.device)
+            N.check(self._lib.mrag_ivf_allowed_per_list(self._h, aptr, n, afmt, 1, out.data_ptr(), 1, _stream_ptr(stream)))
+            return out
+        out = np.empty(self.nlist, dtype=np.int32)
+        N.check(self._lib.mrag_ivf_allowed_per_list(self._h, aptr, n, afmt, 0, out.ctypes.data, 0, _stream_ptr(stream)))
+        return out
+
+    def last_filter(self) -> dict:
+        """Path, allowed rows and live lists of the last filtered search on this index (``mrag_ivf_last_filter``):
+        ``{"path": "probe" | "exact", "allowed": m, "live_lists": l}`` (``live_lists`` is None after path "exact")."""
+        p, m, live = C.c_int(0), C.c_int64(0), C.c_int(0)
+        N.check(self._lib.mrag_ivf_last_filter(self._h, C.byref(p), C.byref(m), C.byref(live)))
+        return {"path": _IVF_FILTER_NAMES[p.value], "allowed": m.value, "live_lists": None if live.value < 0 else live.value}

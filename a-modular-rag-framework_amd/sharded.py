@@ -42,6 +42,15 @@ def shard_bounds(n_total: int, world: int, rank: int) -> Tuple[int, int]:
     return (n_total * rank) // world, (n_total * (rank + 1)) // world
 
 
+def local_allow_mask(allow, n_total: int, lo: int, hi: int) -> np.ndarray:
+    """Global allow-set (bool / uint8 mask over the ``n_total`` rows, or global row positions) -> the local mask over
+    rows ``[lo, hi)`` of one shard (numpy bool), as the single-GPU indexes take it."""
+    from .index import allow_bits
+    words = allow_bits(allow, n_total)        # validates length / range / shape like the single index
+    mask = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_total].astype(np.bool_)
+    return mask[lo:hi]
+
+
 class _Phases:
     """Per-phase milliseconds of one exchange.  CUDA inputs: events on the current stream, read after the call's
     final stream sync (no extra sync); host inputs: ``time.perf_counter``."""
@@ -284,10 +293,7 @@ class ShardedDenseIndex:
     def local_allow(self, allow):
         """Global allow-set (bool / uint8 mask over the ``n_total`` rows, or global row positions) -> this rank's
         local mask over rows ``[lo, hi)`` (numpy bool), as :meth:`DenseIndex.search` takes it."""
-        from .index import allow_bits
-        words = allow_bits(allow, self.n_total)        # validates length / range / shape like the single index
-        mask = np.unpackbits(words.view(np.uint8), bitorder="little")[:self.n_total].astype(np.bool_)
-        return mask[self.lo:self.hi]
+        return local_allow_mask(allow, self.n_total, self.lo, self.hi)
 
     def search(self, queries, k: int, nthreads: int = 0, merge: str = "auto", force_collective: bool = False,
                pipeline: bool = False, allow=None, **kw) -> Tuple[np.ndarray, np.ndarray]:
@@ -420,10 +426,14 @@ class ShardedIVFIndex:
     same centroids.
 
     ``local_search(queries, k, nprobe) -> (scores, ids)`` defaults to an :class:`IVFFlatIndex` on this rank's
-    GPU; tests inject a CPU searcher to exercise the exchange on ``gloo``."""
+    GPU; tests inject a CPU searcher to exercise the exchange on ``gloo``.  A filtered search also calls it with
+    ``allow=`` (local mask), ``filter_path=`` ("probe" / "exact") and ``list_allowed=`` (global per-list counts), and
+    ``local_list_counts(local_mask) -> int [nlist]`` (default: :meth:`IVFFlatIndex.allowed_per_list`) is injectable the
+    same way."""
 
     def __init__(self, dim: int, nlist: int, n_total: int, rank: int, world: int, device: int = 0, group=None,
-                 dtype: str = "f16", metric: str = "cosine", local_search: Optional[Callable] = None):
+                 dtype: str = "f16", metric: str = "cosine", local_search: Optional[Callable] = None,
+                 local_list_counts: Optional[Callable] = None):
         self.dim, self.nlist, self.n_total, self.rank, self.world, self.group = dim, nlist, n_total, rank, world, group
         self.lo, self.hi = shard_bounds(n_total, world, rank)
         self._bufs: dict = {}
@@ -433,7 +443,10 @@ class ShardedIVFIndex:
             self.index = IVFFlatIndex(dim, nlist, metric=metric, dtype=dtype, device=device)
             self.index.set_id_base(self.lo)
             local_search = self.index.search
+            if local_list_counts is None:
+                local_list_counts = self.index.allowed_per_list
         self._local_search = local_search
+        self._local_list_counts = local_list_counts
 
     def train(self, sample_rows, iters: int = 10, seed: int = 0, normalize=None):
         """k-means on rank 0 (``sample_rows`` is ignored elsewhere), centroids broadcast to every rank."""
@@ -459,10 +472,39 @@ class ShardedIVFIndex:
         if len(self.index) > self.hi - self.lo:
             raise ValueError("more rows than this shard owns")
 
-    def search(self, queries, k: int, nprobe: int, nthreads: int = 0, merge: str = "auto",
-               force_collective: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    def global_list_counts(self, local_mask) -> np.ndarray:
+        """Allowed rows per list summed over the ranks (int32 [nlist], host): this rank's counts, all-reduced."""
         import torch
-        sc, ids = self._local_search(queries, k, nprobe)
+        import torch.distributed as dist
+        c = self._local_list_counts(local_mask)
+        c = c.cpu().numpy() if torch.is_tensor(c) else np.asarray(c)
+        t = torch.from_numpy(np.ascontiguousarray(c, dtype=np.int64))
+        if dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            if dist.get_backend(self.group) == "nccl":
+                t = t.to(torch.device("cuda", self.index.device if self.index is not None else torch.cuda.current_device()))
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t.cpu().numpy().astype(np.int32)
+
+    def search(self, queries, k: int, nprobe: int, nthreads: int = 0, merge: str = "auto",
+               force_collective: bool = False, allow=None, filter_path: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
+        """Local search over this rank's rows, then the exchange + merge; every rank returns the full result.
+        ``allow`` (global rows: a mask over ``n_total`` or global row positions) restricts the search to those rows,
+        with the semantics of :meth:`IVFFlatIndex.search`: every rank takes its slice, the per-list allowed counts are
+        summed over the ranks so that all ranks agree on the live lists, and the path ("auto": decided once, from the
+        global counts) is passed explicitly to every rank.  Result = the single-index filtered result."""
+        import torch
+        if allow is not None:
+            from .index import IVF_FILTER_PATHS, ivf_choose_filter_path
+            if filter_path not in IVF_FILTER_PATHS:
+                raise ValueError(f"filter_path must be one of {sorted(IVF_FILTER_PATHS)}, got {filter_path!r}")
+            local = local_allow_mask(allow, self.n_total, self.lo, self.hi)
+            counts = self.global_list_counts(local)
+            if filter_path == "auto":
+                filter_path = ivf_choose_filter_path(int(queries.shape[0]), k, nprobe, self.nlist, self.n_total,
+                                                     int(counts.sum(dtype=np.int64)), self.dim)
+            sc, ids = self._local_search(queries, k, nprobe, allow=local, filter_path=filter_path, list_allowed=counts)
+        else:
+            sc, ids = self._local_search(queries, k, nprobe)
         if not torch.is_tensor(sc):
             sc, ids = torch.from_numpy(np.ascontiguousarray(sc)), torch.from_numpy(np.ascontiguousarray(ids))
         return gather_and_merge(sc, ids, group=self.group, nthreads=nthreads, bufs=self._bufs, merge=merge,

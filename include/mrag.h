@@ -190,8 +190,47 @@ int mrag_ivf_get_assignments(mrag_handle h, int32_t* out, int out_is_device, voi
 int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize,
                     int queries_is_device, int nprobe, int k, float* out_scores, int64_t* out_ids,
                     int out_is_device, void* stream);
+/* Filtered IVF search: the same allow-set contract as mrag_index_search_filtered.  `allow` covers the local rows 0 .. size-1
+ * in insertion order, before id_base (MRAG_ALLOW_BITS32 or MRAG_ALLOW_BYTES, host or device, allow_rows == size).  Results:
+ * (score desc, original row asc), ids = row + id_base, slots past the allowed candidates (-inf, -1); k <= 64, nprobe as
+ * mrag_ivf_search.
+ *   MRAG_IVF_FILTER_PROBE (path P, filter-aware probing): a list is LIVE when it holds at least one allowed row.  Every
+ *     query probes its `nprobe` best live lists, ranked by (centroid score desc, list id asc); a list without an allowed
+ *     row is never probed.  The result is the top-k of the allowed rows of those lists.  With fewer than nprobe live
+ *     lists all of them are probed, and the answer is exactly the filtered brute-force one.
+ *     When every list holds at least one row, an all-allowed set gives exactly what mrag_ivf_search gives (scores and ids).
+ *     An EMPTY list (k-means can leave one) is dead under any allow-set: P probes the next live list in its place, while
+ *     mrag_ivf_search spends a probe on it -- there P can find more rows than the plain search.
+ *   MRAG_IVF_FILTER_EXACT (path E): the top-k over all allowed rows = filtered brute force (the dense filtered search over
+ *     the rows in insertion order).  nprobe == nlist always runs E; so does a P search whose score segments would not fit
+ *     the score buffer (MRAG_IVF_SCORES_MB, 0 included), as the fused list-scan kernel has no filtered form.
+ *   MRAG_IVF_FILTER_AUTO: E when the allowed rows are few enough that scanning them all costs less than the probed scan
+ *     (mrag_ivf_choose_filter_path).  Where AUTO picks E the answer can only improve on P.
+ * list_allowed (optional, NULL = computed from `allow`): allowed rows per list [nlist] int32, in the memory space of
+ * `allow`; only path P reads it, to decide which lists are live.  A sharded index passes the counts summed over its ranks,
+ * so that every rank probes the same lists.
+ * Sync behaviour: a HOST allow-set is counted on the host and the call stays asynchronous (with device queries and
+ * outputs); with a DEVICE allow-set AUTO and E read the allowed count back once, forced P stays asynchronous on `stream`.
+ * Host queries or outputs: the call returns after the results have landed. */
+enum mrag_ivf_filter_path { MRAG_IVF_FILTER_AUTO = 0, MRAG_IVF_FILTER_PROBE = 1, MRAG_IVF_FILTER_EXACT = 2 };
+int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                             int nprobe, int k, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                             const int32_t* list_allowed, int path, float* out_scores, int64_t* out_ids, int out_is_device,
+                             void* stream);
+/* allowed rows per list of an allow-set (formats and sizes as above) -> out_counts [nlist] int32 (host or device) */
+int mrag_ivf_allowed_per_list(mrag_handle h, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                              int32_t* out_counts, int out_is_device, void* stream);
+/* AUTO's rule, handle-free (no GPU needed): E when nprobe >= nlist or allowed_rows <= c * nprobe * total_rows / nlist, with
+ * c measured per regime (a few queries / a batch).  A sharded caller applies it to the global counts and passes the
+ * explicit path to every rank.  *out_path = MRAG_IVF_FILTER_PROBE or MRAG_IVF_FILTER_EXACT. */
+int mrag_ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t total_rows, int64_t allowed_rows, int dim,
+                                int* out_path);
+/* path (PROBE / EXACT), allowed rows and live lists of the LAST filtered search on this handle; live lists is -2 when the
+ * search ran path E (lists are not consulted there).  Blocks until that search is done when a figure is still on the device. */
+int mrag_ivf_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed, int* out_live_lists);
 /* measurement hooks for bench.py (like mrag_index_last_timing): device ms of the list scan (scan + per-query selection kernels, or the fused kernel) and of the
- * whole LAST mrag_ivf_search (hipEvents on its stream), the rows that scan streamed (sum over its
+ * whole LAST mrag_ivf_search or mrag_ivf_search_filtered (hipEvents on its stream; filtered: the list scan + selection on
+ * path P, the search kernel on path E), the rows that scan streamed (sum over its
  * workgroups of their list's length: x ld x 2 = the algorithmic HBM bytes) and its workgroup count. */
 int mrag_ivf_last_timing(mrag_handle h, float* out_scan_ms, float* out_total_ms, int64_t* out_scanned_rows, int* out_n_wg);
 
