@@ -12,6 +12,7 @@ POOL_MEAN, POOL_CLS = 0, 1
 FILTER_AUTO, FILTER_MASK, FILTER_COMPACT = 0, 1, 2
 ALLOW_BITS32, ALLOW_BYTES = 0, 1
 IVF_FILTER_AUTO, IVF_FILTER_PROBE, IVF_FILTER_EXACT = 0, 1, 2
+FP8_BATCH, FP8_STREAM = 0, 1
 
 ERR_NAMES = {-1: "MRAG_ERR_INVALID", -2: "MRAG_ERR_NO_DEVICE", -3: "MRAG_ERR_HIP", -4: "MRAG_ERR_OOM",
              -5: "MRAG_ERR_UNSUPPORTED"}
@@ -68,6 +69,11 @@ SIGNATURES = {
     "mrag_index_search_filtered": [_h, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp],
     "mrag_index_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64)],
     "mrag_index_last_timing": [_h, _fp, _fp],
+    "mrag_index_enable_fp8": [_h],
+    "mrag_index_get_rows_fp8": [_h, _i64, _i64, _vp, _i, _vp],
+    "mrag_index_fp8_default_refine": [_i, C.POINTER(_i)],
+    "mrag_index_search_fp8": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "mrag_index_last_fp8": [_h, C.POINTER(_i), C.POINTER(_i)],
     "mrag_index_measure_clock": [_h, _i],
     "mrag_index_last_clock": [_h, _fp],
     "mrag_topk_merge": [_vp, _vp, _i, _i64, _i, _vp, _vp, _i],

@@ -65,6 +65,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef const __attribute__((address_space(1))) void* glb_vptr;
 
@@ -149,6 +151,18 @@ template <> struct Mfma<MRAG_BF16> {
   typedef bf16x8 frag;
   static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+// fp8 scan copy: the block-scaled 16x16x128 form (2x the fp16 MFMA rate; the unscaled _fp8_fp8 forms run at the fp16
+// rate) with e4m3 A and B (format 0) and neutral E8M0 scales (127 = 2^0).  A 128-element K step is the 128 bytes per row a
+// 16-bit K step stages, so the stage layout and the two 16-byte fragment reads (k halves ph0 / ph1) stay; the two reads
+// form one 32-byte operand.  Which k a register byte stands for does not matter as long as A and B read alike.
+template <> struct Mfma<MRAG_DT_FP8> {
+  typedef i32x4 frag;
+  static __device__ __forceinline__ f32x4 run2(frag a0, frag a1, frag b0, frag b1, f32x4 c) {
+    const i32x8 a = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+    const i32x8 b = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
   }
 };
 
@@ -642,7 +656,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
       if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; ++pf_tile; }
 #pragma unroll
       for (int pp = 0; pp < NPART / 4; ++pp) stage_part(st_a, st_b, st_buf, pp);
-      if (!PENDING || MRAG_DBG(8)) {
+      if (!PENDING || MRAG_DBG(8) || DT == MRAG_DT_FP8) {
 #pragma unroll
         for (int pp = NPART / 4; pp < NPART; ++pp) stage_part(st_a, st_b, st_buf, pp);
       }
@@ -650,7 +664,34 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     const char* sb = smem + buf * STAGE_BYTES;
     buf ^= 1;
     if (MRAG_DBG(8)) return;   // diag 8: ablate LDS reads + MFMA
-    {
+    if constexpr (DT == MRAG_DT_FP8) {
+      // fp8: ONE MFMA per (mf, nf) and step, nothing carried over to the next step.  The B fragments and A rows mf 0-1
+      // (12 reads) go first; then the MFMAs of mf run while the reads of mf + 2 land (4 MFMAs, 2 reads, six times).
+      const int ph1 = ph0 ^ 64;
+      frag g0a[8], g1a[8], g0b[NF], g1b[NF];
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf) {
+        g0b[nf] = *(const frag*)(sb + b_rd + nf * 2048 + ph0);
+        g1b[nf] = *(const frag*)(sb + b_rd + nf * 2048 + ph1);
+      }
+#pragma unroll
+      for (int mf = 0; mf < 8; ++mf) {
+        g0a[mf] = *(const frag*)(sb + a_rd + mf * 2048 + ph0);
+        g1a[mf] = *(const frag*)(sb + a_rd + mf * 2048 + ph1);
+      }
+#pragma unroll
+      for (int mf = 0; mf < 8; ++mf)
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf)
+          acc[mf][nf] = Mfma<DT>::run2(g0a[mf], g1a[mf], g0b[nf], g1b[nf], PENDING ? acc[mf][nf] : (f32x4){0.f, 0.f, 0.f, 0.f});
+      __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
+#define MRAG_SGB8 __builtin_amdgcn_sched_group_barrier(0x008, NF, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      MRAG_SGB8 MRAG_SGB8 MRAG_SGB8 MRAG_SGB8 MRAG_SGB8 MRAG_SGB8
+#undef MRAG_SGB8
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NF, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // as below: the buffer may be restaged after the next barrier
+    } else {
       // Software-pipelined fragment reads, two register sets.  The 12 reads of k half 0 are issued
       // first; the 32 MFMAs of k half 1 of the PREVIOUS step (operands already in registers) run
       // while they land; then the 32 MFMAs of half 0 run with the 12 reads of half 1 interleaved.
@@ -719,7 +760,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
       kstep_sync();
       kstep(std::true_type{});
     }
-    if (!MRAG_DBG(8)) {   // drain: k half 1 of the last K step
+    if constexpr (!MRAG_DBG(8) && DT != MRAG_DT_FP8) {   // drain: k half 1 of the last K step (fp8: nothing pending)
 #pragma unroll
       for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
@@ -1263,14 +1304,23 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
         if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; }
       }
       const char* sb = smem + slot * S_STAGE;
+      if constexpr (DT == MRAG_DT_FP8) {   // one 16x16x128 MFMA per row block: the two k halves are one 32-byte operand
+        const int ph1 = ph0 ^ 64;
+        const frag b0 = *(const frag*)(sb + b_rd + ph0), b1 = *(const frag*)(sb + b_rd + ph1);
+        const frag a00 = *(const frag*)(sb + a_rd + ph0), a01 = *(const frag*)(sb + a_rd + ph1);
+        const frag a10 = *(const frag*)(sb + a_rd + 2048 + ph0), a11 = *(const frag*)(sb + a_rd + 2048 + ph1);
+        acc[0] = Mfma<DT>::run2(a00, a01, b0, b1, acc[0]);
+        acc[1] = Mfma<DT>::run2(a10, a11, b0, b1, acc[1]);
+      } else {
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int ph = ks ? (ph0 ^ 64) : ph0;
-        const frag b = *(const frag*)(sb + b_rd + ph);
-        const frag a0 = *(const frag*)(sb + a_rd + ph);
-        const frag a1 = *(const frag*)(sb + a_rd + 2048 + ph);
-        acc[0] = Mfma<DT>::run(a0, b, acc[0]);
-        acc[1] = Mfma<DT>::run(a1, b, acc[1]);
+        for (int ks = 0; ks < 2; ++ks) {
+          const int ph = ks ? (ph0 ^ 64) : ph0;
+          const frag b = *(const frag*)(sb + b_rd + ph);
+          const frag a0 = *(const frag*)(sb + a_rd + ph);
+          const frag a1 = *(const frag*)(sb + a_rd + 2048 + ph);
+          acc[0] = Mfma<DT>::run(a0, b, acc[0]);
+          acc[1] = Mfma<DT>::run(a1, b, acc[1]);
+        }
       }
       slot = slot == S_NST - 1 ? 0 : slot + 1;
     }
@@ -1837,6 +1887,115 @@ __global__ void remap_ids_kernel(int64_t* __restrict__ ids, int64_t tot, const i
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// fp8 scan copy + exact re-rank (mrag_index_search_fp8; contract in include/mrag.h)
+//   rows8 [cap_rows][ld8] = e4m3fn(clamp(256 * stored 16-bit value, +-448)), ld8 = dim rounded up to 128, pads zero.
+//   A search quantises each prepared query with its own power of two (max |q~| in [128, 256)), picks the top-`refine`
+//   rows by fp8 score with the fp8 instances of K2 / K2s + the unchanged merges, then re-scores those rows exactly.
+// ------------------------------------------------------------------------------------------
+constexpr int FP8_K = 128;            // elements per fp8 K step (the 128 bytes per row a 16-bit K step stages)
+constexpr int FP8_MAX_REFINE = KMAX;  // candidates per query: the batch kernel's list limit
+
+__device__ __forceinline__ float bits_f32(uint16_t b, int is_bf16) {
+  if (is_bf16) return __uint_as_float((uint32_t)b << 16);
+  _Float16 h;
+  __builtin_memcpy(&h, &b, 2);
+  return (float)h;
+}
+// four floats -> four OCP e4m3fn bytes (v_cvt_pk_fp8_f32: round to nearest even); the inputs are clamped to +-448 first
+__device__ __forceinline__ uint32_t e4m3x4(float a, float b, float c, float d) {
+  a = fminf(fmaxf(a, -448.f), 448.f); b = fminf(fmaxf(b, -448.f), 448.f);
+  c = fminf(fmaxf(c, -448.f), 448.f); d = fminf(fmaxf(d, -448.f), 448.f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (uint32_t)w;
+}
+
+// corpus rows [0, n) of a 16-bit matrix (pitch ld) -> the fp8 copy (pitch ld8 bytes, columns >= ld zero); 4 bytes per thread
+__global__ void quant_rows_fp8_kernel(const uint16_t* __restrict__ src, int ld, int is_bf16, int64_t n,
+                                      uint8_t* __restrict__ dst, int ld8) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per = ld8 / 4;
+  if (i >= n * per) return;
+  const int64_t r = i / per;
+  const int c = (int)(i - r * per) * 4;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < ld) {   // ld % 64 == 0: all four columns are inside the 16-bit row
+    const uint2 b = *(const uint2*)(src + (size_t)r * ld + c);
+    v[0] = bits_f32((uint16_t)b.x, is_bf16); v[1] = bits_f32((uint16_t)(b.x >> 16), is_bf16);
+    v[2] = bits_f32((uint16_t)b.y, is_bf16); v[3] = bits_f32((uint16_t)(b.y >> 16), is_bf16);
+  }
+  *(uint32_t*)(dst + (size_t)r * ld8 + c) = e4m3x4(v[0] * 256.f, v[1] * 256.f, v[2] * 256.f, v[3] * 256.f);
+}
+
+// one wave per prepared query row: q~ = e4m3fn(q * 2^e) with max |q * 2^e| in [128, 256) (exact: a power of two); a zero
+// row stays zero.  A positive per-query factor leaves that query's ranking unchanged, so the candidate kernels need no
+// epilogue scaling.
+__global__ __launch_bounds__(64) void quant_queries_fp8_kernel(const uint16_t* __restrict__ src, int ld, int is_bf16,
+                                                               uint8_t* __restrict__ dst, int ld8) {
+  const int lane = threadIdx.x;
+  const uint16_t* row = src + (size_t)blockIdx.x * ld;
+  float amax = 0.f;
+  for (int c = lane; c < ld; c += 64) amax = fmaxf(amax, fabsf(bits_f32(row[c], is_bf16)));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+  int ex = 0;
+  if (amax > 0.f) { (void)frexpf(amax, &ex); ex = 8 - ex; }   // amax = m * 2^E, m in [0.5, 1): amax * 2^(8-E) in [128, 256)
+  uint8_t* out = dst + (size_t)blockIdx.x * ld8;
+  for (int c = lane * 4; c < ld8; c += 256) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < ld) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = ldexpf(bits_f32(row[c + j], is_bf16), ex);
+    }
+    *(uint32_t*)(out + c) = e4m3x4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// one workgroup per query: the fp32 dot product of the 16-bit query with the stored 16-bit row of each of its <= 64
+// candidates (16 lanes per candidate, 8 elements per lane and pass), then the k best in (score desc, row asc) order,
+// + id_base.  Candidate slots without a row (-1) are skipped; output slots past the candidates found are (-inf, -1).
+__global__ __launch_bounds__(256) void fp8_rerank_kernel(const uint16_t* __restrict__ rows, const uint16_t* __restrict__ queries,
+                                                         int ld, int is_bf16, const int64_t* __restrict__ cand, int refine, int k,
+                                                         int64_t id_base, float* __restrict__ out_sc, int64_t* __restrict__ out_id) {
+  __shared__ float s_sc[FP8_MAX_REFINE];
+  __shared__ int s_row[FP8_MAX_REFINE];
+  const int tid = threadIdx.x, grp = tid >> 4, gl = tid & 15;
+  const int64_t q = blockIdx.x;
+  const uint16_t* qr = queries + (size_t)q * ld;
+  for (int c = grp; c < refine; c += 16) {
+    const int64_t r = cand[q * refine + c];
+    float acc = 0.f;
+    if (r >= 0) {
+      const uint16_t* rr = rows + (size_t)r * ld;
+      for (int e = gl * 8; e < ld; e += 128) {
+        const uint4 a = *(const uint4*)(rr + e), b = *(const uint4*)(qr + e);
+        const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc = fmaf(bits_f32((uint16_t)aw[j], is_bf16), bits_f32((uint16_t)bw[j], is_bf16), acc);
+          acc = fmaf(bits_f32((uint16_t)(aw[j] >> 16), is_bf16), bits_f32((uint16_t)(bw[j] >> 16), is_bf16), acc);
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off);   // within the 16-lane group
+    if (gl == 0) { s_sc[c] = acc; s_row[c] = r < 0 ? -1 : (int)r; }
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  const bool valid = tid < refine && s_row[tid] >= 0;
+  const uint64_t my = valid ? make_key(__float_as_uint(s_sc[tid]), (uint32_t)s_row[tid]) : 0ull;
+  int rank = 0;
+  for (int j = 0; j < refine; ++j) {
+    const uint64_t kj = s_row[j] >= 0 ? make_key(__float_as_uint(s_sc[j]), (uint32_t)s_row[j]) : 0ull;
+    rank += kj > my ? 1 : 0;
+  }
+  const int nvalid = __popcll(__ballot(valid));
+  if (valid && rank < k) { out_sc[q * k + rank] = s_sc[tid]; out_id[q * k + rank] = id_base + s_row[tid]; }
+  if (tid >= nvalid && tid < k) { out_sc[q * k + tid] = -INFINITY; out_id[q * k + tid] = -1; }
+}
+
 struct BfIndex : Object {
   int dim = 0, ld = 0, metric = 0, dtype = MRAG_F16;
   int64_t n = 0, cap_rows = 0, id_base = 0;
@@ -1849,8 +2008,16 @@ struct BfIndex : Object {
   bool timed = false, want_clock = false;
   void* q_cleared_buf = nullptr;            // query buffer bookkeeping: rows [q_dirty_rows, q_cleared_rows) are known to be zero
   int64_t q_cleared_rows = 0, q_dirty_rows = 0;
+  // fp8 scan copy (mrag_index_enable_fp8): rows8 [cap_rows][ld8], kept in step with `rows` by add / reserve
+  bool fp8 = false;
+  int ld8 = 0;
+  uint8_t* rows8 = nullptr;
+  DevBuf qbuf8, cand;                       // quantised queries [nq padded][ld8]; candidates (fp8 scores | local rows)
+  int last_refine = -1, last_regime = -1;   // of the last mrag_index_search_fp8
   ~BfIndex() override {
     if (rows) (void)hipFree(rows);
+    if (rows8) (void)hipFree(rows8);
+    qbuf8.release(); cand.release();
     qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
     fw.release();   // (the destroy path synchronised the device)
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
@@ -1890,9 +2057,34 @@ static int grow_rows(BfIndex* ix, int64_t need_rows, hipStream_t stream) {
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for corpus rows failed: %s", bytes, hipGetErrorString(e)); }
   MRAG_HIP(hipMemsetAsync(nr, 0, bytes, stream));
   if (ix->rows && ix->n > 0) MRAG_HIP(hipMemcpyAsync(nr, ix->rows, (size_t)ix->n * ix->ld * 2, hipMemcpyDeviceToDevice, stream));
+  uint8_t* nr8 = nullptr;
+  if (ix->fp8) {   // the fp8 copy grows with the rows
+    const size_t bytes8 = (size_t)cap * ix->ld8;
+    e = hipMalloc((void**)&nr8, bytes8);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(stream);
+      (void)hipFree(nr);
+      return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for the fp8 rows failed: %s", bytes8, hipGetErrorString(e));
+    }
+    MRAG_HIP(hipMemsetAsync(nr8, 0, bytes8, stream));
+    if (ix->rows8 && ix->n > 0) MRAG_HIP(hipMemcpyAsync(nr8, ix->rows8, (size_t)ix->n * ix->ld8, hipMemcpyDeviceToDevice, stream));
+  }
   if (ix->rows) { MRAG_HIP(hipStreamSynchronize(stream)); (void)hipFree(ix->rows); }
+  if (ix->rows8) (void)hipFree(ix->rows8);   // (synchronised above: rows8 exists only next to rows)
   ix->rows = nr;
+  ix->rows8 = nr8;
   ix->cap_rows = cap;
+  return MRAG_OK;
+}
+
+// stored rows [r0, r0 + n) -> their fp8 copy
+static int quant_rows_fp8(BfIndex* ix, int64_t r0, int64_t n, hipStream_t stream) {
+  const int64_t tot = n * (ix->ld8 / 4);
+  if (tot <= 0) return MRAG_OK;
+  hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, ix->rows + (size_t)r0 * ix->ld,
+                     ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, n, ix->rows8 + (size_t)r0 * ix->ld8, ix->ld8);
+  MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
 
@@ -1934,14 +2126,18 @@ constexpr int MAX_QTILES_PER_LAUNCH = 64;
 // the 4-wave / one-wave-per-SIMD form (NF = 8, 256 accumulator registers per lane) is correct but
 // hipcc's allocation of the 256-AGPR tile spills into the K loop (98 ms vs 13.6 ms, round-1 measurement).
 // Column 2 = the filtered dense instance (FILT), picked only when p.allow is set.
+// Row 2 = the fp8 scan copy (mrag_index_search_fp8): dense instance only.
+static int dtype_slot(int dtype) { return dtype == MRAG_F16 ? 0 : (dtype == MRAG_BF16 ? 1 : 2); }
 static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams& p) {
   typedef void (*K2Fn)(BfParams);
-  static const K2Fn fns[2][3] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>,
+  static const K2Fn fns[3][3] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>,
                                   bf_gemm_topk_kernel<MRAG_F16, 4, false, true>},
                                  {bf_gemm_topk_kernel<MRAG_BF16, 4, false>, bf_gemm_topk_kernel<MRAG_BF16, 4, true>,
-                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>}};
-  static bool attr_done[2][3] = {};
-  const int di = dtype == MRAG_F16 ? 0 : 1, de = p.wg_desc ? 1 : (p.allow ? 2 : 0);
+                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>},
+                                 {bf_gemm_topk_kernel<MRAG_DT_FP8, 4, false>, nullptr, nullptr}};
+  static bool attr_done[3][3] = {};
+  const int di = dtype_slot(dtype), de = p.wg_desc ? 1 : (p.allow ? 2 : 0);
+  if (!fns[di][de]) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
   if (!attr_done[di][de]) {
     MRAG_HIP(hipFuncSetAttribute((const void*)fns[di][de], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
     attr_done[di][de] = true;
@@ -1955,7 +2151,7 @@ static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams&
 int bf_launch(const BfLaunch& a) {
   if (a.k <= 0 || a.k > (a.wg_desc ? KMAX : KMAX_WIDE)) return fail(MRAG_ERR_UNSUPPORTED, "k = %d outside 1..%d", a.k, a.wg_desc ? KMAX : KMAX_WIDE);
   hipStream_t stream = a.stream;
-  const int di = a.dtype == MRAG_F16 ? 0 : 1;
+  const int di = dtype_slot(a.dtype);
   BfParams p;
   p.corpus = a.corpus;
   p.ld = a.ld;
@@ -2010,17 +2206,20 @@ int bf_launch(const BfLaunch& a) {
   auto run_stream = [&](const uint16_t* queries, int64_t nq_s, float* out_scores, int64_t* out_ids, bool record_end,
                         size_t extra_counts) -> int {
     typedef void (*SFn)(StreamParams);
-    static const SFn sfns[2][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
+    static const SFn sfns[3][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
                                        {bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>}},
                                       {{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
-                                       {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}}};
+                                       {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}},
+                                      {{bf_stream_topk_kernel<MRAG_DT_FP8, 2, 128>, bf_stream_topk_kernel<MRAG_DT_FP8, 1, 512>},
+                                       {nullptr, nullptr}}};
     static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
-    static bool s_attr[2][2][2] = {};
+    static bool s_attr[3][2][2] = {};
     // the 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
     // 64-row chunk (1 x 1M x 768: 0.431 ms at k = 64 against 0.332 ms at k = 100 on the wide instance)
     const int wi = (a.k > 32) ? 1 : 0;
     const int fi = a.allow ? 1 : 0;   // filtered instance (path M)
     const int grp = wi ? 8 : SQ;
+    if (!sfns[di][fi][wi]) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
     if (!s_attr[di][fi][wi]) {
       MRAG_HIP(hipFuncSetAttribute((const void*)sfns[di][fi][wi], hipFuncAttributeMaxDynamicSharedMemorySize, slds[wi]));
       s_attr[di][fi][wi] = true;
@@ -2067,7 +2266,7 @@ int bf_launch(const BfLaunch& a) {
   static const bool wide_off = [] { const char* e = getenv("MRAG_NO_WIDE_BATCH"); return e && atoi(e) != 0; }();   // test knob: every k > 64 search through the streaming kernel
   const bool wide_batch = a.k > KMAX && a.nq > 32 && n_ctiles >= 64 && !wide_off;
   if (!a.wg_desc) g_wide_redone = 0;
-  if (!wide_batch && (a.k > KMAX || (a.nq <= (a.k > 32 ? 8 : SQ) && n_ctiles >= 8))) return run_stream(a.queries, a.nq, a.out_scores, a.out_ids, true, 0);
+  if (!wide_batch && (a.k > KMAX || a.force_stream || (a.nq <= (a.k > 32 ? 8 : SQ) && n_ctiles >= 8))) return run_stream(a.queries, a.nq, a.out_scores, a.out_ids, true, 0);
   if (wide_batch) {
     // ---- wide batch: the batch kernel at k' = 64 over S >= 4k/64 splits + merge to k + verification (bf_wide_verify_kernel),
     // the flagged queries redone by the streaming kernel.  10 000 queries at the reference's pool of 200 were 1 250 streaming
@@ -2403,6 +2602,7 @@ int mrag_index_create(int dim, int metric, int storage_dtype, int device, mrag_h
   ix->device = device;
   ix->dim = dim;
   ix->ld = (int)round_up(dim, BK);
+  ix->ld8 = (int)round_up(dim, FP8_K);
   ix->metric = metric;
   ix->dtype = storage_dtype;
   for (auto& e : ix->ev) {
@@ -2455,6 +2655,7 @@ int mrag_index_add(mrag_handle h, const void* rows, int64_t n, int src_dtype, in
   }
   MRAG_TRY(launch_prep_rows(src, src_dtype, n, ix->dim, ix->rows + (size_t)ix->n * ix->ld, ix->ld, ix->dtype,
                             normalize, stream));
+  if (ix->fp8) MRAG_TRY(quant_rows_fp8(ix, ix->n, n, stream));
   if (!rows_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   ix->n += n;
   return MRAG_OK;
@@ -2691,6 +2892,122 @@ int mrag_index_last_clock(mrag_handle h, float* out_ghz) {
   const double dc = (double)(w[2] - w[0]), dr = (double)(w[3] - w[1]);
   if (dr <= 0 || dc <= 0) return fail(MRAG_ERR_UNSUPPORTED, "the last search did not run the batch kernel (no clock stamps)");
   *out_ghz = (float)(dc / dr * 0.1);   // s_memrealtime ticks at 100 MHz
+  return MRAG_OK;
+}
+
+int mrag_index_enable_fp8(mrag_handle h) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->metric != MRAG_METRIC_COSINE) return fail(MRAG_ERR_INVALID, "the fp8 scan copy serves cosine indexes only");
+  if (ix->fp8) return MRAG_OK;
+  MRAG_TRY(use_device(ix->device));
+  if (ix->cap_rows > 0) {
+    // rows already stored (adds on any stream): settle them, build the copy on the null stream, finish it here (a one-off)
+    MRAG_HIP(hipDeviceSynchronize());
+    const size_t bytes8 = (size_t)ix->cap_rows * ix->ld8;
+    hipError_t e = hipMalloc((void**)&ix->rows8, bytes8);
+    if (e != hipSuccess) { (void)hipGetLastError(); ix->rows8 = nullptr; return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for the fp8 rows failed: %s", bytes8, hipGetErrorString(e)); }
+    MRAG_HIP(hipMemsetAsync(ix->rows8, 0, bytes8, nullptr));
+    MRAG_TRY(quant_rows_fp8(ix, 0, ix->n, nullptr));
+    MRAG_HIP(hipStreamSynchronize(nullptr));
+  }
+  ix->fp8 = true;
+  return MRAG_OK;
+}
+
+int mrag_index_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, int out_is_device, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (!ix->fp8) return fail(MRAG_ERR_INVALID, "no fp8 scan copy (mrag_index_enable_fp8)");
+  if (row0 < 0 || n < 0 || row0 + n > ix->n) return fail(MRAG_ERR_INVALID, "row range [%lld,%lld) outside [0,%lld)", (long long)row0, (long long)(row0 + n), (long long)ix->n);
+  if (n == 0) return MRAG_OK;
+  if (!out) return fail(MRAG_ERR_INVALID, "out is NULL");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  MRAG_HIP(hipMemcpy2DAsync(out, (size_t)ix->dim, ix->rows8 + (size_t)row0 * ix->ld8, (size_t)ix->ld8, (size_t)ix->dim, (size_t)n,
+                            out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  if (!out_is_device) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_index_fp8_default_refine(int k, int* out) {
+  if (!out) return fail(MRAG_ERR_INVALID, "out is NULL");
+  if (k < 1 || k > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "fp8 search serves 1 <= k <= %d, got %d", FP8_MAX_REFINE, k);
+  *out = std::min(FP8_MAX_REFINE, std::max(40, 4 * k));
+  return MRAG_OK;
+}
+
+int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int k, int refine, float* out_scores, int64_t* out_ids, int out_is_device, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (!ix->fp8) return fail(MRAG_ERR_INVALID, "no fp8 scan copy on this index (mrag_index_enable_fp8)");
+  if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
+  if (k < 1 || k > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "fp8 search serves 1 <= k <= %d, got %d", FP8_MAX_REFINE, k);
+  if (refine == 0) MRAG_TRY(mrag_index_fp8_default_refine(k, &refine));
+  if (refine < k || refine > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "refine = %d outside k..%d (k = %d)", refine, FP8_MAX_REFINE, k);
+  if (nq == 0) return MRAG_OK;
+  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  ix->timed = false;
+  ix->last_refine = -1;
+
+  float* d_sc = out_scores;
+  int64_t* d_id = out_ids;
+  if (!out_is_device) {
+    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
+    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
+    d_sc = (float*)ix->out_sc.p;
+    d_id = (int64_t*)ix->out_id.p;
+  }
+  const bool stream_regime = nq <= SQ;   // as the plain search: up to 16 queries take the streaming kernel
+  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  if (ix->n == 0) {
+    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));
+  } else {
+    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
+    const int64_t nq_pad = round_up(nq, TQ) + SQ;   // prep_queries keeps qbuf rows [nq, nq_pad) zero: so are their fp8 rows
+    MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
+    hipLaunchKernelGGL(quant_queries_fp8_kernel, dim3((unsigned)nq_pad), dim3(64), 0, stream, (const uint16_t*)ix->qbuf.p, ix->ld,
+                       ix->dtype == MRAG_BF16 ? 1 : 0, (uint8_t*)ix->qbuf8.p, ix->ld8);
+    MRAG_HIP(hipGetLastError());
+    MRAG_TRY(ix->cand.ensure((size_t)nq * refine * 12));
+    int64_t* c_id = (int64_t*)ix->cand.p;
+    float* c_sc = (float*)(c_id + (size_t)nq * refine);
+    BfLaunch a = search_launch(ix, nq, refine, c_sc, c_id, stream);
+    a.corpus = (const uint16_t*)ix->rows8;
+    a.queries = (const uint16_t*)ix->qbuf8.p;
+    a.ld = ix->ld8 / 2;              // in 16-bit units: the kernels address rows of ld8 bytes
+    a.dtype = MRAG_DT_FP8;
+    a.id_base = 0;                   // local rows for the re-rank
+    a.force_stream = stream_regime;
+    MRAG_TRY(bf_launch(a));
+    hipLaunchKernelGGL(fp8_rerank_kernel, dim3((unsigned)nq), dim3(256), 0, stream, (const uint16_t*)ix->rows, (const uint16_t*)ix->qbuf.p,
+                       ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)c_id, refine, k, ix->id_base, d_sc, d_id);
+    MRAG_HIP(hipGetLastError());
+  }
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->timed = true;
+  ix->last_refine = refine;
+  ix->last_regime = stream_regime ? MRAG_FP8_STREAM : MRAG_FP8_BATCH;
+  if (!out_is_device) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+  }
+  return MRAG_OK;
+}
+
+int mrag_index_last_fp8(mrag_handle h, int* out_refine, int* out_regime) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_refine < 0) return fail(MRAG_ERR_INVALID, "no completed fp8 search on this index");
+  if (out_refine) *out_refine = ix->last_refine;
+  if (out_regime) *out_regime = ix->last_regime;
   return MRAG_OK;
 }
 

@@ -64,6 +64,10 @@ int launch_prep_rows(const void* src, int src_dtype, int64_t n, int dim, void* d
                      int storage_dtype, int normalize, hipStream_t stream);
 
 
+// Internal operand type of the fp8 scan copy (mrag_index_search_fp8): OCP e4m3fn bytes.  Not an ABI dtype: a BfLaunch
+// with this dtype carries `ld` in 16-bit units (bytes per row / 2), so every stage and tile offset stays as it is.
+constexpr int MRAG_DT_FP8 = 16;
+
 // One fused similarity + top-k pass (K2) and the candidate merge (K4) over PREPARED operands
 // (storage dtype, padded to `ld`, query buffer padded to a multiple of 256 rows).
 struct BfLaunch {
@@ -88,6 +92,7 @@ struct BfLaunch {
   long long* clock = nullptr;         // optional device long long[4]: batch kernel workgroup 0's clock stamps
   const uint32_t* allow = nullptr;    // dense mode, optional: allow-set bitset over the corpus rows (bit r%32 of word r/32),
                                       // padded with zero words to whole 256-row tiles; runs the filtered (FILT) instances
+  bool force_stream = false;          // dense mode, k <= 64: the streaming kernel whatever nq and the corpus size are
 };
 int bf_launch(const BfLaunch& a);
 

@@ -110,6 +110,18 @@ def ivf_choose_filter_path(nq: int, k: int, nprobe: int, nlist: int, total_rows:
     return _IVF_FILTER_NAMES[out.value]
 
 
+PRECISIONS = ("exact", "fp8")
+_FP8_REGIMES = {N.FP8_BATCH: "batch", N.FP8_STREAM: "stream"}
+
+
+def fp8_default_refine(k: int) -> int:
+    """Candidate pool of an fp8 search when ``refine`` is not given (``mrag_index_fp8_default_refine``, no GPU
+    needed): ``min(64, max(40, 4k))`` for ``1 <= k <= 64``; any other ``k`` raises :class:`MragError`."""
+    out = C.c_int(0)
+    N.check(N.load().mrag_index_fp8_default_refine(int(k), C.byref(out)))
+    return out.value
+
+
 def _stream_ptr(stream) -> Optional[int]:
     if stream is None:
         return None
@@ -119,13 +131,20 @@ def _stream_ptr(stream) -> Optional[int]:
 class DenseIndex:
     """Brute-force cosine (or inner-product) top-k index on one GPU."""
 
-    def __init__(self, dim: int, metric: str = "cosine", dtype: str = "f16", device: int = 0):
+    def __init__(self, dim: int, metric: str = "cosine", dtype: str = "f16", device: int = 0, fp8_scan: bool = False):
         self._lib = N.load()
         self.dim, self.metric, self.dtype, self.device = int(dim), metric, dtype, int(device)
         h = C.c_uint64(0)
         N.check(self._lib.mrag_index_create(self.dim, N.METRIC_COSINE if metric == "cosine" else N.METRIC_IP,
                                             N.MRAG_F16 if dtype == "f16" else N.MRAG_BF16, self.device, C.byref(h)))
         self._h = h
+        if fp8_scan:
+            self.enable_fp8()
+
+    def enable_fp8(self):
+        """Keep an fp8 (e4m3fn) copy of the rows for ``search(precision="fp8")`` (``mrag_index_enable_fp8``): built
+        from the rows already stored, then kept current by every add.  Cosine indexes only; idempotent."""
+        N.check(self._lib.mrag_index_enable_fp8(self._h))
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -170,9 +189,17 @@ class DenseIndex:
         N.check(self._lib.mrag_index_get_rows(self._h, int(row0), int(n), out.ctypes.data, 0, None))
         return out
 
+    def rows_fp8(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The fp8 copy of rows ``[row0, row0 + n)`` as its raw e4m3fn bytes ([n, dim] uint8)."""
+        n = len(self) - row0 if n is None else n
+        out = np.empty((n, self.dim), dtype=np.uint8)
+        N.check(self._lib.mrag_index_get_rows_fp8(self._h, int(row0), int(n), out.ctypes.data, 0, None))
+        return out
+
     # -- search ---------------------------------------------------------------------------
     def search(self, queries, k: int, normalize: Optional[bool] = None, stream=None, out=None, allow=None,
-               filter_path: str = "auto") -> Tuple["np.ndarray", "np.ndarray"]:
+               filter_path: str = "auto", precision: str = "exact", refine: Optional[int] = None
+               ) -> Tuple["np.ndarray", "np.ndarray"]:
         """-> (scores [nq,k] fp32 descending, ids [nq,k] int64; (-inf, -1) past the corpus).
 
         Host queries give numpy results (the call returns when they have landed); CUDA
@@ -183,11 +210,26 @@ class DenseIndex:
         ``len(self)`` local rows (numpy, or a torch tensor on the host or on this index's device) or a host array of
         row positions.  Slots past the number of allowed rows are (-inf, -1).  ``filter_path``: "auto", "mask" (the
         search kernels drop disallowed rows) or "compact" (the allowed rows are gathered and searched alone); see
-        :meth:`last_filter`.  ``allow=None`` is the plain search."""
+        :meth:`last_filter`.  ``allow=None`` is the plain search.
+
+        ``precision="fp8"`` (index built with ``fp8_scan=True`` or :meth:`enable_fp8`; ``1 <= k <= 64``) picks the
+        ``refine`` best rows per query (``k <= refine <= 64``; None: :func:`fp8_default_refine`) from the fp8 copy and
+        re-scores them exactly against the 16-bit rows: the scores are exact, the row set is approximate (measured
+        recall in DESIGN.md).  It does not combine with ``allow``."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision == "fp8" and allow is not None:
+            raise ValueError("precision='fp8' does not combine with allow= (filtered search is exact only)")
+        if refine is not None and precision != "fp8":
+            raise ValueError("refine applies to precision='fp8' only")
         if normalize is None:
             normalize = self.metric == "cosine"
         if allow is not None:
             return self._search_filtered(queries, k, normalize, stream, out, allow, filter_path)
+        fp8 = precision == "fp8"
+        r = 0 if refine is None else int(refine)
+        if fp8 and r < 0:
+            raise ValueError(f"refine must be positive, got {refine}")
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         if is_dev:
             import torch
@@ -198,13 +240,21 @@ class DenseIndex:
                 ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
             else:
                 sc, ids = out
-            N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k),
-                                                sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
+            if fp8:
+                N.check(self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k), r,
+                                                        sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
+            else:
+                N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k),
+                                                    sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
             return sc, ids
         sc = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k),
-                                            sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+        if fp8:
+            N.check(self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k), r,
+                                                    sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+        else:
+            N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k),
+                                                sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
         return sc, ids
 
     def _search_filtered(self, queries, k, normalize, stream, out, allow, filter_path):
@@ -240,6 +290,13 @@ class DenseIndex:
         p, m = C.c_int(0), C.c_int64(0)
         N.check(self._lib.mrag_index_last_filter(self._h, C.byref(p), C.byref(m)))
         return {"path": _FILTER_NAMES[p.value], "allowed": m.value}
+
+    def last_fp8(self) -> dict:
+        """Refine pool and regime of the last fp8 search on this index (``mrag_index_last_fp8``):
+        ``{"refine": r, "regime": "batch" | "stream"}``."""
+        r, g = C.c_int(0), C.c_int(0)
+        N.check(self._lib.mrag_index_last_fp8(self._h, C.byref(r), C.byref(g)))
+        return {"refine": r.value, "regime": _FP8_REGIMES[g.value]}
 
     def max_k(self, nq: int = 1) -> int:
         """Largest ``k`` :meth:`search` serves (``mrag_index_max_k``); above it the library raises

@@ -266,11 +266,12 @@ class ShardedDenseIndex:
 
     ``local_search(queries, k) -> (scores, ids)`` defaults to a :class:`DenseIndex` on this
     rank's GPU with ``id_base`` = the shard's first global row; tests inject a CPU searcher
-    to exercise the exchange + merge on ``gloo``."""
+    to exercise the exchange + merge on ``gloo``.  ``fp8_scan=True`` gives that index its fp8 copy, so that
+    ``search(..., precision="fp8", refine=...)`` (passed through to the local search) runs the fp8 scan per shard."""
 
     def __init__(self, dim: int, n_total: int, rank: int, world: int, device: int = 0, group=None,
                  dtype: str = "f16", metric: str = "cosine",
-                 local_search: Optional[Callable] = None):
+                 local_search: Optional[Callable] = None, fp8_scan: bool = False):
         self.dim, self.n_total, self.rank, self.world, self.group = dim, n_total, rank, world, group
         self.lo, self.hi = shard_bounds(n_total, world, rank)
         self._bufs: dict = {}
@@ -278,7 +279,7 @@ class ShardedDenseIndex:
         self.index = None
         if local_search is None:
             from .index import DenseIndex
-            self.index = DenseIndex(dim, metric=metric, dtype=dtype, device=device)
+            self.index = DenseIndex(dim, metric=metric, dtype=dtype, device=device, fp8_scan=fp8_scan)
             self.index.set_id_base(self.lo)
             self.index.reserve(self.hi - self.lo)
             local_search = self.index.search

@@ -129,6 +129,32 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
 /* path the LAST filtered search on this handle took (MRAG_FILTER_MASK / MRAG_FILTER_COMPACT) and its allowed-row count.
  * Blocks until that search is done when the count is still on the device (device allow-set, MRAG_FILTER_MASK). */
 int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed);
+/* fp8 scan copy + exact re-rank (cosine indexes).  mrag_index_enable_fp8 keeps, next to the 16-bit rows, an OCP e4m3fn
+ * copy rows8 [capacity][ld8], ld8 = dim rounded up to 128: byte (r, c) = e4m3fn(clamp(256 * x, -448, 448)), x the STORED
+ * 16-bit value of row r (exact in fp32), rounded to nearest even; pad rows and pad columns are 0.  |x| <= 1 for unit rows,
+ * so 256 * x fills the normal range without overflow.  The copy is built from the rows already stored when it is enabled
+ * (the call synchronises the device; idempotent) and kept current by every later add and reserve; it costs ld8 bytes per
+ * row of capacity.  A non-cosine index gets MRAG_ERR_INVALID.
+ * mrag_index_search_fp8: 1 <= k <= 64 and k <= refine <= 64 (refine = 0: mrag_index_fp8_default_refine(k) =
+ * min(64, max(40, 4k))); anything else, or an index without the copy, is MRAG_ERR_INVALID.  Each query is prepared as in
+ * mrag_index_search (normalize, rounding to the storage dtype) and quantised with its own power of two 2^e, chosen so
+ * that max |q * 2^e| lies in [128, 256) (a zero query stays zero).  The top-`refine` rows by fp8 score (block-scaled
+ * MFMA, fp32 accumulation) are the candidates; up to 16 queries take the streaming kernel, more the batch kernel.  The
+ * candidates are then re-scored exactly: fp32 dot product of the prepared 16-bit query with the stored 16-bit row, so
+ * the returned scores are exact-path scores (equal to the plain search's up to fp32 summation order), never fp8 scores.
+ * Output: the k best candidates by that score, (score desc, row asc), ids = id_base + row; slots past the candidates
+ * found (fewer than k rows) are (-inf, -1).  The result is approximate only in WHICH rows are returned: a true top-k row
+ * that the fp8 ranking leaves outside the refine pool is missed.  Sync behaviour as mrag_index_search.
+ * mrag_index_get_rows_fp8: bytes of rows [row0, row0 + n) as [n, dim] uint8 (tests).  mrag_index_last_fp8: refine and
+ * regime of the last fp8 search on the handle.  mrag_index_last_timing covers fp8 searches too: gemm = the fp8 candidate
+ * kernel(s), total = the whole call. */
+enum mrag_fp8_regime { MRAG_FP8_BATCH = 0, MRAG_FP8_STREAM = 1 };
+int mrag_index_enable_fp8(mrag_handle h);
+int mrag_index_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, int out_is_device, void* stream);
+int mrag_index_fp8_default_refine(int k, int* out);
+int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int k, int refine, float* out_scores, int64_t* out_ids, int out_is_device, void* stream);
+int mrag_index_last_fp8(mrag_handle h, int* out_refine, int* out_regime);
 /* the re-ranker's candidate lookup by row id.  Replaces the 1 + ceil(N/bs) embed calls +
  * N x _cosine of DenseReranker.score (retrieval_backend.py:227-245) for candidates whose rows are already
  * in the index: out_scores[i] = <query, stored row row_ids[i]> (the cosine when rows and query are
