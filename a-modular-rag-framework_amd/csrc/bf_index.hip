@@ -2117,10 +2117,33 @@ int64_t bf_last_wide_redone() { return g_wide_redone; }
 int bf_max_k() { return KMAX; }            // fused batch kernel / IVF list scan
 int bf_max_k_wide() { return KMAX_WIDE; }  // streaming kernel, 8 queries per launch
 int64_t bf_round_rows(int64_t n) { return round_up(n, TM); }
+// + 16 zero rows: the streaming kernel's last 8-query group reads a 16-row block
+int64_t bf_query_rows(int64_t nq) { return round_up(nq, TQ) + SQ; }
 
 // Query batches are cut so that one launch keeps its candidate lists (4.6 KB per workgroup and
 // query) within a few GB: at most 64 query tiles (16 384 queries) per launch.
 constexpr int MAX_QTILES_PER_LAUNCH = 64;
+
+// The regime of a dense search of nq queries over n_rows rows: bf_launch runs it, AUTO's filter rule plans for it.
+enum BfRegime { BF_STREAM, BF_WIDE_BATCH, BF_BATCH };
+static BfRegime bf_regime(int64_t nq, int k, int64_t n_rows, bool force_stream) {
+  static const bool wide_off = [] { const char* e = getenv("MRAG_NO_WIDE_BATCH"); return e && atoi(e) != 0; }();   // test knob: every k > 64 search through the streaming kernel
+  const int64_t n_ctiles = (n_rows + TM - 1) / TM;
+  if (k > KMAX && nq > 32 && n_ctiles >= 64 && !wide_off) return BF_WIDE_BATCH;
+  if (k > KMAX || force_stream || (nq <= (k > 32 ? 8 : SQ) && n_ctiles >= 8)) return BF_STREAM;
+  return BF_BATCH;
+}
+
+// the maximum dynamic LDS of a kernel, set once per process (the attribute is process-wide)
+static int set_max_lds(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::vector<const void*> done;
+  std::lock_guard<std::mutex> lock(mu);
+  if (std::find(done.begin(), done.end(), fn) != done.end()) return MRAG_OK;
+  MRAG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.push_back(fn);
+  return MRAG_OK;
+}
 
 // K2 launcher.  The kernel is templated on the wave tiling; only the 8-wave form (NF = 4) is built:
 // the 4-wave / one-wave-per-SIMD form (NF = 8, 256 accumulator registers per lane) is correct but
@@ -2135,23 +2158,50 @@ static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams&
                                  {bf_gemm_topk_kernel<MRAG_BF16, 4, false>, bf_gemm_topk_kernel<MRAG_BF16, 4, true>,
                                   bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>},
                                  {bf_gemm_topk_kernel<MRAG_DT_FP8, 4, false>, nullptr, nullptr}};
-  static bool attr_done[3][3] = {};
   const int di = dtype_slot(dtype), de = p.wg_desc ? 1 : (p.allow ? 2 : 0);
   if (!fns[di][de]) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
-  if (!attr_done[di][de]) {
-    MRAG_HIP(hipFuncSetAttribute((const void*)fns[di][de], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    attr_done[di][de] = true;
-  }
+  MRAG_TRY(set_max_lds((const void*)fns[di][de], LDS_TOTAL));
   if (!grid) return MRAG_OK;
   hipLaunchKernelGGL(fns[di][de], dim3((unsigned)grid), dim3(NTHR), LDS_TOTAL, stream, p);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
 
+// K2s instances: [dtype slot][filtered (path M)][512-entry lists (k > 32)]; the fp8 row serves the plain search only.
+// The 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
+// 64-row chunk (1 x 1M x 768: 0.431 ms at k = 64 against 0.332 ms at k = 100 on the wide instance)
+typedef void (*K2sFn)(StreamParams);
+static int k2s_instance(int dtype, bool filt, bool wide, K2sFn* fn, int* lds) {
+  static const K2sFn fns[3][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
+                                      {bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>}},
+                                     {{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
+                                      {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}},
+                                     {{bf_stream_topk_kernel<MRAG_DT_FP8, 2, 128>, bf_stream_topk_kernel<MRAG_DT_FP8, 1, 512>},
+                                      {nullptr, nullptr}}};
+  static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
+  *fn = fns[dtype_slot(dtype)][filt][wide];
+  *lds = slds[wide];
+  if (!*fn) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
+  return set_max_lds((const void*)*fn, *lds);
+}
+
+// the merge's view of one K2 / K2s launch: its lists and counts over T query tiles x S splits (descriptor mode: the
+// probes of a.pair_loc), the nq queries it served and where their results go
+static MergeParams merge_params(const BfLaunch& a, const void* list, const void* counts, int T, int S, int64_t nq,
+                                float* out_scores, int64_t* out_ids) {
+  const bool desc = a.wg_desc != nullptr;
+  MergeParams mp;
+  mp.list = (const uint2*)list; mp.counts = (const int*)counts;
+  mp.T = T; mp.S = S; mp.k = a.k; mp.nq = nq; mp.id_base = a.id_base;
+  mp.pair_loc = desc ? (const int2*)a.pair_loc : nullptr; mp.nprobe = desc ? a.nprobe : 0; mp.row_ids = desc ? a.row_ids : nullptr;
+  mp.cap = merge_lds_entries(desc ? a.nprobe : S, a.k);
+  mp.out_scores = out_scores; mp.out_ids = out_ids;
+  return mp;
+}
+
 int bf_launch(const BfLaunch& a) {
   if (a.k <= 0 || a.k > (a.wg_desc ? KMAX : KMAX_WIDE)) return fail(MRAG_ERR_UNSUPPORTED, "k = %d outside 1..%d", a.k, a.wg_desc ? KMAX : KMAX_WIDE);
   hipStream_t stream = a.stream;
-  const int di = dtype_slot(a.dtype);
   BfParams p;
   p.corpus = a.corpus;
   p.ld = a.ld;
@@ -2187,13 +2237,8 @@ int bf_launch(const BfLaunch& a) {
 #ifdef MRAG_DIAG
     MRAG_TRY(dump_stamps(p.dbg, stream));
 #endif
-    MergeParams mp;
-    mp.list = p.list; mp.counts = p.counts;
-    mp.T = 0; mp.S = 0; mp.k = a.k; mp.nq = a.nq; mp.id_base = a.id_base;
-    mp.pair_loc = (const int2*)a.pair_loc; mp.nprobe = a.nprobe; mp.row_ids = a.row_ids;
-    mp.out_scores = a.out_scores; mp.out_ids = a.out_ids;
     if (a.nq) {
-      mp.cap = merge_lds_entries(a.nprobe, a.k);
+      const MergeParams mp = merge_params(a, p.list, p.counts, 0, 0, a.nq, a.out_scores, a.out_ids);
       hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)a.nq), dim3(64), (size_t)mp.cap * 8, stream, mp);
       MRAG_HIP(hipGetLastError());
     }
@@ -2205,25 +2250,11 @@ int bf_launch(const BfLaunch& a) {
   // consecutive launches (exact, one HBM pass each).  `extra_counts`: ints the caller keeps behind the per-region counts.
   auto run_stream = [&](const uint16_t* queries, int64_t nq_s, float* out_scores, int64_t* out_ids, bool record_end,
                         size_t extra_counts) -> int {
-    typedef void (*SFn)(StreamParams);
-    static const SFn sfns[3][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
-                                       {bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>}},
-                                      {{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
-                                       {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}},
-                                      {{bf_stream_topk_kernel<MRAG_DT_FP8, 2, 128>, bf_stream_topk_kernel<MRAG_DT_FP8, 1, 512>},
-                                       {nullptr, nullptr}}};
-    static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
-    static bool s_attr[3][2][2] = {};
-    // the 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
-    // 64-row chunk (1 x 1M x 768: 0.431 ms at k = 64 against 0.332 ms at k = 100 on the wide instance)
-    const int wi = (a.k > 32) ? 1 : 0;
-    const int fi = a.allow ? 1 : 0;   // filtered instance (path M)
+    const bool wi = a.k > 32;
+    K2sFn fn;
+    int lds;
+    MRAG_TRY(k2s_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
     const int grp = wi ? 8 : SQ;
-    if (!sfns[di][fi][wi]) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
-    if (!s_attr[di][fi][wi]) {
-      MRAG_HIP(hipFuncSetAttribute((const void*)sfns[di][fi][wi], hipFuncAttributeMaxDynamicSharedMemorySize, slds[wi]));
-      s_attr[di][fi][wi] = true;
-    }
     const int S = std::max(1, std::min(n_ctiles, 256));
     if (!extra_counts) {    // (a caller with extra_counts has sized both workspaces itself: ensure() does not keep contents)
       MRAG_TRY(a.lists->ensure((size_t)S * TQ * QCAP * 8));
@@ -2236,145 +2267,110 @@ int bf_launch(const BfLaunch& a) {
       sp.n_rows = (int)a.n_rows; sp.n_ctiles = n_ctiles; sp.nq = (int)gq; sp.S = S; sp.k = a.k;
       sp.list = (uint2*)a.lists->p; sp.counts = (int*)a.counts->p;
       sp.allow = a.allow;
-      hipLaunchKernelGGL(sfns[di][fi][wi], dim3((unsigned)S), dim3(NTHR), slds[wi], stream, sp);
+      hipLaunchKernelGGL(fn, dim3((unsigned)S), dim3(NTHR), lds, stream, sp);
       MRAG_HIP(hipGetLastError());
       if (record_end && g0 + grp >= nq_s && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
-      MergeParams mp;
-      mp.list = sp.list; mp.counts = sp.counts;
-      mp.T = 1; mp.S = S; mp.k = a.k; mp.nq = gq; mp.id_base = a.id_base;
-      mp.pair_loc = nullptr; mp.nprobe = 0; mp.row_ids = nullptr;
-      mp.out_scores = out_scores + (size_t)g0 * a.k; mp.out_ids = out_ids + (size_t)g0 * a.k;
+      const MergeParams mp = merge_params(a, sp.list, sp.counts, 1, S, gq, out_scores + (size_t)g0 * a.k, out_ids + (size_t)g0 * a.k);
       if (wi || S > 64) {
         // K4s (heads of the sorted lists through LDS) + K4w for the queries it flags (adversarial layouts only)
-        static bool s_attr2 = false;
-        if (!s_attr2) {
-          MRAG_HIP(hipFuncSetAttribute((const void*)bf_merge_sorted_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MS_CAP * 8));
-          s_attr2 = true;
-        }
+        MRAG_TRY(set_max_lds((const void*)bf_merge_sorted_kernel, MS_CAP * 8));
         int* flags = (int*)a.counts->p + (size_t)S * TQ;       // 16 ints behind the per-region counts
         static const int ms_cap = [] { const char* e = getenv("MRAG_K4S_CAP"); return e ? std::max(0, std::min(atoi(e), MS_CAP)) : MS_CAP; }();   // test knob: 0 sends every query to K4w
         hipLaunchKernelGGL(bf_merge_sorted_kernel, dim3((unsigned)gq), dim3(256), (size_t)MS_CAP * 8, stream, mp, flags, ms_cap);
         hipLaunchKernelGGL(bf_merge_wide_kernel, dim3((unsigned)gq), dim3(256), 0, stream, mp, (const int*)flags);
       } else {
-        mp.cap = merge_lds_entries(S, a.k);
         hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)gq), dim3(64), (size_t)mp.cap * 8, stream, mp);
       }
       MRAG_HIP(hipGetLastError());
     }
     return MRAG_OK;
   };
-  static const bool wide_off = [] { const char* e = getenv("MRAG_NO_WIDE_BATCH"); return e && atoi(e) != 0; }();   // test knob: every k > 64 search through the streaming kernel
-  const bool wide_batch = a.k > KMAX && a.nq > 32 && n_ctiles >= 64 && !wide_off;
-  if (!a.wg_desc) g_wide_redone = 0;
-  if (!wide_batch && (a.k > KMAX || a.force_stream || (a.nq <= (a.k > 32 ? 8 : SQ) && n_ctiles >= 8))) return run_stream(a.queries, a.nq, a.out_scores, a.out_ids, true, 0);
-  if (wide_batch) {
-    // ---- wide batch: the batch kernel at k' = 64 over S >= 4k/64 splits + merge to k + verification (bf_wide_verify_kernel),
-    // the flagged queries redone by the streaming kernel.  10 000 queries at the reference's pool of 200 were 1 250 streaming
-    // launches (one HBM pass each, ~0.5 s over 1M rows); now ceil(T / 16..19) batch-kernel launches.
+  const BfRegime regime = bf_regime(a.nq, a.k, a.n_rows, a.force_stream);
+  g_wide_redone = 0;
+  if (regime == BF_STREAM) return run_stream(a.queries, a.nq, a.out_scores, a.out_ids, true, 0);
+  // ---- batch regimes: the batch kernel over (query tile, corpus split) grids of at most T_max query tiles, each launch
+  // followed by its merge.
+  // Wide batch (k > 64): the batch kernel at k' = 64 over S >= 4k/64 splits + merge to k + verification
+  // (bf_wide_verify_kernel), the flagged queries redone by the streaming kernel.  10 000 queries at the reference's pool of
+  // 200 were 1 250 streaming launches (one HBM pass each, ~0.5 s over 1M rows); now ceil(T / 16..19) batch-kernel launches.
+  const bool wide = regime == BF_WIDE_BATCH;
+  const int T_all = (int)((a.nq + TQ - 1) / TQ);
+  int T_max = MAX_QTILES_PER_LAUNCH;
+  size_t flag_off = 0, stage_off_b = 0, res_off_b = 0;
+  int* need = nullptr;
+  if (wide) {
     int n_cu = 256;
     { int S0, x0; choose_split(1, 1 << 30, &S0, &x0); n_cu = S0; }                       // (choose_split(1, inf) = CU count)
     const int S_min = std::max(4, (4 * a.k + KMAX - 1) / KMAX);
-    const int T_max = std::max(1, std::min(MAX_QTILES_PER_LAUNCH, n_cu / S_min));
-    const int T_all = (int)((a.nq + TQ - 1) / TQ);
+    T_max = std::max(1, std::min(MAX_QTILES_PER_LAUNCH, n_cu / S_min));
     const int S_stream = std::max(1, std::min(n_ctiles, 256));
     // one sizing of both workspaces for every launch below (ensure() drops contents)
     const size_t grid_max = (size_t)std::max(n_cu, S_stream);          // T * S <= CUs for every launch below; the streaming redo uses S_stream regions
     MRAG_TRY(a.lists->ensure(grid_max * TQ * QCAP * 8));
     const size_t cnt_ints = grid_max * TQ + 16;
-    const size_t flag_off = cnt_ints, need_off = flag_off + (size_t)T_max * TQ;                    // ints
-    const size_t stage_off_b = round_up((int64_t)((need_off + (size_t)a.nq) * sizeof(int)), 256);     // bytes: 8 staged query rows, then results
-    const size_t res_off_b = stage_off_b + (size_t)16 * a.ld * 2;
+    flag_off = cnt_ints;
+    const size_t need_off = flag_off + (size_t)T_max * TQ;                                        // ints
+    stage_off_b = round_up((int64_t)((need_off + (size_t)a.nq) * sizeof(int)), 256);              // bytes: 8 staged query rows, then results
+    res_off_b = stage_off_b + (size_t)16 * a.ld * 2;
     MRAG_TRY(a.counts->ensure(res_off_b + (size_t)8 * a.k * 12 + 256));
-    int* need = (int*)a.counts->p + need_off;
-    static bool s_attr3 = false;
-    if (!s_attr3) {
-      MRAG_HIP(hipFuncSetAttribute((const void*)bf_merge_sorted_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MS_CAP * 8));
-      s_attr3 = true;
-    }
-    for (int t0 = 0; t0 < T_all; t0 += T_max) {
-      const int T = std::min(T_max, T_all - t0);
-      const int64_t q0 = (int64_t)t0 * TQ;
-      const int64_t nq = std::min<int64_t>(a.nq - q0, (int64_t)T * TQ);
-      int S, xcd;
-      choose_split(T, n_ctiles, &S, &xcd);
-      const size_t grid = (size_t)T * S;
-      p.queries = a.queries + (size_t)q0 * a.ld;
-      p.n_rows = (int)a.n_rows; p.n_ctiles = n_ctiles; p.nq = (int)nq;
-      p.T = T; p.S = S; p.xcd_map = xcd; p.k = KMAX;
-      p.wg_desc = nullptr;
-      p.list = (uint2*)a.lists->p;
-      p.counts = (int*)a.counts->p;
-      MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
-      if (t0 + T_max >= T_all && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
-      MergeParams mp;
-      mp.list = p.list; mp.counts = p.counts;
-      mp.T = T; mp.S = S; mp.k = a.k; mp.nq = nq; mp.id_base = a.id_base;
-      mp.pair_loc = nullptr; mp.nprobe = 0; mp.row_ids = nullptr;
-      mp.out_scores = a.out_scores + (size_t)q0 * a.k;
-      mp.out_ids = a.out_ids + (size_t)q0 * a.k;
-      int* flags = (int*)a.counts->p + flag_off;
-      hipLaunchKernelGGL(bf_merge_sorted_kernel, dim3((unsigned)nq), dim3(256), (size_t)MS_CAP * 8, stream, mp, flags, MS_CAP);
-      hipLaunchKernelGGL(bf_merge_wide_kernel, dim3((unsigned)nq), dim3(256), 0, stream, mp, (const int*)flags);
-      hipLaunchKernelGGL(bf_wide_verify_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, (const uint2*)p.list, (const int*)p.counts,
-                         S, KMAX, a.k, nq, (const float*)mp.out_scores, (const int64_t*)mp.out_ids, a.id_base, need + q0);
-      MRAG_HIP(hipGetLastError());
-    }
-    // the flagged queries, exactly, eight per streaming launch (their rows staged contiguously)
-    std::vector<int> h_need((size_t)a.nq);
-    MRAG_HIP(hipMemcpyAsync(h_need.data(), need, (size_t)a.nq * sizeof(int), hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-    std::vector<int64_t> redo;
-    for (int64_t q = 0; q < a.nq; ++q) if (h_need[(size_t)q]) redo.push_back(q);
-    g_wide_redone = (int64_t)redo.size();
-    uint16_t* stage = (uint16_t*)((char*)a.counts->p + stage_off_b);
-    float* r_sc = (float*)((char*)a.counts->p + res_off_b);
-    int64_t* r_id = (int64_t*)((char*)a.counts->p + res_off_b + (size_t)8 * a.k * 4);
-    for (size_t g0 = 0; g0 < redo.size(); g0 += 8) {
-      const size_t m = std::min<size_t>(8, redo.size() - g0);
-      MRAG_HIP(hipMemsetAsync(stage, 0, (size_t)16 * a.ld * 2, stream));
-      for (size_t i = 0; i < m; ++i)
-        MRAG_HIP(hipMemcpyAsync(stage + i * a.ld, a.queries + (size_t)redo[g0 + i] * a.ld, (size_t)a.ld * 2, hipMemcpyDeviceToDevice, stream));
-      MRAG_TRY(run_stream(stage, (int64_t)m, r_sc, r_id, false, 1));
-      for (size_t i = 0; i < m; ++i) {
-        MRAG_HIP(hipMemcpyAsync(a.out_scores + (size_t)redo[g0 + i] * a.k, r_sc + i * a.k, (size_t)a.k * 4, hipMemcpyDeviceToDevice, stream));
-        MRAG_HIP(hipMemcpyAsync(a.out_ids + (size_t)redo[g0 + i] * a.k, r_id + i * a.k, (size_t)a.k * 8, hipMemcpyDeviceToDevice, stream));
-      }
-    }
-    return MRAG_OK;
+    need = (int*)a.counts->p + need_off;
+    MRAG_TRY(set_max_lds((const void*)bf_merge_sorted_kernel, MS_CAP * 8));
   }
-  // ---- dense mode: (query tile, corpus split) grid, query batches of <= 64 tiles ----------------
-  const int T_all = (int)((a.nq + TQ - 1) / TQ);
-  for (int t0 = 0; t0 < T_all; t0 += MAX_QTILES_PER_LAUNCH) {
-    const int T = std::min(MAX_QTILES_PER_LAUNCH, T_all - t0);
+  for (int t0 = 0; t0 < T_all; t0 += T_max) {
+    const int T = std::min(T_max, T_all - t0);
     const int64_t q0 = (int64_t)t0 * TQ;
     const int64_t nq = std::min<int64_t>(a.nq - q0, (int64_t)T * TQ);
     int S, xcd;
     choose_split(T, n_ctiles, &S, &xcd);
     const size_t grid = (size_t)T * S;
-    MRAG_TRY(a.lists->ensure(grid * TQ * QCAP * 8));
-    MRAG_TRY(a.counts->ensure(grid * TQ * sizeof(int)));
+    if (!wide) {
+      MRAG_TRY(a.lists->ensure(grid * TQ * QCAP * 8));
+      MRAG_TRY(a.counts->ensure(grid * TQ * sizeof(int)));
+    }
     p.queries = a.queries + (size_t)q0 * a.ld;
-    p.n_rows = (int)a.n_rows;
-    p.n_ctiles = n_ctiles;
-    p.nq = (int)nq;
-    p.T = T; p.S = S; p.xcd_map = xcd;
+    p.n_rows = (int)a.n_rows; p.n_ctiles = n_ctiles; p.nq = (int)nq;
+    p.T = T; p.S = S; p.xcd_map = xcd; p.k = wide ? KMAX : a.k;
     p.wg_desc = nullptr;
     p.list = (uint2*)a.lists->p;
     p.counts = (int*)a.counts->p;
     MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
-    if (t0 + MAX_QTILES_PER_LAUNCH >= T_all && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
-    MergeParams mp;
-    mp.list = p.list; mp.counts = p.counts;
-    mp.T = T; mp.S = S; mp.k = a.k; mp.nq = nq; mp.id_base = a.id_base;
-    mp.pair_loc = nullptr; mp.nprobe = 0; mp.row_ids = nullptr;
-    mp.out_scores = a.out_scores + (size_t)q0 * a.k;
-    mp.out_ids = a.out_ids + (size_t)q0 * a.k;
-    mp.cap = merge_lds_entries(S, a.k);
-    hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)nq), dim3(64), (size_t)mp.cap * 8, stream, mp);
+    if (t0 + T_max >= T_all && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
+    const MergeParams mp = merge_params(a, p.list, p.counts, T, S, nq, a.out_scores + (size_t)q0 * a.k, a.out_ids + (size_t)q0 * a.k);
+    if (wide) {
+      int* flags = (int*)a.counts->p + flag_off;
+      hipLaunchKernelGGL(bf_merge_sorted_kernel, dim3((unsigned)nq), dim3(256), (size_t)MS_CAP * 8, stream, mp, flags, MS_CAP);
+      hipLaunchKernelGGL(bf_merge_wide_kernel, dim3((unsigned)nq), dim3(256), 0, stream, mp, (const int*)flags);
+      hipLaunchKernelGGL(bf_wide_verify_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, (const uint2*)p.list, (const int*)p.counts,
+                         S, KMAX, a.k, nq, (const float*)mp.out_scores, (const int64_t*)mp.out_ids, a.id_base, need + q0);
+    } else {
+      hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)nq), dim3(64), (size_t)mp.cap * 8, stream, mp);
+    }
     MRAG_HIP(hipGetLastError());
 #ifdef MRAG_DIAG
-    MRAG_TRY(dump_stamps(p.dbg, stream));
+    if (!wide) MRAG_TRY(dump_stamps(p.dbg, stream));
 #endif
+  }
+  if (!wide) return MRAG_OK;
+  // the flagged queries, exactly, eight per streaming launch (their rows staged contiguously)
+  std::vector<int> h_need((size_t)a.nq);
+  MRAG_HIP(hipMemcpyAsync(h_need.data(), need, (size_t)a.nq * sizeof(int), hipMemcpyDeviceToHost, stream));
+  MRAG_HIP(hipStreamSynchronize(stream));
+  std::vector<int64_t> redo;
+  for (int64_t q = 0; q < a.nq; ++q) if (h_need[(size_t)q]) redo.push_back(q);
+  g_wide_redone = (int64_t)redo.size();
+  uint16_t* stage = (uint16_t*)((char*)a.counts->p + stage_off_b);
+  float* r_sc = (float*)((char*)a.counts->p + res_off_b);
+  int64_t* r_id = (int64_t*)((char*)a.counts->p + res_off_b + (size_t)8 * a.k * 4);
+  for (size_t g0 = 0; g0 < redo.size(); g0 += 8) {
+    const size_t m = std::min<size_t>(8, redo.size() - g0);
+    MRAG_HIP(hipMemsetAsync(stage, 0, (size_t)16 * a.ld * 2, stream));
+    for (size_t i = 0; i < m; ++i)
+      MRAG_HIP(hipMemcpyAsync(stage + i * a.ld, a.queries + (size_t)redo[g0 + i] * a.ld, (size_t)a.ld * 2, hipMemcpyDeviceToDevice, stream));
+    MRAG_TRY(run_stream(stage, (int64_t)m, r_sc, r_id, false, 1));
+    for (size_t i = 0; i < m; ++i) {
+      MRAG_HIP(hipMemcpyAsync(a.out_scores + (size_t)redo[g0 + i] * a.k, r_sc + i * a.k, (size_t)a.k * 4, hipMemcpyDeviceToDevice, stream));
+      MRAG_HIP(hipMemcpyAsync(a.out_ids + (size_t)redo[g0 + i] * a.k, r_id + i * a.k, (size_t)a.k * 8, hipMemcpyDeviceToDevice, stream));
+    }
   }
   return MRAG_OK;
 }
@@ -2384,57 +2380,133 @@ int bf_launch(const BfLaunch& a) {
 using namespace mrag;
 
 namespace mrag {
-// Search plumbing shared by mrag_index_search and mrag_index_search_filtered.
-// An empty result: every slot (-inf, -1); the K2 events bracket nothing.
-static int fill_empty(BfIndex* ix, float* d_sc, int64_t* d_id, int64_t tot, hipStream_t stream) {
-  hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_sc, d_id, tot);
+// every slot of sc / ids (n each) -> (-inf, -1)
+int launch_fill_empty(float* sc, int64_t* ids, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sc, ids, n);
   MRAG_HIP(hipGetLastError());
-  MRAG_HIP(hipEventRecord(ix->ev[1], stream));
-  MRAG_HIP(hipEventRecord(ix->ev[2], stream));
   return MRAG_OK;
 }
 
-// queries -> storage dtype in ix->qbuf, zero padded to a multiple of 256 rows
-static int prep_queries(BfIndex* ix, const void* queries, int64_t nq, int q_dtype, size_t esz, int normalize,
-                        int queries_is_device, hipStream_t stream) {
-  const int64_t nq_pad = round_up(nq, TQ) + SQ;   // + 16 zero rows: the last 8-query group of the k > 64 path reads a 16-row block
-  const size_t qbytes = (size_t)nq_pad * ix->ld * 2;
-  MRAG_TRY(ix->qbuf.ensure(qbytes));
-  const void* qsrc = queries;
-  if (!queries_is_device) {
-    const size_t bytes = (size_t)nq * ix->dim * esz;
-    MRAG_TRY(ix->stage_in.ensure(bytes));
-    MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, queries, bytes, hipMemcpyHostToDevice, stream));
-    qsrc = ix->stage_in.p;
-  }
-  // rows [nq, nq_pad) must be zero; only rows an earlier (larger) batch wrote need clearing again, so a stream of
-  // equal-sized searches (the online regime: one question per call) pays the fill launch once
-  if (ix->qbuf.p != ix->q_cleared_buf || nq_pad > ix->q_cleared_rows) {
-    MRAG_HIP(hipMemsetAsync(ix->qbuf.p, 0, qbytes, stream));
-    ix->q_cleared_buf = ix->qbuf.p; ix->q_cleared_rows = nq_pad; ix->q_dirty_rows = 0;
-  } else if (ix->q_dirty_rows > nq) {
-    MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(ix->q_dirty_rows - nq) * ix->ld * 2, stream));
-    ix->q_dirty_rows = nq;
-  }
-  ix->q_dirty_rows = std::max<int64_t>(ix->q_dirty_rows, nq);
-  return launch_prep_rows(qsrc, q_dtype, nq, ix->dim, ix->qbuf.p, ix->ld, ix->dtype,
-                          normalize && ix->metric == MRAG_METRIC_COSINE, stream);
+// nq and k of the exact dense searches
+static int check_nq_k(int64_t nq, int k) {
+  if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
+  if (k <= 0) return fail(MRAG_ERR_INVALID, "k must be positive");
+  if (k > KMAX_WIDE) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the top-k limit %d (see mrag_index_max_k)", k, KMAX_WIDE);
+  return MRAG_OK;
 }
 
-// the launch of a search over all stored rows (prepared queries in ix->qbuf)
-static BfLaunch search_launch(BfIndex* ix, int64_t nq, int k, float* d_sc, int64_t* d_id, hipStream_t stream) {
-  BfLaunch a;
-  a.corpus = ix->rows;
-  a.queries = (const uint16_t*)ix->qbuf.p;
-  a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
-  a.nq = nq; a.n_rows = ix->n;
-  a.id_base = ix->id_base;
-  a.out_scores = d_sc; a.out_ids = d_id;
-  a.lists = &ix->lists; a.counts = &ix->counts;
-  a.stream = stream;
-  a.ev_k2_begin = ix->ev[1]; a.ev_k2_end = ix->ev[2];
-  return a;
-}
+// One call of a dense search entry point: the plumbing mrag_index_search, _filtered and _fp8 share around their own work.
+struct DenseSearch {
+  BfIndex* ix;
+  int64_t nq;
+  int k;
+  float* out_scores;
+  int64_t* out_ids;
+  int out_is_device;
+  hipStream_t stream;
+  size_t esz = 0;             // bytes per query element
+  float* d_sc = nullptr;      // the results on the device: the caller's buffers, or out_sc / out_id for host outputs
+  int64_t* d_id = nullptr;
+
+  // After the entry point's own argument checks, for nq > 0: the buffers (allow_null: a filtered search's NULL allow-set
+  // over a non-empty index), the query dtype and the batch size, then the device.  `last` (the entry point's record of its
+  // last search) reads -1 from here until the search completes.
+  int begin(const void* queries, int q_dtype, bool allow_null = false, int* last = nullptr) {
+    if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
+    if (allow_null) return fail(MRAG_ERR_INVALID, "allow is NULL");
+    esz = dtype_size(q_dtype);
+    if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+    if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
+    MRAG_TRY(use_device(ix->device));
+    ix->timed = false;
+    if (last) *last = -1;
+    d_sc = out_scores;
+    d_id = out_ids;
+    if (!out_is_device) {
+      MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
+      MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
+      d_sc = (float*)ix->out_sc.p;
+      d_id = (int64_t*)ix->out_id.p;
+    }
+    return MRAG_OK;
+  }
+
+  // An empty result: every slot (-inf, -1); the K2 events bracket nothing.
+  int fill_empty() {
+    MRAG_TRY(launch_fill_empty(d_sc, d_id, nq * k, stream));
+    MRAG_HIP(hipEventRecord(ix->ev[1], stream));
+    MRAG_HIP(hipEventRecord(ix->ev[2], stream));
+    return MRAG_OK;
+  }
+
+  // queries -> storage dtype in ix->qbuf, zero padded to bf_query_rows(nq) rows
+  int prep_queries(const void* queries, int q_dtype, int normalize, int queries_is_device) {
+    const int64_t nq_pad = bf_query_rows(nq);
+    const size_t qbytes = (size_t)nq_pad * ix->ld * 2;
+    MRAG_TRY(ix->qbuf.ensure(qbytes));
+    const void* qsrc = queries;
+    if (!queries_is_device) {
+      const size_t bytes = (size_t)nq * ix->dim * esz;
+      MRAG_TRY(ix->stage_in.ensure(bytes));
+      MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, queries, bytes, hipMemcpyHostToDevice, stream));
+      qsrc = ix->stage_in.p;
+    }
+    // rows [nq, nq_pad) must be zero; only rows an earlier (larger) batch wrote need clearing again, so a stream of
+    // equal-sized searches (the online regime: one question per call) pays the fill launch once
+    if (ix->qbuf.p != ix->q_cleared_buf || nq_pad > ix->q_cleared_rows) {
+      MRAG_HIP(hipMemsetAsync(ix->qbuf.p, 0, qbytes, stream));
+      ix->q_cleared_buf = ix->qbuf.p; ix->q_cleared_rows = nq_pad; ix->q_dirty_rows = 0;
+    } else if (ix->q_dirty_rows > nq) {
+      MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(ix->q_dirty_rows - nq) * ix->ld * 2, stream));
+      ix->q_dirty_rows = nq;
+    }
+    ix->q_dirty_rows = std::max<int64_t>(ix->q_dirty_rows, nq);
+    return launch_prep_rows(qsrc, q_dtype, nq, ix->dim, ix->qbuf.p, ix->ld, ix->dtype,
+                            normalize && ix->metric == MRAG_METRIC_COSINE, stream);
+  }
+
+  // the launch of a search for k_launch results per query over all stored rows (prepared queries in ix->qbuf)
+  BfLaunch launch(int k_launch, float* sc, int64_t* ids) const {
+    BfLaunch a;
+    a.corpus = ix->rows;
+    a.queries = (const uint16_t*)ix->qbuf.p;
+    a.ld = ix->ld; a.dtype = ix->dtype; a.k = k_launch;
+    a.nq = nq; a.n_rows = ix->n;
+    a.id_base = ix->id_base;
+    a.out_scores = sc; a.out_ids = ids;
+    a.lists = &ix->lists; a.counts = &ix->counts;
+    a.stream = stream;
+    a.ev_k2_begin = ix->ev[1]; a.ev_k2_end = ix->ev[2];
+    return a;
+  }
+
+  // the exact search's launch, with the batch kernel's clock stamps when they are asked for (mrag_index_measure_clock)
+  int exact_launch(BfLaunch* a) {
+    *a = launch(k, d_sc, d_id);
+    if (ix->want_clock) {
+      MRAG_TRY(ix->clock.ensure(64));
+      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
+      a->clock = (long long*)ix->clock.p;
+    }
+    return MRAG_OK;
+  }
+
+  // the search's device work is done: ev[3], the search is timed
+  int end() {
+    MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+    ix->timed = true;
+    return MRAG_OK;
+  }
+
+  // host outputs: copied back, the call returns when they have landed
+  int copy_back() const {
+    if (out_is_device) return MRAG_OK;
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+    return MRAG_OK;
+  }
+};
 
 // ---- filtered search: AUTO's choice between path M and path C ------------------------------------------------------
 // Path C pays a gather of the m allowed rows (read + write of m x ld x 2 B) and searches m rows; path M searches all n.
@@ -2466,14 +2538,12 @@ int filter_choose_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
   const FilterRule& r = filter_rule();
   if (r.force != MRAG_FILTER_AUTO) return r.force;
   if ((double)round_up(m, TM) * ld * 2 > r.scratch_mb * 1048576.0) return MRAG_FILTER_MASK;
-  // the regime bf_launch picks for the unfiltered search over n rows
-  const int n_ctiles = (int)((n + TM - 1) / TM), m_ctiles = (int)((m + TM - 1) / TM);
-  const bool wide_batch = k > KMAX && nq > 32 && n_ctiles >= 64;
+  // the regime bf_launch runs for the unfiltered search over n rows
+  const BfRegime regime = bf_regime(nq, k, n, false);
   // k > 64 over fewer than 64 compacted tiles leaves the wide-batch path for the streaming kernel, 8 queries per launch:
   // 1 000 queries x 1M x 768 at k = 200 and 1 % of the rows measured 6.0 ms compacted against 2.4 ms masked
-  if (wide_batch && m_ctiles < 64) return MRAG_FILTER_MASK;
-  const bool streaming = !wide_batch && (k > KMAX || (nq <= (k > 32 ? 8 : SQ) && n_ctiles >= 8));
-  return (double)m <= (streaming ? r.stream_frac : r.batch_frac) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
+  if (regime == BF_WIDE_BATCH && bf_regime(nq, k, m, false) != BF_WIDE_BATCH) return MRAG_FILTER_MASK;
+  return (double)m <= (regime == BF_STREAM ? r.stream_frac : r.batch_frac) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
 }
 
 // ---- filtered search over prepared operands (mrag_index_search_filtered, and the exact path of mrag_ivf_search_filtered)
@@ -2724,47 +2794,21 @@ int mrag_index_search(mrag_handle h, const void* queries, int64_t nq, int q_dtyp
                       void* stream_) {
   BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
   if (!ix) return MRAG_ERR_INVALID;
-  if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
-  if (k <= 0) return fail(MRAG_ERR_INVALID, "k must be positive");
-  if (k > KMAX_WIDE) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the top-k limit %d (see mrag_index_max_k)", k, KMAX_WIDE);
+  MRAG_TRY(check_nq_k(nq, k));
   if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
-  const size_t esz = dtype_size(q_dtype);
-  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
-  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
-  MRAG_TRY(use_device(ix->device));
-  hipStream_t stream = (hipStream_t)stream_;
-  ix->timed = false;
-
-  float* d_sc = out_scores;
-  int64_t* d_id = out_ids;
-  if (!out_is_device) {
-    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-    d_sc = (float*)ix->out_sc.p;
-    d_id = (int64_t*)ix->out_id.p;
-  }
-  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_};
+  MRAG_TRY(s.begin(queries, q_dtype));
+  MRAG_HIP(hipEventRecord(ix->ev[0], s.stream));
   if (ix->n == 0) {
-    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));
+    MRAG_TRY(s.fill_empty());
   } else {
-    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
-    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
-    if (ix->want_clock) {
-      MRAG_TRY(ix->clock.ensure(64));
-      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
-      a.clock = (long long*)ix->clock.p;
-    }
+    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
+    BfLaunch a;
+    MRAG_TRY(s.exact_launch(&a));
     MRAG_TRY(bf_launch(a));
   }
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->timed = true;
-  if (!out_is_device) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-  }
-  return MRAG_OK;
+  MRAG_TRY(s.end());
+  return s.copy_back();
 }
 
 int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize,
@@ -2773,59 +2817,31 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
                                void* stream_) {
   BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
   if (!ix) return MRAG_ERR_INVALID;
-  if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
-  if (k <= 0) return fail(MRAG_ERR_INVALID, "k must be positive");
-  if (k > KMAX_WIDE) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the top-k limit %d (see mrag_index_max_k)", k, KMAX_WIDE);
+  MRAG_TRY(check_nq_k(nq, k));
   if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
   if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
   if (path != MRAG_FILTER_AUTO && path != MRAG_FILTER_MASK && path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown filter path %d", path);
   if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
-  if (!allow && ix->n > 0) return fail(MRAG_ERR_INVALID, "allow is NULL");
-  const size_t esz = dtype_size(q_dtype);
-  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
-  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
-  MRAG_TRY(use_device(ix->device));
-  hipStream_t stream = (hipStream_t)stream_;
-  ix->timed = false;
-  ix->last_fpath = -1;
-
-  float* d_sc = out_scores;
-  int64_t* d_id = out_ids;
-  if (!out_is_device) {
-    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-    d_sc = (float*)ix->out_sc.p;
-    d_id = (int64_t*)ix->out_id.p;
-  }
+  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_};
+  MRAG_TRY(s.begin(queries, q_dtype, !allow && ix->n > 0, &ix->last_fpath));
   const int64_t n = ix->n;
   int64_t m = -1;                     // allowed rows, when known on the host
   // the whole-search figure (ev[0] .. ev[3]) covers the device work: with a host allow-set it starts after the
   // host-side packing and count, at the bitset's upload
-  MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_FILTER_MASK, &m, ix->ev[0], stream));
+  MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_FILTER_MASK, &m, ix->ev[0], s.stream));
   const int chosen = path != MRAG_FILTER_AUTO ? path : filter_choose_path(nq, k, n, m, ix->ld);
   if (m == 0) {
-    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));       // nothing allowed: no search kernel
+    MRAG_TRY(s.fill_empty());         // nothing allowed: no search kernel
   } else {
-    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
-    BfLaunch a = search_launch(ix, nq, k, d_sc, d_id, stream);
-    if (ix->want_clock) {
-      MRAG_TRY(ix->clock.ensure(64));
-      MRAG_HIP(hipMemsetAsync(ix->clock.p, 0, 64, stream));
-      a.clock = (long long*)ix->clock.p;
-    }
-    MRAG_TRY(filter_search(ix->fw, a, chosen, m, stream));
+    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
+    BfLaunch a;
+    MRAG_TRY(s.exact_launch(&a));
+    MRAG_TRY(filter_search(ix->fw, a, chosen, m, s.stream));
   }
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->timed = true;
+  MRAG_TRY(s.end());
   ix->last_fpath = chosen;
   ix->last_fallowed = m;
-  if (!out_is_device) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-  }
-  return MRAG_OK;
+  return s.copy_back();
 }
 
 int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed) {
@@ -2947,38 +2963,23 @@ int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_
   if (refine == 0) MRAG_TRY(mrag_index_fp8_default_refine(k, &refine));
   if (refine < k || refine > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "refine = %d outside k..%d (k = %d)", refine, FP8_MAX_REFINE, k);
   if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
-  const size_t esz = dtype_size(q_dtype);
-  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
-  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
-  MRAG_TRY(use_device(ix->device));
-  hipStream_t stream = (hipStream_t)stream_;
-  ix->timed = false;
-  ix->last_refine = -1;
-
-  float* d_sc = out_scores;
-  int64_t* d_id = out_ids;
-  if (!out_is_device) {
-    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-    d_sc = (float*)ix->out_sc.p;
-    d_id = (int64_t*)ix->out_id.p;
-  }
+  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_};
+  MRAG_TRY(s.begin(queries, q_dtype, false, &ix->last_refine));
   const bool stream_regime = nq <= SQ;   // as the plain search: up to 16 queries take the streaming kernel
-  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  MRAG_HIP(hipEventRecord(ix->ev[0], s.stream));
   if (ix->n == 0) {
-    MRAG_TRY(fill_empty(ix, d_sc, d_id, nq * k, stream));
+    MRAG_TRY(s.fill_empty());
   } else {
-    MRAG_TRY(prep_queries(ix, queries, nq, q_dtype, esz, normalize, queries_is_device, stream));
-    const int64_t nq_pad = round_up(nq, TQ) + SQ;   // prep_queries keeps qbuf rows [nq, nq_pad) zero: so are their fp8 rows
+    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
+    const int64_t nq_pad = bf_query_rows(nq);   // prep_queries keeps qbuf rows [nq, nq_pad) zero: so are their fp8 rows
     MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
-    hipLaunchKernelGGL(quant_queries_fp8_kernel, dim3((unsigned)nq_pad), dim3(64), 0, stream, (const uint16_t*)ix->qbuf.p, ix->ld,
+    hipLaunchKernelGGL(quant_queries_fp8_kernel, dim3((unsigned)nq_pad), dim3(64), 0, s.stream, (const uint16_t*)ix->qbuf.p, ix->ld,
                        ix->dtype == MRAG_BF16 ? 1 : 0, (uint8_t*)ix->qbuf8.p, ix->ld8);
     MRAG_HIP(hipGetLastError());
     MRAG_TRY(ix->cand.ensure((size_t)nq * refine * 12));
     int64_t* c_id = (int64_t*)ix->cand.p;
     float* c_sc = (float*)(c_id + (size_t)nq * refine);
-    BfLaunch a = search_launch(ix, nq, refine, c_sc, c_id, stream);
+    BfLaunch a = s.launch(refine, c_sc, c_id);
     a.corpus = (const uint16_t*)ix->rows8;
     a.queries = (const uint16_t*)ix->qbuf8.p;
     a.ld = ix->ld8 / 2;              // in 16-bit units: the kernels address rows of ld8 bytes
@@ -2986,20 +2987,14 @@ int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_
     a.id_base = 0;                   // local rows for the re-rank
     a.force_stream = stream_regime;
     MRAG_TRY(bf_launch(a));
-    hipLaunchKernelGGL(fp8_rerank_kernel, dim3((unsigned)nq), dim3(256), 0, stream, (const uint16_t*)ix->rows, (const uint16_t*)ix->qbuf.p,
-                       ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)c_id, refine, k, ix->id_base, d_sc, d_id);
+    hipLaunchKernelGGL(fp8_rerank_kernel, dim3((unsigned)nq), dim3(256), 0, s.stream, (const uint16_t*)ix->rows, (const uint16_t*)ix->qbuf.p,
+                       ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)c_id, refine, k, ix->id_base, s.d_sc, s.d_id);
     MRAG_HIP(hipGetLastError());
   }
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->timed = true;
+  MRAG_TRY(s.end());
   ix->last_refine = refine;
   ix->last_regime = stream_regime ? MRAG_FP8_STREAM : MRAG_FP8_BATCH;
-  if (!out_is_device) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-  }
-  return MRAG_OK;
+  return s.copy_back();
 }
 
 int mrag_index_last_fp8(mrag_handle h, int* out_refine, int* out_regime) {

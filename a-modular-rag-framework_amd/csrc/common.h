@@ -120,6 +120,9 @@ int filter_search(FilterWork& w, BfLaunch a, int path, int64_t m, hipStream_t st
 int bf_max_k();
 int bf_max_k_wide();
 int64_t bf_round_rows(int64_t n);     // rows rounded up to the kernel's tile (256)
+int64_t bf_query_rows(int64_t nq);    // rows of a prepared query buffer: whole 256-query tiles + 16 zero rows
+// every slot of sc / ids (n each) -> (-inf, -1): the result of a search with nothing to search
+int launch_fill_empty(float* sc, int64_t* ids, int64_t n, hipStream_t stream);
 
 // "Score segments + select" regime of the IVF search (ivf_scan.hip).  One scan workgroup = one descriptor:
 //   [0] gq base: slot s of the workgroup scores query row gq[base + s] (< 0: none); or -1 - first for the

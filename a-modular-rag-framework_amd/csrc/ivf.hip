@@ -298,11 +298,6 @@ __global__ void ivf_live_bits_kernel(const int* __restrict__ counts, int nlist, 
   if (lane == 32) live[l >> 5] = (uint32_t)(b >> 32);
 }
 
-__global__ void ivf_fill_empty_kernel(float* __restrict__ sc, int64_t* __restrict__ ids, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { sc[i] = -INFINITY; ids[i] = -1; }
-}
-
 __global__ void ids_to_i32_kernel(const int64_t* __restrict__ ids, int64_t n, int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (int32_t)ids[i];
@@ -633,27 +628,43 @@ static int64_t ivf_chunk_queries(const IvfIndex* ix, int64_t nq, int nprobe) {
   return chunk;
 }
 
+// where a search writes its nq x k results: the caller's buffers, or out_sc / out_id for host outputs, copied back by
+// ivf_copy_back (the search synchronises at its end)
+static int ivf_stage_outputs(IvfIndex* ix, int64_t nq, int k, float* out_scores, int64_t* out_ids, int out_is_device, float** d_sc, int64_t** d_id) {
+  if (out_is_device) { *d_sc = out_scores; *d_id = out_ids; return MRAG_OK; }
+  MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
+  MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
+  *d_sc = (float*)ix->out_sc.p; *d_id = (int64_t*)ix->out_id.p;
+  return MRAG_OK;
+}
+
+static int ivf_copy_back(int64_t nq, int k, float* out_scores, int64_t* out_ids, int out_is_device, const float* d_sc, const int64_t* d_id, hipStream_t stream) {
+  if (out_is_device) return MRAG_OK;
+  MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
+  MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+  return MRAG_OK;
+}
+
+// queries -> storage dtype in ix->qbuf, zero padded to bf_query_rows(nq) rows
+static int ivf_prep_queries(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, hipStream_t stream) {
+  const int64_t nq_pad = bf_query_rows(nq);
+  MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
+  MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));   // (rows < nq: written whole by the prepare kernel)
+  return ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream);
+}
+
 // one chunk of a search (<= 2^20 queries whose score segments fit the buffer): probe selection, plan, list scan, selection
 // live_bits / stored_bits (filtered search, path P): probe only live lists, select only allowed stored positions
 static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
                             int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx,
-                            const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr) {
+                            const uint32_t* live_bits, const uint32_t* stored_bits) {
   hipEvent_t ev_scan0 = ix->cev[2 * chunk_idx], ev_scan1 = ix->cev[2 * chunk_idx + 1];
   unsigned long long* d_stats = (unsigned long long*)ix->stats.p;
 
-  float* d_sc = out_scores;
-  int64_t* d_id = out_ids;
-  if (!out_is_device) {
-    MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-    MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-    d_sc = (float*)ix->out_sc.p;
-    d_id = (int64_t*)ix->out_id.p;
-  }
+  float* d_sc; int64_t* d_id;
+  MRAG_TRY(ivf_stage_outputs(ix, nq, k, out_scores, out_ids, out_is_device, &d_sc, &d_id));
   // 1) queries -> storage dtype; probe lists
-  const int64_t nq_pad = bf_round_rows(nq) + 16;   // + 16 zero rows: the streaming kernel's last 8-query group reads a 16-row block
-  MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
-  MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));   // (rows < nq: written whole by the prepare kernel)
-  MRAG_TRY(ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream));
+  MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
   MRAG_TRY(ix->tmp_id.ensure((size_t)nq * nprobe * 8));
   MRAG_TRY(ix->tmp_sc.ensure((size_t)nq * nprobe * 4));
   // The list scan (and the probe selection before it) runs as "score segments + select" (ivf_scan.hip) whenever the
@@ -791,10 +802,63 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
   }
   ix->last_scores_path = use_scores;
   (void)n_wg;
-  if (!out_is_device) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+  return ivf_copy_back(nq, k, out_scores, out_ids, out_is_device, d_sc, d_id, stream);
+}
+
+// the per-chunk events of a search in n_chunks chunks: list scan begin, list scan end
+static int ivf_grow_cev(IvfIndex* ix, int n_chunks) {
+  while ((int)ix->cev.size() < 2 * n_chunks) {
+    hipEvent_t e = nullptr;
+    MRAG_HIP(hipEventCreate(&e));
+    ix->cev.push_back(e);
   }
+  return MRAG_OK;
+}
+
+// the chunks of a search of nq queries, chunk queries each, one after another (live_bits / stored_bits: as ivf_search_chunk)
+static int ivf_run_chunks(IvfIndex* ix, const void* queries, int64_t nq, int64_t chunk, int q_dtype, int normalize, int queries_is_device,
+                          int nprobe, int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream,
+                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr) {
+  const int n_chunks = (int)((nq + chunk - 1) / chunk);
+  MRAG_TRY(ivf_grow_cev(ix, n_chunks));
+  const size_t qrow = (size_t)ix->dim * esize(q_dtype);
+  for (int c = 0; c < n_chunks; ++c) {
+    const int64_t off = (int64_t)c * chunk, m = std::min(chunk, nq - off);
+    MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, m, q_dtype, normalize, queries_is_device, nprobe, k,
+                              out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c, live_bits, stored_bits));
+  }
+  ix->n_chunks = n_chunks;
+  return MRAG_OK;
+}
+
+// nq, k and nprobe of both IVF searches
+static int ivf_check_nq_k(int64_t nq, int k, int nprobe) {
+  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
+  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
+  return MRAG_OK;
+}
+
+// After an IVF search's own argument checks: *nprobe clamped and checked (nq == 0 stops there: the caller returns), the
+// buffers, the index finalized, the batch cut into chunks of *chunk queries, `stream` ordered behind the previous search.
+static int ivf_search_begin(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, const float* out_scores, const int64_t* out_ids,
+                            hipStream_t stream, int* nprobe, int64_t* chunk) {
+  *nprobe = std::min(*nprobe, ix->nlist);
+  // probe selection = top-nprobe over the centroids: the fused kernel up to 64, the streaming kernel up to 256
+  // (8 queries per launch); nprobe == nlist needs no selection at all
+  if (*nprobe > bf_max_k_wide() && *nprobe < ix->nlist)
+    return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", *nprobe, bf_max_k_wide(), ix->nlist);
+  if (nq == 0) return MRAG_OK;
+  if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
+  if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
+  MRAG_TRY(use_device(ix->device));
+  MRAG_TRY(ivf_finalize(ix, stream));
+  *chunk = ivf_chunk_queries(ix, nq, *nprobe);
+  if (*chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
+  ix->timed = false;
+  // an asynchronous search (device queries + device results) returns with the handle's scratch buffers still in use on ITS
+  // stream; a following search on another stream first waits for that one's end event (a no-op on the same stream or after a
+  // synchronous search), so callers may switch streams between searches on one handle
+  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
   return MRAG_OK;
 }
 
@@ -803,42 +867,15 @@ int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype,
                     int k, float* out_scores, int64_t* out_ids, int out_is_device, void* stream_) {
   IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
   if (!ix) return MRAG_ERR_INVALID;
-  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
-  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
-  nprobe = std::min(nprobe, ix->nlist);
-  // probe selection = top-nprobe over the centroids: the fused kernel up to 64, the streaming kernel up to 256
-  // (8 queries per launch); nprobe == nlist needs no selection at all
-  if (nprobe > bf_max_k_wide() && nprobe < ix->nlist)
-    return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", nprobe, bf_max_k_wide(), ix->nlist);
-  if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
-  if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
-  MRAG_TRY(use_device(ix->device));
+  MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
   hipStream_t stream = (hipStream_t)stream_;
-  MRAG_TRY(ivf_finalize(ix, stream));
-  const int64_t chunk = ivf_chunk_queries(ix, nq, nprobe);
-  if (chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
-  const int n_chunks = (int)((nq + chunk - 1) / chunk);
-  while ((int)ix->cev.size() < 2 * n_chunks) {
-    hipEvent_t e = nullptr;
-    MRAG_HIP(hipEventCreate(&e));
-    ix->cev.push_back(e);
-  }
-  ix->timed = false;
-  // an asynchronous search (device queries + device results) returns with the handle's scratch buffers still in use on ITS
-  // stream; a following search on another stream first waits for that one's end event (a no-op on the same stream or after a
-  // synchronous search), so callers may switch streams between searches on one handle
-  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  int64_t chunk = 0;
+  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  if (nq == 0) return MRAG_OK;
   MRAG_HIP(hipEventRecord(ix->ev[0], stream));
   MRAG_TRY(ix->stats.ensure(16));
   MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
-  const size_t qrow = (size_t)ix->dim * esize(q_dtype);
-  for (int c = 0; c < n_chunks; ++c) {
-    const int64_t off = (int64_t)c * chunk, m = std::min(chunk, nq - off);
-    MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, m, q_dtype, normalize, queries_is_device, nprobe, k,
-                              out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c));
-  }
-  ix->n_chunks = n_chunks;
+  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device, stream));
   MRAG_HIP(hipEventRecord(ix->ev[3], stream));
   ix->end_recorded = true;
   ix->timed = true;
@@ -949,29 +986,19 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
                              void* stream_) {
   IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
   if (!ix) return MRAG_ERR_INVALID;
-  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
-  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
+  MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
   MRAG_TRY(check_allow_args(ix, allow, allow_rows, allow_format));
   if (path != MRAG_IVF_FILTER_AUTO && path != MRAG_IVF_FILTER_PROBE && path != MRAG_IVF_FILTER_EXACT)
     return fail(MRAG_ERR_INVALID, "unknown IVF filter path %d", path);
-  nprobe = std::min(nprobe, ix->nlist);
-  if (nprobe > bf_max_k_wide() && nprobe < ix->nlist)
-    return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", nprobe, bf_max_k_wide(), ix->nlist);
-  if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
-  if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
-  MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
-  MRAG_TRY(ivf_finalize(ix, stream));
+  int64_t chunk = 0;
+  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  if (nq == 0) return MRAG_OK;
+  ix->last_fpath = -1;
   // path P runs the score-segment regime only, every chunk without a host round trip (ivf_search_chunk's no_sync case);
   // where that does not hold (nprobe == nlist, MRAG_IVF_SCORES_MB = 0, segments too big) the search runs path E
   const int64_t cap = ivf_scores_cap();
-  const int64_t chunk = ivf_chunk_queries(ix, nq, nprobe);
-  if (chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
   const bool probe_fits = cap > 0 && nprobe < ix->nlist && chunk * nprobe * ivfs_pitch(ix->max_list_rows) * 4 <= cap;
-  ix->timed = false;
-  ix->last_fpath = -1;
-  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
   const int64_t n = ix->n;
   int64_t m = -1;
   MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_IVF_FILTER_PROBE, &m, ix->ev[0], stream));
@@ -985,32 +1012,18 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
   }
   MRAG_TRY(ix->stats.ensure(16));
   MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
-  while ((int)ix->cev.size() < 2) {
-    hipEvent_t e = nullptr;
-    MRAG_HIP(hipEventCreate(&e));
-    ix->cev.push_back(e);
-  }
+  MRAG_TRY(ivf_grow_cev(ix, 1));
   int live = -2;
   if (chosen == MRAG_IVF_FILTER_EXACT || m == 0) {
-    float* d_sc = out_scores;
-    int64_t* d_id = out_ids;
-    if (!out_is_device) {
-      MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-      MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-      d_sc = (float*)ix->out_sc.p;
-      d_id = (int64_t*)ix->out_id.p;
-    }
+    float* d_sc; int64_t* d_id;
+    MRAG_TRY(ivf_stage_outputs(ix, nq, k, out_scores, out_ids, out_is_device, &d_sc, &d_id));
     if (m == 0) {                      // nothing allowed: no search kernel
       MRAG_HIP(hipEventRecord(ix->cev[0], stream));
-      hipLaunchKernelGGL(ivf_fill_empty_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, stream, d_sc, d_id, nq * k);
-      MRAG_HIP(hipGetLastError());
+      MRAG_TRY(launch_fill_empty(d_sc, d_id, nq * k, stream));
       MRAG_HIP(hipEventRecord(ix->cev[1], stream));
     } else {
       // path E: the dense filtered search over the rows in arrival order (ix->raw: whole zeroed 256-row tiles), ids = row + id_base
-      const int64_t nq_pad = bf_round_rows(nq) + 16;   // + 16 zero rows: the streaming kernel's last 8-query group reads a 16-row block
-      MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
-      MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));
-      MRAG_TRY(ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream));
+      MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
       BfLaunch a;
       a.corpus = ix->raw; a.queries = (const uint16_t*)ix->qbuf.p; a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
       a.nq = nq; a.n_rows = n; a.id_base = ix->id_base;
@@ -1020,10 +1033,7 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
       MRAG_TRY(filter_search(ix->fw, a, filter_choose_path(nq, k, n, m, ix->ld), m, stream));
     }
     ix->n_chunks = 1;
-    if (!out_is_device) {
-      MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-      MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
-    }
+    MRAG_TRY(ivf_copy_back(nq, k, out_scores, out_ids, out_is_device, d_sc, d_id, stream));
     if (m == 0) live = 0;
   } else {
     // path P: allow-set -> stored positions + per-list counts; liveness from those counts or the caller's (sharded: global)
@@ -1047,20 +1057,8 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
     hipLaunchKernelGGL(ivf_live_bits_kernel, dim3((unsigned)(bf_round_rows(ix->nlist) / 256)), dim3(256), 0, stream, cnt, ix->nlist,
                        flist_live(ix), flist_nlive(ix));
     MRAG_HIP(hipGetLastError());
-    const int n_chunks = (int)((nq + chunk - 1) / chunk);
-    while ((int)ix->cev.size() < 2 * n_chunks) {
-      hipEvent_t e = nullptr;
-      MRAG_HIP(hipEventCreate(&e));
-      ix->cev.push_back(e);
-    }
-    const size_t qrow = (size_t)ix->dim * esize(q_dtype);
-    for (int c = 0; c < n_chunks; ++c) {
-      const int64_t off = (int64_t)c * chunk, mq = std::min(chunk, nq - off);
-      MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, mq, q_dtype, normalize, queries_is_device, nprobe, k,
-                                out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c,
-                                (const uint32_t*)flist_live(ix), (const uint32_t*)ix->fstored.p));
-    }
-    ix->n_chunks = n_chunks;
+    MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device,
+                            stream, (const uint32_t*)flist_live(ix), (const uint32_t*)ix->fstored.p));
     // the figures last_filter reports, kept apart from the words the next call overwrites (no sync here)
     MRAG_TRY(ix->flast.ensure(8));
     MRAG_HIP(hipMemcpyAsync(ix->flast.p, ix->fw.fwork.p, 4, hipMemcpyDeviceToDevice, stream));

@@ -128,6 +128,29 @@ def _stream_ptr(stream) -> Optional[int]:
     return int(getattr(stream, "cuda_stream", stream))
 
 
+def _run_search(call, queries, nq: int, k: int, is_dev: int, device: int, stream, device_work: bool, out=None):
+    """What every search method shares: results [nq, k] where the queries live (CUDA tensors on their device, ``out``
+    reused when given, or numpy arrays), ``stream`` defaulting to torch's current stream when the call works on device
+    buffers (``device_work``), then ``call(scores_ptr, ids_ptr, out_is_device, stream_ptr)``.  The caller holds every
+    buffer the call reads until it returns."""
+    if device_work and stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device)
+    if is_dev:
+        import torch
+        if out is None:
+            sc = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+            ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+        else:
+            sc, ids = out
+        N.check(call(sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
+        return sc, ids
+    sc = np.empty((nq, k), dtype=np.float32)
+    ids = np.empty((nq, k), dtype=np.int64)
+    N.check(call(sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+    return sc, ids
+
+
 class DenseIndex:
     """Brute-force cosine (or inner-product) top-k index on one GPU."""
 
@@ -231,31 +254,14 @@ class DenseIndex:
         if fp8 and r < 0:
             raise ValueError(f"refine must be positive, got {refine}")
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
-        if is_dev:
-            import torch
-            if stream is None:
-                stream = torch.cuda.current_stream(self.device)
-            if out is None:
-                sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
-                ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
-            else:
-                sc, ids = out
-            if fp8:
-                N.check(self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k), r,
-                                                        sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
-            else:
-                N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k),
-                                                    sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
-            return sc, ids
-        sc = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
+        norm = int(bool(normalize))
         if fp8:
-            N.check(self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k), r,
-                                                    sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
+            def call(sc, ids, out_dev, st):
+                return self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, norm, is_dev, int(k), r, sc, ids, out_dev, st)
         else:
-            N.check(self._lib.mrag_index_search(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k),
-                                                sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
-        return sc, ids
+            def call(sc, ids, out_dev, st):
+                return self._lib.mrag_index_search(self._h, ptr, nq, dt, norm, is_dev, int(k), sc, ids, out_dev, st)
+        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev), out)
 
     def _search_filtered(self, queries, k, normalize, stream, out, allow, filter_path):
         if filter_path not in FILTER_PATHS:
@@ -264,25 +270,11 @@ class DenseIndex:
         akeep, aptr, afmt, adev = _allow_buffer(allow, n, self.device)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         path = FILTER_PATHS[filter_path]
-        if is_dev or adev:
-            import torch
-            if stream is None:
-                stream = torch.cuda.current_stream(self.device)
-        if is_dev:
-            if out is None:
-                sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
-                ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
-            else:
-                sc, ids = out
-            N.check(self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), 1, int(k), aptr, n, afmt,
-                                                         adev, path, sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
-            return sc, ids
-        sc = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        N.check(self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), 0, int(k), aptr, n, afmt,
-                                                     adev, path, sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
-        del akeep
-        return sc, ids
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), is_dev, int(k), aptr, n, afmt,
+                                                        adev, path, sc, ids, out_dev, st)
+        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or adev), out)
 
     def last_filter(self) -> dict:
         """Path and allowed-row count of the last filtered search on this index (``mrag_index_last_filter``):
@@ -522,20 +514,11 @@ class IVFFlatIndex:
         if allow is not None:
             return self._search_filtered(queries, k, nprobe, normalize, allow, filter_path, list_allowed, stream)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
-        if is_dev:
-            import torch
-            sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
-            ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(self.device)
-            N.check(self._lib.mrag_ivf_search(self._h, ptr, nq, dt, self._norm(normalize), 1, int(nprobe), int(k),
-                                              sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
-            return sc, ids
-        sc = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        N.check(self._lib.mrag_ivf_search(self._h, ptr, nq, dt, self._norm(normalize), is_dev, int(nprobe), int(k),
-                                          sc.ctypes.data, ids.ctypes.data, 0, None))
-        return sc, ids
+        norm = self._norm(normalize)
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_ivf_search(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), sc, ids, out_dev, st)
+        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev))
 
     def _list_allowed_buffer(self, list_allowed, adev: int):
         if list_allowed is None:
@@ -566,22 +549,12 @@ class IVFFlatIndex:
         lkeep, lptr = self._list_allowed_buffer(list_allowed, adev)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         path = IVF_FILTER_PATHS[filter_path]
-        if is_dev or adev:
-            import torch
-            if stream is None:
-                stream = torch.cuda.current_stream(self.device)
-        if is_dev:
-            sc = torch.empty((nq, k), dtype=torch.float32, device=keep.device)
-            ids = torch.empty((nq, k), dtype=torch.int64, device=keep.device)
-            N.check(self._lib.mrag_ivf_search_filtered(self._h, ptr, nq, dt, self._norm(normalize), 1, int(nprobe), int(k), aptr, n,
-                                                       afmt, adev, lptr, path, sc.data_ptr(), ids.data_ptr(), 1, _stream_ptr(stream)))
-            return sc, ids
-        sc = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        N.check(self._lib.mrag_ivf_search_filtered(self._h, ptr, nq, dt, self._norm(normalize), 0, int(nprobe), int(k), aptr, n,
-                                                   afmt, adev, lptr, path, sc.ctypes.data, ids.ctypes.data, 0, _stream_ptr(stream)))
-        del akeep, lkeep
-        return sc, ids
+        norm = self._norm(normalize)
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_ivf_search_filtered(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), aptr, n, afmt, adev,
+                                                      lptr, path, sc, ids, out_dev, st)
+        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or adev))
 
     def allowed_per_list(self, allow, stream=None):
         """Allowed rows per list of an allow-set (``mrag_ivf_allowed_per_list``): int32 [nlist], a numpy array for a
