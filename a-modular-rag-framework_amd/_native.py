@@ -68,6 +68,7 @@ SIGNATURES = {
     "mrag_index_score_rows": [_h, _vp, _i, _i, _vp, _i64, _vp, _vp],
     "mrag_index_search_filtered": [_h, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp],
     "mrag_index_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64)],
+    "mrag_index_search_range": [_h, _vp, _i64, _i, _i, _i, _i, C.c_float, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
     "mrag_index_last_timing": [_h, _fp, _fp],
     "mrag_index_enable_fp8": [_h],
     "mrag_index_get_rows_fp8": [_h, _i64, _i64, _vp, _i, _vp],

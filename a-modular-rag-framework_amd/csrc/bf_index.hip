@@ -56,6 +56,7 @@
 #include <type_traits>
 
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <algorithm>
 
@@ -97,6 +98,8 @@ constexpr int OFF_FLAGS = OFF_STAT + 2048;      // int[4]
 constexpr int OFF_RM = OFF_FLAGS + 16;          // float[4 columns][2][512 threads]: each lane's two largest
                                                 // per-tile maxima per query column (kept out of the VGPR budget)
 constexpr int LDS_TOTAL = OFF_RM + 4 * 2 * NTHR * 4;
+constexpr int OFF_RCNT = LDS_TOTAL;             // RANGE instances: int[256] rows >= the floor per query of this split
+constexpr int LDS_TOTAL_RANGE = OFF_RCNT + 1024;
 
 struct BfParams {
   const uint16_t* corpus;   // [n_cap][ld]
@@ -118,6 +121,8 @@ struct BfParams {
   uint2* list;              // [T*S][256][QCAP]  {score bits, local row}: one 8-byte store per push
   int* counts;              // [T*S][256] entries left in the kept area
   const uint32_t* allow;    // FILT instances: allow-set bitset (bit r%32 of word r/32), padded with zero words to whole tiles
+  float floor;              // RANGE instances: score floor (finite); rows scoring >= floor are listed and counted
+  int* rcounts;             // RANGE instances: [T*S][256] rows >= floor per (workgroup, query), one slot each
 };
 
 __device__ __forceinline__ uint32_t f32_ord(float f) {
@@ -466,9 +471,13 @@ __device__ __forceinline__ void compact_owned(uint2* __restrict__ wg_list, int w
 // instance, the dense (t, s) instance carries neither.
 // FILT: filtered search (path M, dense instances only): rows whose bit in p.allow is clear score -inf in the epilogue,
 // exactly like the rows past the corpus in a partial last tile, so they are never listed and the certificates stay sound.
-template <int DT, int NF, bool DESC, bool FILT = false>
+// RANGE: range search (dense instances only): every threshold starts at next_below(p.floor) and only rises from there, so
+// only rows >= the floor are listed; the rows >= floor of each query are counted once per tile (before the push, so a
+// replayed tile is not counted twice) into LDS and written to the workgroup's count slots at the end of the split.
+template <int DT, int NF, bool DESC, bool FILT = false, bool RANGE = false>
 __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_topk_kernel(BfParams p) {
   static_assert(!(FILT && DESC), "filtered search runs the dense instance only");
+  static_assert(!(RANGE && DESC), "range search runs the dense instance only");
   constexpr int WN = 16 / NF;            // waves along the query dimension
   constexpr int NW = 2 * WN;             // waves per workgroup
   constexpr int NT = 64 * NW;            // threads per workgroup
@@ -537,8 +546,11 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
   uint32_t* stat = (uint32_t*)(smem + OFF_STAT);   // [2][256] orderable bits, ds_min target
   int* flags = (int*)(smem + OFF_FLAGS);
   uint32_t* rm = (uint32_t*)(smem + OFF_RM);
+  int* rcnt = (int*)(smem + OFF_RCNT);   // RANGE only (inside LDS_TOTAL_RANGE)
+  const float fnb = RANGE ? next_below(p.floor) : -INFINITY;   // RANGE: a score is listed / counted iff it beats fnb
   if (tid < TQ) {
-    tau_c[tid] = -INFINITY;
+    tau_c[tid] = fnb;
+    if constexpr (RANGE) rcnt[tid] = 0;
     kcnt[tid] = 0;
     stat[tid] = 0xFFFFFFFFu;
     stat[TQ + tid] = 0xFFFFFFFFu;
@@ -875,9 +887,13 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
           MRAG_STAMP(11);
 #pragma unroll
           for (int nf = 0; nf < NF; ++nf) thr[nf] = next_below(ord_f32(stat_cur[q0 + nf * 16]));
+          if constexpr (RANGE) {
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf) thr[nf] = fmaxf(thr[nf], fnb);
+          }
         } else {
 #pragma unroll
-          for (int nf = 0; nf < NF; ++nf) thr[nf] = -INFINITY;
+          for (int nf = 0; nf < NF; ++nf) thr[nf] = fnb;
         }
       } else {
 #pragma unroll
@@ -889,6 +905,26 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf)
         if (q0 + nf * 16 >= nq_local) thr[nf] = INFINITY;   // padding queries never list anything
+      if constexpr (RANGE) {
+        // rows >= floor of this lane's 32 scores per query column (rows past the corpus and disallowed rows are -inf here);
+        // a wave-uniform skip for columns nobody reaches, then the 8 lanes of a query are summed into its LDS counter
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf) {
+          float tm = -INFINITY;
+#pragma unroll
+          for (int mf = 0; mf < 8; ++mf) tm = fmaxf(tm, fmaxf(fmaxf(acc[mf][nf][0], acc[mf][nf][1]), fmaxf(acc[mf][nf][2], acc[mf][nf][3])));
+          if (!__any(tm > fnb)) continue;
+          int c = 0;
+#pragma unroll
+          for (int mf = 0; mf < 8; ++mf)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c += acc[mf][nf][j] > fnb ? 1 : 0;
+          if (q0 + nf * 16 >= nq_local) c = 0;   // padding queries never count
+          c += __shfl_xor(c, 16);
+          c += __shfl_xor(c, 32);
+          if (elane < 16 && c) atomicAdd(&rcnt[q0 + nf * 16], c);
+        }
+      }
       int cseg[NF];   // this lane's segment fill, per query column
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) cseg[nf] = scnt[(q0 + nf * 16) * NGRP + grp];
@@ -1159,6 +1195,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     p.clock[3] = (long long)__builtin_amdgcn_s_memrealtime();
   }
   if (tid < TQ) p.counts[(size_t)wg * TQ + tid] = kcnt[tid];
+  if constexpr (RANGE) if (tid < TQ) p.rcounts[(size_t)wg * TQ + tid] = rcnt[tid];
 }
 
 
@@ -1195,6 +1232,8 @@ struct StreamParams {
   uint2* list;               // K4 layout: [(wg*256 + q)*QCAP + i]
   int* counts;               // [wg*256 + q]
   const uint32_t* allow;     // FILT instances: allow-set bitset, as BfParams::allow
+  float floor;               // RANGE instances: score floor, as BfParams::floor
+  int* rcounts;              // RANGE instances: [wg*256 + q] rows >= floor of the workgroup's split
 };
 
 // one wave: cut query q's LDS list (<= 64*R entries) to its k best (sorted), raise tau
@@ -1229,7 +1268,8 @@ __device__ __forceinline__ void stream_compact(uint2* __restrict__ lst, int* __r
   if (lane == 0) cnt[q] = min(c, k);
 }
 
-template <int DT, int QPW, int LCAP, bool FILT = false>
+// RANGE: tau starts at next_below(p.floor) (only rows >= floor are listed) and the wave filter counts the rows >= floor.
+template <int DT, int QPW, int LCAP, bool FILT = false, bool RANGE = false>
 __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p) {
   typedef typename Mfma<DT>::frag frag;
   typedef StreamLds<QPW, LCAP> L;
@@ -1244,7 +1284,11 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
   uint2* lists = (uint2*)(smem + S_OFF_LIST);
   int* cnt = (int*)(smem + L::OFF_CNT);
   float* tau = (float*)(smem + L::OFF_TAU);
-  if (tid < SQ) { cnt[tid] = 0; tau[tid] = -INFINITY; }
+  const float fnb = RANGE ? next_below(p.floor) : -INFINITY;
+  if (tid < SQ) { cnt[tid] = 0; tau[tid] = fnb; }
+  int rc[QPW];   // RANGE: rows >= floor of this wave's queries (wave-uniform)
+#pragma unroll
+  for (int qq = 0; qq < QPW; ++qq) rc[qq] = 0;
 
   const uint32_t row_b = (uint32_t)p.ld * 2u;
   const uint32_t voff_e = (uint32_t)(lane >> 3) * row_b + (uint32_t)(((lane & 7) ^ (lane >> 4)) * 16);
@@ -1347,6 +1391,11 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
 #pragma unroll 1
       for (int c0 = 0; c0 < TM; c0 += 64) {
         const float v = sc[qi * S_SC_LD + c0 + lane];
+        if constexpr (RANGE) {
+          const int hits = __popcll(__ballot(v > fnb));
+          if (QPW == 1 || qq == 0) rc[0] += hits;
+          else rc[QPW - 1] += hits;
+        }
         const bool pass = v > tau[qi];                 // strict: a later tie loses to the rows already listed
         const unsigned long long bal = __ballot(pass);
         if (bal) {
@@ -1364,6 +1413,7 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
   // ---- end of the split: k best per query (sorted) into the K4 layout ------------------------
   for (int qq = 0; qq < QPW; ++qq) {
     const int qi = QPW * w + qq;
+    if constexpr (RANGE) if (lane == 0 && qi < SQ) p.rcounts[(size_t)wg * TQ + qi] = qi < p.nq ? (qq == 0 ? rc[0] : rc[QPW - 1]) : 0;
     if (qi >= p.nq) { if (lane == 0 && qi < SQ) p.counts[(size_t)wg * TQ + qi] = 0; continue; }
     uint2* lst = lists + qi * LCAP;
     stream_compact<LCAP / 64>(lst, cnt, tau, qi, p.k, lane);
@@ -1704,6 +1754,19 @@ __global__ __launch_bounds__(256) void bf_merge_wide_kernel(MergeParams p, const
   for (int i = nsel + tid; i < k; i += 256) { p.out_scores[q * k + i] = -INFINITY; p.out_ids[q * k + i] = -1; }
 }
 
+// range search: out[q] = the sum of query q's count slots over the S splits of its query tile (one wave per query)
+__global__ __launch_bounds__(64) void range_count_sum_kernel(const int* __restrict__ slots, int S, int64_t nq, int64_t* __restrict__ out) {
+  const int64_t q = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (q >= nq) return;
+  const int t = (int)(q / TQ), ql = (int)(q % TQ);
+  long long c = 0;
+  for (int s = lane; s < S; s += 64) c += slots[(size_t)(t * S + s) * TQ + ql];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if (lane == 0) out[q] = (int64_t)c;
+}
+
 __global__ void fill_empty_kernel(float* sc, int64_t* ids, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { sc[i] = -INFINITY; ids[i] = -1; }
@@ -2001,6 +2064,7 @@ struct BfIndex : Object {
   int64_t n = 0, cap_rows = 0, id_base = 0;
   uint16_t* rows = nullptr;
   DevBuf qbuf, lists, counts, stage_in, out_sc, out_id, clock;
+  DevBuf rslots, out_cnt;                   // range search: per-(workgroup, query) count slots; counts for host outputs
   FilterWork fw;                            // filtered search: allow bitset, counts, compacted rows
   int last_fpath = -1;                      // path of the last filtered search (MRAG_FILTER_MASK / _COMPACT), -1 = none
   int64_t last_fallowed = -1;               // its allowed-row count; -1 = still on the device (fwork word 0, read on demand)
@@ -2019,6 +2083,7 @@ struct BfIndex : Object {
     if (rows8) (void)hipFree(rows8);
     qbuf8.release(); cand.release();
     qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
+    rslots.release(); out_cnt.release();
     fw.release();   // (the destroy path synchronised the device)
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
@@ -2166,6 +2231,20 @@ static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams&
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
+// the RANGE instances (range search): [16-bit dtype slot][filtered (path M)]
+static int launch_k2_range(int dtype, size_t grid, hipStream_t stream, const BfParams& p) {
+  typedef void (*K2Fn)(BfParams);
+  static const K2Fn fns[2][2] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false, false, true>, bf_gemm_topk_kernel<MRAG_F16, 4, false, true, true>},
+                                 {bf_gemm_topk_kernel<MRAG_BF16, 4, false, false, true>, bf_gemm_topk_kernel<MRAG_BF16, 4, false, true, true>}};
+  const int di = dtype_slot(dtype);
+  if (di > 1 || p.wg_desc) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
+  const K2Fn fn = fns[di][p.allow ? 1 : 0];
+  MRAG_TRY(set_max_lds((const void*)fn, LDS_TOTAL_RANGE));
+  if (!grid) return MRAG_OK;
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(NTHR), LDS_TOTAL_RANGE, stream, p);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
 
 // K2s instances: [dtype slot][filtered (path M)][512-entry lists (k > 32)]; the fp8 row serves the plain search only.
 // The 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
@@ -2183,6 +2262,26 @@ static int k2s_instance(int dtype, bool filt, bool wide, K2sFn* fn, int* lds) {
   *lds = slds[wide];
   if (!*fn) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
   return set_max_lds((const void*)*fn, *lds);
+}
+// the RANGE instances of K2s: [16-bit dtype slot][filtered][512-entry lists]
+static int k2s_range_instance(int dtype, bool filt, bool wide, K2sFn* fn, int* lds) {
+  static const K2sFn fns[2][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, false, true>},
+                                      {bf_stream_topk_kernel<MRAG_F16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true, true>}},
+                                     {{bf_stream_topk_kernel<MRAG_BF16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, false, true>},
+                                      {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true, true>}}};
+  static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
+  const int di = dtype_slot(dtype);
+  if (di > 1) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
+  *fn = fns[di][filt][wide];
+  *lds = slds[wide];
+  return set_max_lds((const void*)*fn, *lds);
+}
+// range search: the per-query sums of the count slots of one launch (T query tiles x S splits) -> out[0 .. nq)
+static int launch_range_sum(const BfLaunch& a, int S, int64_t nq, int64_t* out) {
+  if (!out || nq <= 0) return MRAG_OK;
+  hipLaunchKernelGGL(range_count_sum_kernel, dim3((unsigned)nq), dim3(64), 0, a.stream, (const int*)a.rslots->p, S, nq, out);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
 }
 
 // the merge's view of one K2 / K2s launch: its lists and counts over T query tiles x S splits (descriptor mode: the
@@ -2211,6 +2310,9 @@ int bf_launch(const BfLaunch& a) {
   p.stamps = nullptr;
   p.clock = a.clock;
   p.allow = a.wg_desc ? nullptr : a.allow;
+  p.floor = a.floor;
+  p.rcounts = nullptr;
+  if (a.range && (a.wg_desc || !a.rslots)) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense mode only");
 #ifdef MRAG_DIAG
   {
     p.dbg = MRAG_DIAG;
@@ -2253,12 +2355,14 @@ int bf_launch(const BfLaunch& a) {
     const bool wi = a.k > 32;
     K2sFn fn;
     int lds;
-    MRAG_TRY(k2s_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
+    if (a.range) MRAG_TRY(k2s_range_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
+    else MRAG_TRY(k2s_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
     const int grp = wi ? 8 : SQ;
     const int S = std::max(1, std::min(n_ctiles, 256));
     if (!extra_counts) {    // (a caller with extra_counts has sized both workspaces itself: ensure() does not keep contents)
       MRAG_TRY(a.lists->ensure((size_t)S * TQ * QCAP * 8));
       MRAG_TRY(a.counts->ensure(((size_t)S * TQ + 16) * sizeof(int)));   // + the K4s fallback flags of one query group
+      if (a.range) MRAG_TRY(a.rslots->ensure((size_t)S * TQ * sizeof(int)));
     }
     for (int64_t g0 = 0; g0 < nq_s; g0 += grp) {
       const int64_t gq = std::min<int64_t>(grp, nq_s - g0);
@@ -2267,8 +2371,12 @@ int bf_launch(const BfLaunch& a) {
       sp.n_rows = (int)a.n_rows; sp.n_ctiles = n_ctiles; sp.nq = (int)gq; sp.S = S; sp.k = a.k;
       sp.list = (uint2*)a.lists->p; sp.counts = (int*)a.counts->p;
       sp.allow = a.allow;
+      sp.floor = a.floor;
+      sp.rcounts = a.range ? (int*)a.rslots->p : nullptr;
       hipLaunchKernelGGL(fn, dim3((unsigned)S), dim3(NTHR), lds, stream, sp);
       MRAG_HIP(hipGetLastError());
+      // (the wide-batch redo, extra_counts != 0, only fixes lists: its queries were counted by the batch pass)
+      if (a.range && !extra_counts) MRAG_TRY(launch_range_sum(a, S, gq, a.out_counts ? a.out_counts + g0 : nullptr));
       if (record_end && g0 + grp >= nq_s && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
       const MergeParams mp = merge_params(a, sp.list, sp.counts, 1, S, gq, out_scores + (size_t)g0 * a.k, out_ids + (size_t)g0 * a.k);
       if (wi || S > 64) {
@@ -2313,6 +2421,7 @@ int bf_launch(const BfLaunch& a) {
     stage_off_b = round_up((int64_t)((need_off + (size_t)a.nq) * sizeof(int)), 256);              // bytes: 8 staged query rows, then results
     res_off_b = stage_off_b + (size_t)16 * a.ld * 2;
     MRAG_TRY(a.counts->ensure(res_off_b + (size_t)8 * a.k * 12 + 256));
+    if (a.range) MRAG_TRY(a.rslots->ensure(grid_max * TQ * sizeof(int)));
     need = (int*)a.counts->p + need_off;
     MRAG_TRY(set_max_lds((const void*)bf_merge_sorted_kernel, MS_CAP * 8));
   }
@@ -2326,6 +2435,7 @@ int bf_launch(const BfLaunch& a) {
     if (!wide) {
       MRAG_TRY(a.lists->ensure(grid * TQ * QCAP * 8));
       MRAG_TRY(a.counts->ensure(grid * TQ * sizeof(int)));
+      if (a.range) MRAG_TRY(a.rslots->ensure(grid * TQ * sizeof(int)));
     }
     p.queries = a.queries + (size_t)q0 * a.ld;
     p.n_rows = (int)a.n_rows; p.n_ctiles = n_ctiles; p.nq = (int)nq;
@@ -2333,8 +2443,14 @@ int bf_launch(const BfLaunch& a) {
     p.wg_desc = nullptr;
     p.list = (uint2*)a.lists->p;
     p.counts = (int*)a.counts->p;
-    MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
+    if (a.range) {
+      p.rcounts = (int*)a.rslots->p;
+      MRAG_TRY(launch_k2_range(a.dtype, grid, stream, p));
+    } else {
+      MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
+    }
     if (t0 + T_max >= T_all && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
+    if (a.range) MRAG_TRY(launch_range_sum(a, S, nq, a.out_counts ? a.out_counts + q0 : nullptr));
     const MergeParams mp = merge_params(a, p.list, p.counts, T, S, nq, a.out_scores + (size_t)q0 * a.k, a.out_ids + (size_t)q0 * a.k);
     if (wide) {
       int* flags = (int*)a.counts->p + flag_off;
@@ -2404,9 +2520,11 @@ struct DenseSearch {
   int64_t* out_ids;
   int out_is_device;
   hipStream_t stream;
+  int64_t* out_counts = nullptr;   // range search only: per-query counts [nq], in the memory space of the other outputs
   size_t esz = 0;             // bytes per query element
   float* d_sc = nullptr;      // the results on the device: the caller's buffers, or out_sc / out_id for host outputs
   int64_t* d_id = nullptr;
+  int64_t* d_cnt = nullptr;   // (range search) the counts on the device: out_counts, or out_cnt for host outputs
 
   // After the entry point's own argument checks, for nq > 0: the buffers (allow_null: a filtered search's NULL allow-set
   // over a non-empty index), the query dtype and the batch size, then the device.  `last` (the entry point's record of its
@@ -2422,11 +2540,16 @@ struct DenseSearch {
     if (last) *last = -1;
     d_sc = out_scores;
     d_id = out_ids;
+    d_cnt = out_counts;
     if (!out_is_device) {
       MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
       MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
       d_sc = (float*)ix->out_sc.p;
       d_id = (int64_t*)ix->out_id.p;
+      if (out_counts) {
+        MRAG_TRY(ix->out_cnt.ensure((size_t)nq * 8));
+        d_cnt = (int64_t*)ix->out_cnt.p;
+      }
     }
     return MRAG_OK;
   }
@@ -2434,6 +2557,7 @@ struct DenseSearch {
   // An empty result: every slot (-inf, -1); the K2 events bracket nothing.
   int fill_empty() {
     MRAG_TRY(launch_fill_empty(d_sc, d_id, nq * k, stream));
+    if (d_cnt) MRAG_HIP(hipMemsetAsync(d_cnt, 0, (size_t)nq * 8, stream));
     MRAG_HIP(hipEventRecord(ix->ev[1], stream));
     MRAG_HIP(hipEventRecord(ix->ev[2], stream));
     return MRAG_OK;
@@ -2503,6 +2627,7 @@ struct DenseSearch {
     if (out_is_device) return MRAG_OK;
     MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
     MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
+    if (out_counts) MRAG_HIP(hipMemcpyAsync(out_counts, d_cnt, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
     MRAG_HIP(hipStreamSynchronize(stream));
     return MRAG_OK;
   }
@@ -2841,6 +2966,53 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
   MRAG_TRY(s.end());
   ix->last_fpath = chosen;
   ix->last_fallowed = m;
+  return s.copy_back();
+}
+
+int mrag_index_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                            int k, float min_score, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                            int filter_path, float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device,
+                            void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_nq_k(nq, k));
+  if (!std::isfinite(min_score)) return fail(MRAG_ERR_INVALID, "min_score must be finite, got %g", (double)min_score);
+  if (allow) {
+    if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
+    if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
+    if (filter_path != MRAG_FILTER_AUTO && filter_path != MRAG_FILTER_MASK && filter_path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown filter path %d", filter_path);
+  }
+  if (nq == 0) return MRAG_OK;
+  if (!out_counts) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_, out_counts};
+  MRAG_TRY(s.begin(queries, q_dtype, false, allow ? &ix->last_fpath : nullptr));
+  const int64_t n = ix->n;
+  int64_t m = n;                      // rows searched (allow-set: allowed rows when known on the host, else -1)
+  int chosen = -1;
+  if (allow) {
+    MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, filter_path != MRAG_FILTER_MASK, &m, ix->ev[0], s.stream));
+    chosen = filter_path != MRAG_FILTER_AUTO ? filter_path : filter_choose_path(nq, k, n, m, ix->ld);
+  } else {
+    MRAG_HIP(hipEventRecord(ix->ev[0], s.stream));
+  }
+  if (n == 0 || m == 0) {
+    MRAG_TRY(s.fill_empty());         // nothing to search: every slot (-inf, -1), every count 0
+  } else {
+    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
+    BfLaunch a;
+    MRAG_TRY(s.exact_launch(&a));
+    a.range = true;
+    a.floor = min_score;
+    a.out_counts = s.d_cnt;
+    a.rslots = &ix->rslots;
+    if (allow) MRAG_TRY(filter_search(ix->fw, a, chosen, m, s.stream));
+    else MRAG_TRY(bf_launch(a));
+  }
+  MRAG_TRY(s.end());
+  if (allow) {
+    ix->last_fpath = chosen;
+    ix->last_fallowed = m;
+  }
   return s.copy_back();
 }
 

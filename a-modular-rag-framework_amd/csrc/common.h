@@ -93,6 +93,11 @@ struct BfLaunch {
   const uint32_t* allow = nullptr;    // dense mode, optional: allow-set bitset over the corpus rows (bit r%32 of word r/32),
                                       // padded with zero words to whole 256-row tiles; runs the filtered (FILT) instances
   bool force_stream = false;          // dense mode, k <= 64: the streaming kernel whatever nq and the corpus size are
+  // range search (dense mode, 16-bit operands): the RANGE instances list only rows scoring >= `floor` and count them
+  bool range = false;
+  float floor = 0.f;                  // finite
+  int64_t* out_counts = nullptr;      // device [nq]: rows >= floor per query (NULL: lists only -- the wide-batch redo)
+  DevBuf* rslots = nullptr;           // workspace: one count slot per (workgroup, query)
 };
 int bf_launch(const BfLaunch& a);
 

@@ -9,6 +9,8 @@ descending, then row ascending.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 from typing import Optional, Tuple
 
 import numpy as np
@@ -122,6 +124,29 @@ def fp8_default_refine(k: int) -> int:
     return out.value
 
 
+def range_floor(min_score) -> np.float32:
+    """The fp32 floor a range search compares against: the smallest float32 >= ``min_score`` (so that "score >= floor"
+    on the fp32 scores means "score >= min_score").  NaN, +-inf and values beyond the float32 range raise ``ValueError``."""
+    if isinstance(min_score, (bool, np.bool_)) or not isinstance(min_score, numbers.Real):
+        raise ValueError(f"min_score must be a real number, got {min_score!r}")
+    x = float(min_score)
+    if not math.isfinite(x):
+        raise ValueError(f"min_score must be finite, got {min_score!r}")
+    with np.errstate(over="ignore"):
+        f = np.float32(x)
+    if not np.isfinite(f):
+        raise ValueError(f"min_score {min_score!r} lies outside the float32 range")
+    if float(f) < x:
+        f = np.nextafter(f, np.float32(np.inf))
+    return f
+
+
+def _check_k(k, k_max: int) -> int:
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= k_max:
+        raise ValueError(f"k must be an integer in [1, {k_max}], got {k!r}")
+    return int(k)
+
+
 def _stream_ptr(stream) -> Optional[int]:
     if stream is None:
         return None
@@ -161,6 +186,7 @@ class DenseIndex:
         N.check(self._lib.mrag_index_create(self.dim, N.METRIC_COSINE if metric == "cosine" else N.METRIC_IP,
                                             N.MRAG_F16 if dtype == "f16" else N.MRAG_BF16, self.device, C.byref(h)))
         self._h = h
+        self.id_base = 0
         if fp8_scan:
             self.enable_fp8()
 
@@ -192,6 +218,7 @@ class DenseIndex:
 
     def set_id_base(self, base: int):
         N.check(self._lib.mrag_index_set_id_base(self._h, int(base)))
+        self.id_base = int(base)
 
     def add(self, rows, normalize: Optional[bool] = None, stream=None):
         """Append rows ([n, dim] numpy / torch, host or device).  ``normalize`` defaults to
@@ -275,6 +302,102 @@ class DenseIndex:
             return self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), is_dev, int(k), aptr, n, afmt,
                                                         adev, path, sc, ids, out_dev, st)
         return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or adev), out)
+
+    def range_search(self, queries, min_score: float, k: int, normalize: Optional[bool] = None, allow=None,
+                     filter_path: str = "auto", stream=None, out=None, precision: str = "exact"):
+        """Rows scoring >= ``min_score`` (``mrag_index_search_range``) -> (scores [nq,k] fp32, ids [nq,k] int64, counts [nq]
+        int64).
+
+        Per query, with c = the number of rows scoring >= ``min_score`` (inclusive; the floor is the smallest float32 >=
+        ``min_score``, see :func:`range_floor`): the best ``min(k, c)`` of them, (score desc, row asc), then (-inf, -1)
+        slots; ``counts[q] = c`` exactly, so a query is truncated when ``counts[q] > k``.  Scores are the ones
+        :meth:`search` computes, and the search is exact.  ``min_score`` must be finite and ``1 <= k <= 256``
+        (``ValueError`` otherwise, before any GPU work).  Host queries give numpy arrays; CUDA tensors give CUDA tensors
+        written on ``stream``; ``out=(scores, ids, counts)`` reuses buffers.  ``allow`` / ``filter_path`` as in
+        :meth:`search`.  There is no fp8 range search: ``precision="fp8"`` raises ``ValueError``."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision == "fp8":
+            raise ValueError("precision='fp8' does not combine with a score floor (range search is exact only)")
+        floor = range_floor(min_score)
+        k = _check_k(k, self.max_k())
+        if filter_path not in FILTER_PATHS:
+            raise ValueError(f"filter_path must be one of {sorted(FILTER_PATHS)}, got {filter_path!r}")
+        if normalize is None:
+            normalize = self.metric == "cosine"
+        n, akeep, aptr, afmt, adev = 0, None, None, N.ALLOW_BITS32, 0
+        if allow is not None:
+            n = len(self)
+            akeep, aptr, afmt, adev = _allow_buffer(allow, n, self.device)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        if out is not None:
+            counts = out[2]
+        elif is_dev:
+            import torch
+            counts = torch.empty(nq, dtype=torch.int64, device=keep.device)
+        else:
+            counts = np.empty(nq, dtype=np.int64)
+        path = FILTER_PATHS[filter_path]
+        norm = int(bool(normalize))
+
+        def call(sc, ids, out_dev, st):
+            cptr = counts.data_ptr() if out_dev else counts.ctypes.data
+            return self._lib.mrag_index_search_range(self._h, ptr, nq, dt, norm, is_dev, k, float(floor), aptr, n, afmt, adev,
+                                                     path, sc, ids, cptr, out_dev, st)
+        sc, ids = _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or adev),
+                              None if out is None else (out[0], out[1]))
+        del akeep
+        return sc, ids, counts
+
+    def self_join(self, min_score: float, k: int = 64, batch: int = 16384):
+        """Every stored row as a query against all the others: its epsilon-neighbour list -> CUDA tensors on this index's
+        device (scores [n,k] fp32, ids [n,k] int64, counts [n] int64), as :meth:`range_search` returns them with the row
+        itself removed (``1 <= k <= 255``).
+
+        The stored 16-bit rows go to the search kernels device to device (unpacked to fp32 and rounded back: the same
+        bits, no renormalisation).  Batches of ``batch`` rows run in order on torch's current stream; the result does not
+        depend on ``batch``.  Each batch asks for k + 1 rows so that the row's own entry can be dropped exactly, also among
+        duplicate rows that tie with it; ``counts`` excludes the row itself when it reached the floor (with
+        ``metric="ip"`` it may not).  When more than k rows tie with or beat the row's own score its entry is not among
+        the k + 1 listed, and whether it reached the floor is decided from its fp64 self dot product."""
+        import torch
+        floor = range_floor(min_score)
+        k = _check_k(k, self.max_k() - 1)
+        if isinstance(batch, (bool, np.bool_)) or not isinstance(batch, numbers.Integral) or int(batch) < 1:
+            raise ValueError(f"batch must be a positive integer, got {batch!r}")
+        n, dev = len(self), torch.device("cuda", self.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        if n == 0:
+            return scores, ids, counts
+        stream = torch.cuda.current_stream(dev)
+        b = min(int(batch), n)
+        rows = torch.empty((b, self.dim), dtype=torch.float32, device=dev)
+        sc_b = torch.empty((b, k + 1), dtype=torch.float32, device=dev)
+        id_b = torch.empty((b, k + 1), dtype=torch.int64, device=dev)
+        cnt_b = torch.empty(b, dtype=torch.int64, device=dev)
+        with torch.cuda.stream(stream):
+            for r0 in range(0, n, b):
+                m = min(b, n - r0)
+                q = rows[:m]
+                N.check(self._lib.mrag_index_get_rows(self._h, r0, m, q.data_ptr(), 1, _stream_ptr(stream)))
+                s, i, c = self.range_search(q, float(floor), k + 1, normalize=False, stream=stream,
+                                            out=(sc_b[:m], id_b[:m], cnt_b[:m]))
+                own = torch.arange(r0, r0 + m, device=dev, dtype=torch.int64) + self.id_base
+                is_self = i == own[:, None]
+                found = is_self.any(dim=1)
+                # the row's own entry moves behind the others (stable), the first k remain
+                order = torch.argsort(is_self.to(torch.int8), dim=1, stable=True)[:, :k]
+                scores[r0:r0 + m] = torch.gather(s, 1, order)
+                ids[r0:r0 + m] = torch.gather(i, 1, order)
+                # listed -> it reached the floor; not listed with every row >= floor listed (c <= k + 1) -> it did not;
+                # otherwise more than k rows tie with or beat it: its fp64 self dot product decides
+                qd = q.to(torch.float64)
+                self_dot = (qd * qd).sum(dim=1)
+                reached = found | ((c > k + 1) & (self_dot >= float(floor)))
+                counts[r0:r0 + m] = c - reached.to(torch.int64)
+        return scores, ids, counts
 
     def last_filter(self) -> dict:
         """Path and allowed-row count of the last filtered search on this index (``mrag_index_last_filter``):

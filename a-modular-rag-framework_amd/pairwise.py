@@ -44,6 +44,44 @@ def semantic_edges(vectors, threshold: float = 0.9, device: int = 0) -> List[Tup
     return [(int(i), int(j), float(v)) for i, j, v in zip(iu[keep], ju[keep], s[iu, ju][keep])]
 
 
+def neighbor_lists_to_edges(scores, ids, id_base: int = 0) -> List[Tuple[int, int, float]]:
+    """Per-row neighbour lists (row r lists ``ids[r]`` with ``scores[r]``; ids carry ``id_base``, -1 = empty slot) ->
+    [(i, j, sim)] with i < j in (i, j) order.  A pair is an edge when either side lists the other; ``sim`` is the larger
+    of the two directions' scores.  A row listing itself is ignored."""
+    s = np.asarray(scores, dtype=np.float32)
+    ids = np.asarray(ids, dtype=np.int64)
+    if s.shape != ids.shape or ids.ndim != 2:
+        raise ValueError(f"expected matching [n, k] scores and ids, got {s.shape} and {ids.shape}")
+    n, k = ids.shape
+    src = np.repeat(np.arange(n, dtype=np.int64), k)
+    flat = ids.reshape(-1)
+    dst = flat - int(id_base)
+    sim = s.reshape(-1)
+    keep = (flat >= 0) & (dst != src)
+    src, dst, sim = src[keep], dst[keep], sim[keep]
+    if src.size == 0:
+        return []
+    i, j = np.minimum(src, dst), np.maximum(src, dst)
+    order = np.lexsort((-sim.astype(np.float64), j, i))   # by (i, j), the larger score first
+    i, j, sim = i[order], j[order], sim[order]
+    first = np.ones(i.size, dtype=bool)
+    first[1:] = (i[1:] != i[:-1]) | (j[1:] != j[:-1])
+    return [(int(a), int(b), float(v)) for a, b, v in zip(i[first], j[first], sim[first])]
+
+
+def semantic_edges_index(index, threshold: float = 0.9, k: int = 64, batch: int = 16384):
+    """``semantic_edges`` over the rows of a :class:`~mrag_amd.index.DenseIndex` at corpus scale -> (edges,
+    truncated_rows): the range self-join (:meth:`DenseIndex.self_join`) lists up to ``k`` neighbours >= ``threshold`` per
+    row (fp32 scores over the stored 16-bit rows) and :func:`neighbor_lists_to_edges` turns the lists into the
+    [(i, j, sim)] form of ``semantic_edges`` (local rows, i < j, (i, j) order).  ``truncated_rows`` (int64 array) lists
+    the rows with more than ``k`` neighbours >= ``threshold``: their edge sets may be incomplete.  ``semantic_edges``
+    stays the fp64 path."""
+    sc, ids, counts = index.self_join(threshold, k=k, batch=batch)
+    edges = neighbor_lists_to_edges(sc.cpu().numpy(), ids.cpu().numpy(), index.id_base)
+    truncated = np.nonzero(counts.cpu().numpy() > k)[0].astype(np.int64)
+    return edges, truncated
+
+
 def mmr_diversify(items: Sequence[Tuple[str, float, Optional[Sequence[float]]]], *, top_k: int = 20,
                   lambda_weight: float = 0.7, device: int = 0):
     """Same selection rule as the reference: first pick = best score; afterwards

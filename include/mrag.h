@@ -129,6 +129,22 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
 /* path the LAST filtered search on this handle took (MRAG_FILTER_MASK / MRAG_FILTER_COMPACT) and its allowed-row count.
  * Blocks until that search is done when the count is still on the device (device allow-set, MRAG_FILTER_MASK). */
 int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed);
+/* Range search: the rows scoring >= min_score ("every passage with cosine >= t"), with an exact count.  Per query, with c =
+ * the number of searched rows whose score is >= min_score (inclusive): out_scores / out_ids hold the best min(k, c) of them,
+ * (score desc, row asc), ids = id_base + row; the slots after them are (-inf, -1); out_counts[q] = c exactly (int64, in the
+ * memory space of the other outputs), so a query is truncated when out_counts[q] > k.  The score is the one the plain search
+ * computes (fp32 accumulation over the stored 16-bit row and the prepared query), and the search is exact in every regime.
+ * min_score must be finite (NaN / +-inf: MRAG_ERR_INVALID); 1 <= k <= mrag_index_max_k.  A floor below every score
+ * returns exactly what mrag_index_search (or, with an allow-set, mrag_index_search_filtered) returns, with counts = the
+ * searched rows; a floor above every score returns all (-inf, -1) and zero counts.
+ * allow == NULL searches every row; otherwise allow, allow_rows, allow_format, allow_is_device and filter_path are those of
+ * mrag_index_search_filtered (same AUTO rule, same record for mrag_index_last_filter).  Sync behaviour, streams, host and
+ * device outputs and mrag_index_last_timing as mrag_index_search / mrag_index_search_filtered.  The fp8 scan copy has no
+ * range mode. */
+int mrag_index_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                            int k, float min_score, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                            int filter_path, float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device,
+                            void* stream);
 /* fp8 scan copy + exact re-rank (cosine indexes).  mrag_index_enable_fp8 keeps, next to the 16-bit rows, an OCP e4m3fn
  * copy rows8 [capacity][ld8], ld8 = dim rounded up to 128: byte (r, c) = e4m3fn(clamp(256 * x, -448, 448)), x the STORED
  * 16-bit value of row r (exact in fp32), rounded to nearest even; pad rows and pad columns are 0.  |x| <= 1 for unit rows,
