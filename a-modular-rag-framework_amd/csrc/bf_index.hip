@@ -84,10 +84,7 @@ constexpr int SEG = 64;                   // private list segment per (query, la
 constexpr int KEPT = 64;                  // compacted entries per query (= largest k)
 constexpr int QCAP = KEPT + NGRP * SEG;   // 576 list entries per (workgroup, query)
 constexpr int KMAX = KEPT;
-#ifndef MRAG_DENSE_TILES
-#define MRAG_DENSE_TILES 8
-#endif
-constexpr int DENSE_TILES = MRAG_DENSE_TILES;             // tiles of a split filtered by the mask + LDS path (see the epilogue)
+constexpr int DENSE_TILES = 8;            // tiles of a split filtered by the mask + LDS path (see the epilogue)
 constexpr int K_CERT = 16;                // k served by the 16-row threshold certificate
 
 constexpr int OFF_TAU = GEMM_LDS;               // float[256]      k-th best after a compaction
@@ -115,8 +112,6 @@ struct BfParams {
   int xcd_map;              // 0: plain map; else S % 8 == 0 and this many query tiles share an XCD at a time
   const int* wg_desc;       // descriptor mode (IVF list scan): per workgroup {query row0, valid queries,
                             // first tile, end tile, end row, 0,0,0}; NULL = dense (t, s) decomposition
-  int dbg;                  // development ablations (MRAG_DEBUG_FLAGS); 0 in production
-  long long* stamps;        // dbg & 16: block 0 / wave 0 writes s_memtime stamps here
   long long* clock;         // 4 words or NULL: workgroup 0's s_memtime / s_memrealtime at entry and exit
   uint2* list;              // [T*S][256][QCAP]  {score bits, local row}: one 8-byte store per push
   int* counts;              // [T*S][256] entries left in the kept area
@@ -192,45 +187,18 @@ __device__ __forceinline__ void lds_store_u32(void* p, uint32_t x) {
   asm volatile("ds_write_b32 %0, %1" : : "v"(lds_off(p)), "v"(x) : "memory");
 }
 
-// Cache policy of the corpus-stream LDS-DMA loads ("" = default, " nt" = non-temporal), measured on one box:
+// Cache policy of the corpus-stream LDS-DMA loads (written into their asm strings), measured on one box:
 //   batch kernel (K2): the five workgroups of an XCD that share a corpus stream rely on each other's lines staying in
 //     L2 for a moment -- nt made it 13 % SLOWER (13.5 -> 15.2 ms at 10 k x 1M): default policy.
 //   streaming kernel (K2s): every corpus byte is read ONCE per launch by ONE workgroup -- nt: 0.270 -> 0.257 ms
 //     (5.69 -> 5.98 TB/s at 1 x 1M x 768).
-#ifndef MRAG_A_POLICY
-#define MRAG_A_POLICY ""
-#endif
-#ifndef MRAG_S_POLICY
-#define MRAG_S_POLICY " nt"
-#endif
-// K walk of the batch kernel.  1 / 2 = corpus tiles with an odd global index / odd index inside the split walk their K
-// steps last-to-first, so that the query K slices a workgroup has just used are the ones it asks for next (LRU-friendly:
-// the VERDICT r2 #1a experiment).  Measured round 3, same box, interleaved (tools/ab.sh): 10 000 x 1 M x 768
-// 13.83 / 13.88 / 13.90 ms forward vs 14.05 / 14.01 / 14.02 (by global parity) and 14.02 / 14.06 / 14.02 (by split
-// parity): 1.2 % SLOWER; 1 000 x 1 M 1.593-1.600 vs 1.593-1.613; C2 unchanged.  It also makes a row's fp32 accumulation
-// order depend on its tile parity (sharded != unsharded in the last bit).  Not taken: 0.
-#ifndef MRAG_ZZ
-#define MRAG_ZZ 0
-#endif
 
-// Diagnostics (ablations, s_memtime stamps) exist only in a -DMRAG_DIAG=<flags> build (make DIAG=<flags>):
-// the flags are COMPILE-TIME constants, so an ablated build carries no extra branches or registers
-// (run-time flags cost the K loop its register budget and made every ablation read 15-30 % slow).
-// the production kernel carries none of them.
-#ifdef MRAG_DIAG
-#define MRAG_DBG(bit) ((MRAG_DIAG) & (bit))
-#define MRAG_STAMP(i)                                                                     \
-  do {                                                                                    \
-    if (((MRAG_DIAG) & 16) && stamp_on && blockIdx.x == 0 && tid == 0 && stamp_n < 64) {   \
-      p.stamps[stamp_n * 2] = (i);                                                        \
-      p.stamps[stamp_n * 2 + 1] = (long long)__builtin_readcyclecounter();                \
-      ++stamp_n;                                                                          \
-    }                                                                                     \
-  } while (0)
-#else
-#define MRAG_DBG(bit) 0
-#define MRAG_STAMP(i) do { } while (0)
-#endif
+// K walk of the batch kernel: every corpus tile walks its K steps first-to-last.  Walking the K steps of every other tile
+// last-to-first (so that the query K slices a workgroup has just used are the ones it asks for next: the VERDICT r2 #1a
+// experiment) was measured round 3, same box, interleaved (tools/ab.sh): 10 000 x 1 M x 768 13.83 / 13.88 / 13.90 ms
+// forward vs 14.05 / 14.01 / 14.02 (by global parity) and 14.02 / 14.06 / 14.02 (by split parity): 1.2 % SLOWER;
+// 1 000 x 1 M 1.593-1.600 vs 1.593-1.613; C2 unchanged.  It also made a row's fp32 accumulation order depend on its tile
+// parity (sharded != unsharded in the last bit).  Not taken.
 
 // One wave compacts query q: the k best of its kept area + 8 segments go (sorted, best first)
 // into the kept area, the segments are emptied, tau_c rises to the k-th.  The keys are staged
@@ -357,10 +325,8 @@ __device__ __forceinline__ int tail_slot(const int (&pre)[NGRP + 1], int e) {
 // stage keys, rank.  `scratch` = the 8-KiB rank_and_keep work area of this wave.
 template <int NB, bool WIDE = false>
 __device__ __forceinline__ void tail_compact(uint2* __restrict__ wg_list, int q0, int k, int lane,
-                                             uint64_t* __restrict__ scratch, uint2* __restrict__ park, const float* thr_lds,
-                                             long long* dbg_t = nullptr) {
+                                             uint64_t* __restrict__ scratch, uint2* __restrict__ park, const float* thr_lds) {
   const int* kcnt = (const int*)(smem + OFF_KCNT);
-  if (dbg_t) dbg_t[0] = (long long)__builtin_readcyclecounter();
   const int* scnt = (const int*)(smem + OFF_SCNT);
   {
     uint2 first[NB];
@@ -374,10 +340,8 @@ __device__ __forceinline__ void tail_compact(uint2* __restrict__ wg_list, int q0
       first[u] = make_uint2(0u, 0u);
       if (lane < pre[NGRP]) first[u] = wg_list[(size_t)q * QCAP + tail_slot(pre, lane)];
     }
-    if (dbg_t) dbg_t[1] = (long long)__builtin_readcyclecounter();
 #pragma unroll
     for (int u = 0; u < NB; ++u) park[u * 64 + lane] = first[u];
-    if (dbg_t) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); dbg_t[2] = (long long)__builtin_readcyclecounter(); }
   }
 #pragma unroll 1
   for (int u = 0; u < NB; ++u) {
@@ -409,11 +373,8 @@ __device__ __forceinline__ void tail_compact(uint2* __restrict__ wg_list, int q0
       if (valid) scratch[total + __popcll(bal & ((1ull << lane) - 1ull))] = make_key(en.x, en.y);
       total += __popcll(bal);
     }
-    if (dbg_t && u < 4) dbg_t[3 + 2 * u] = (long long)__builtin_readcyclecounter();
     rank_and_keep<WIDE>(wg_list + (size_t)q * QCAP, q, k, lane, scratch, total);
-    if (dbg_t && u < 4) dbg_t[4 + 2 * u] = (long long)__builtin_readcyclecounter();
   }
-  if (dbg_t) dbg_t[11] = (long long)__builtin_readcyclecounter();
 }
 
 __device__ __forceinline__ void compact_query(uint2* __restrict__ lst, int q, int k,
@@ -481,25 +442,13 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
   constexpr int WN = 16 / NF;            // waves along the query dimension
   constexpr int NW = 2 * WN;             // waves per workgroup
   constexpr int NT = 64 * NW;            // threads per workgroup
-  // Wave roles (MRAG_K2_ROLES=1): only waves 0-3 (one per SIMD) issue the LDS-DMA loads of a stage, 16 each instead of 8 from
-  // every wave: the SIMD partner of a loading wave goes straight to its fragment reads and MFMAs, so the two waves of a SIMD
-  // stop hitting their DMA issues, their read bursts and the barrier together.
-#ifndef MRAG_K2_ROLES
-#define MRAG_K2_ROLES 0
-#endif
-  constexpr bool ROLES = MRAG_K2_ROLES != 0 && NW == 8;
-  constexpr int CPW = ROLES ? 8 : 32 / NW;           // 1-KiB DMA chunks per (loading) wave per operand and stage
+  constexpr int CPW = 32 / NW;           // 1-KiB DMA chunks per wave per operand and stage
   constexpr int QPW = TQ / NW;           // queries whose lists a wave owns (compaction)
   typedef typename Mfma<DT>::frag frag;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w / WN, wn = w % WN;
-#ifdef MRAG_DIAG
-  int stamp_n = 0;
-  bool stamp_on = true;   // narrowed to tiles 60..65 of the split inside the tile loop (the sparse regime)
-#endif
-  MRAG_STAMP(0);
   // held clock = d(s_memtime) / d(s_memrealtime) x 100 MHz over workgroup 0's lifetime (MI355X_MICROARCH.md, DVFS
   // item 6): two stamps at entry, two at exit, written by one lane to a buffer nothing else reads; p.clock is
   // NULL unless the caller asked for the reading (bench.py's "held_clock_ghz")
@@ -537,7 +486,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     tile_hi = (int)(((long long)(s + 1) * p.n_ctiles) / p.S);
     rows_end = p.n_rows;
   }
-  uint2* wg_list = p.list + (MRAG_DBG(64) ? (size_t)(wg & 255) : (size_t)wg) * TQ * QCAP;   // diag 64: alias list memory (timing only)
+  uint2* wg_list = p.list + (size_t)wg * TQ * QCAP;
   const int ksteps = p.ksteps;
 
   float* tau_c = (float*)(smem + OFF_TAU);
@@ -566,31 +515,27 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
   const uint32_t row_b = (uint32_t)p.ld * 2u;                       // bytes per row
   const uint32_t voff_e = (uint32_t)(lane >> 3) * row_b + (uint32_t)(((lane & 7) ^ (lane >> 4)) * 16);        // even chunks
   const uint32_t voff_o = (uint32_t)(lane >> 3) * row_b + (uint32_t)(((lane & 7) ^ (4 + (lane >> 4))) * 16);  // odd chunks
-  const int lw = ROLES ? (w & 3) : w;          // loading wave's slot
-  const bool loader = !ROLES || w < 4;
-  const char* q_ptr = (const char*)(p.queries + (size_t)q_row0 * p.ld) + (size_t)(CPW * lw) * 8 * row_b;
+  const char* q_ptr = (const char*)(p.queries + (size_t)q_row0 * p.ld) + (size_t)(CPW * w) * 8 * row_b;
   const size_t tile_bytes = (size_t)TM * p.ld * 2;
   const uint32_t chunk_b = 8u * row_b;                               // 8 rows
 
   // One stage = 2*CPW LDS-DMA loads per wave (CPW corpus chunks, CPW query chunks), issued from inline
   // asm two at a time.  hipcc does not count them: every wait for them is an explicit s_waitcnt vmcnt
   // below.  M0 (LDS destination base) is written inside the statement that uses it and restored after.
-  f32x4 dbg_sink0 = {0.f, 0.f, 0.f, 0.f}, dbg_sink1 = {0.f, 0.f, 0.f, 0.f};   // diag 16384 only
   constexpr int NPART = CPW;   // two chunks per part, two operands
   auto stage_part = [&](const char* a, const char* b, int buf, int part) {   // first half of the parts: corpus chunks; second half: query chunks
-    if (!loader) return;
     const int op = part / (NPART / 2), i = (part % (NPART / 2)) * 2;
-    if (op == 1 && (CPW * lw + i) * 8 >= nq_local && DESC) return;
+    if (op == 1 && (CPW * w + i) * 8 >= nq_local && DESC) return;
     const char* base = op ? b : a;
-    const uint32_t la = (uint32_t)(buf * STAGE_BYTES + op * A_BYTES + (CPW * lw + i) * 1024);   // wave-uniform
+    const uint32_t la = (uint32_t)(buf * STAGE_BYTES + op * A_BYTES + (CPW * w + i) * 1024);   // wave-uniform
     const char* c0 = base + (size_t)i * chunk_b;
     const char* c1 = c0 + chunk_b;
     uint32_t keep;
-    if (op == 0) {   // corpus chunks: streamed once per workgroup (cache policy: MRAG_A_POLICY)
+    if (op == 0) {   // corpus chunks: streamed once per workgroup (cache policy: default, see the top of the file)
       asm volatile(
           "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3" MRAG_A_POLICY "\n\t"
-          "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %4" MRAG_A_POLICY "\n\t"
+          "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+          "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %4\n\t"
           "s_mov_b32 m0, %0"
           : "=&s"(keep)
           : "v"(voff_e), "v"(voff_o), "s"(c0), "s"(c1), "s"(la)
@@ -628,24 +573,17 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 
   // prefetch cursor: (tile, k step) of the NEXT stage to issue, advanced with scalar adds only
   const int n_tiles = tile_hi - tile_lo;
-  const char* a_tile = (const char*)p.corpus + (size_t)tile_lo * tile_bytes + (size_t)(CPW * lw) * 8 * row_b;   // tile being prefetched (+ this wave's row block)
+  const char* a_tile = (const char*)p.corpus + (size_t)tile_lo * tile_bytes + (size_t)(CPW * w) * 8 * row_b;   // tile being prefetched (+ this wave's row block)
   int pf_kk = 0, pf_left = n_tiles * ksteps;
-  // K walk direction (MRAG_ZZ, see the top of the file): 0 = every corpus tile first-to-last (shipped)
-  int pf_tile = (MRAG_ZZ == 2) ? 0 : tile_lo;
-  auto pf_koff = [&]() -> int {
-    if (DESC || MRAG_ZZ == 0) return pf_kk * (BK * 2);
-    return ((pf_tile & 1) ? (ksteps - 1 - pf_kk) : pf_kk) * (BK * 2);
-  };
   int buf = 0;
   if (pf_left > 0) {
-    const int ko = pf_koff();
+    const int ko = pf_kk * (BK * 2);
     stage(a_tile + ko, q_ptr + ko, 0);
     --pf_left;
-    if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; ++pf_tile; }
+    if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  MRAG_STAMP(1);
 
   // One K step: prefetch the next stage, then this stage's fragment reads + 64 MFMAs per wave.
   // PENDING: the previous K step of this corpus tile left its k-half-1 fragments in f1a/f1b;
@@ -658,24 +596,23 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     // follow two at a time between the pending MFMAs (corpus chunks first: they can miss L2), so that the wave
     // feeds the MFMA pipe again after 2 DMA issues instead of 8 (all at the top: 13.38 ms; 4 + 4: 13.21; 2 + 6: 13.22
     // vs 13.38 in a second pairing).
-    const bool do_stage = pf_left > 0 && !MRAG_DBG(4);   // diag 4: ablate the loads
-    const int st_ko = pf_koff();
+    const bool do_stage = pf_left > 0;
+    const int st_ko = pf_kk * (BK * 2);
     const char* st_a = a_tile + st_ko;
     const char* st_b = q_ptr + st_ko;
     const int st_buf = buf ^ 1;
     if (do_stage) {
       --pf_left;
-      if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; ++pf_tile; }
+      if (++pf_kk == ksteps) { pf_kk = 0; a_tile += tile_bytes; }
 #pragma unroll
       for (int pp = 0; pp < NPART / 4; ++pp) stage_part(st_a, st_b, st_buf, pp);
-      if (!PENDING || MRAG_DBG(8) || DT == MRAG_DT_FP8) {
+      if (!PENDING || DT == MRAG_DT_FP8) {
 #pragma unroll
         for (int pp = NPART / 4; pp < NPART; ++pp) stage_part(st_a, st_b, st_buf, pp);
       }
     }
     const char* sb = smem + buf * STAGE_BYTES;
     buf ^= 1;
-    if (MRAG_DBG(8)) return;   // diag 8: ablate LDS reads + MFMA
     if constexpr (DT == MRAG_DT_FP8) {
       // fp8: ONE MFMA per (mf, nf) and step, nothing carried over to the next step.  The B fragments and A rows mf 0-1
       // (12 reads) go first; then the MFMAs of mf run while the reads of mf + 2 land (4 MFMAs, 2 reads, six times).
@@ -715,7 +652,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) f0b[nf] = *(const frag*)(sb + b_rd + nf * 2048 + ph0);
 #pragma unroll
-      for (int mf = 0; mf < 8; ++mf) f0a[mf] = (MRAG_DBG(8192) && mf >= 4) ? f0a[mf - 4] : *(const frag*)(sb + a_rd + mf * 2048 + ph0);   // diag 8192: a third fewer LDS reads (timing only)
+      for (int mf = 0; mf < 8; ++mf) f0a[mf] = *(const frag*)(sb + a_rd + mf * 2048 + ph0);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (PENDING) {
 #pragma unroll
@@ -738,7 +675,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) f1b[nf] = *(const frag*)(sb + b_rd + nf * 2048 + ph1);
 #pragma unroll
-      for (int mf = 0; mf < 8; ++mf) f1a[mf] = (MRAG_DBG(8192) && mf >= 4) ? f1a[mf - 4] : *(const frag*)(sb + a_rd + mf * 2048 + ph1);
+      for (int mf = 0; mf < 8; ++mf) f1a[mf] = *(const frag*)(sb + a_rd + mf * 2048 + ph1);
 #pragma unroll
       for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
@@ -758,10 +695,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
   };
 
   for (int ti = 0; ti < n_tiles; ++ti) {
-#ifdef MRAG_DIAG
-    stamp_on = DESC || (ti >= 60 && ti < 66);   // descriptor mode (IVF): one or two tiles per workgroup, stamp them all
-    MRAG_STAMP(2);
-#endif
     // allow-set words of this wave's 128 rows of the tile (wave-uniform: one scalar load, issued before the K loop so
     // that its latency hides under the tile's MFMAs)
     u32x4 allow_w = {~0u, ~0u, ~0u, ~0u};
@@ -772,24 +705,13 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
       kstep_sync();
       kstep(std::true_type{});
     }
-    if constexpr (!MRAG_DBG(8) && DT != MRAG_DT_FP8) {   // drain: k half 1 of the last K step (fp8: nothing pending)
+    if constexpr (DT != MRAG_DT_FP8) {   // drain: k half 1 of the last K step (fp8: nothing pending)
 #pragma unroll
       for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = Mfma<DT>::run(f1a[mf], f1b[nf], acc[mf][nf]);
     }
-    MRAG_STAMP(3);
-    if (MRAG_DBG(1)) {
-      // ablation: no top-k filter; keep the accumulators observable, then clear them
-      float x = 0.f;
-#pragma unroll
-      for (int mf = 0; mf < 8; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          x += acc[mf][nf][0] + acc[mf][nf][1] + acc[mf][nf][2] + acc[mf][nf][3];
-        }
-      if (x == 123456.789f) kcnt[0] = 1;
-    } else {
+    {
       // =========================== fused top-k epilogue ===================================
       const int tile = tile_lo + ti;   // ti = tile index inside the split
       // lane-derived values are recomputed from an opaque copy so that nothing the epilogue
@@ -801,7 +723,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
       const int grp = wm * 4 + (elane >> 4);                     // this lane's segment of each of its queries
       const bool certify = p.k <= K_CERT;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stage prefetched during the last K step has landed (issued a K step ago: no stall)
-      MRAG_STAMP(10 + (ti == 0 ? 0 : 100));
       if ((tile + 1) * TM > rows_end) {
 #pragma unroll
         for (int mf = 0; mf < 8; ++mf)
@@ -884,7 +805,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
             }
             __syncthreads();
           }
-          MRAG_STAMP(11);
 #pragma unroll
           for (int nf = 0; nf < NF; ++nf) thr[nf] = next_below(ord_f32(stat_cur[q0 + nf * 16]));
           if constexpr (RANGE) {
@@ -929,7 +849,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) cseg[nf] = scnt[(q0 + nf * 16) * NGRP + grp];
       if (ti < DENSE_TILES) __builtin_amdgcn_s_barrier();   // every wave is done reading the stage buffer the dense push pass reuses as scratch
-      MRAG_STAMP(21);
 
       // ---- push: attempt 0 = whole tile at once; a full segment -> replay in 4 sub-rounds ------
       int attempt = 0, round = 0;
@@ -953,7 +872,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
   #pragma unroll
             for (int mf = 0; mf < 8; ++mf) tm = fmaxf(tm, fmaxf(fmaxf(acc[mf][nf][0], acc[mf][nf][1]), fmaxf(acc[mf][nf][2], acc[mf][nf][3])));
             tmax[nf] = tm;
-            if (!__any(tm > thr[nf]) || MRAG_DBG(32 | 512)) continue;   // dbg 32: ablate list pushes (512: of the dense path only)
+            if (!__any(tm > thr[nf])) continue;
             uint32_t pm = 0u;
   #pragma unroll
             for (int mf = 7; mf >= 0; --mf)
@@ -1001,7 +920,7 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
             for (int mf = 0; mf < 8; ++mf) {
               const f32x4 a = acc[mf][nf];
               if (attempt && (mf >> 1) != round) continue;      // replay: 2 accumulators (<= 8 pushes/segment) per round
-              if (hit[mf] == 0ull || MRAG_DBG(32 | 1024)) continue;   // dbg 32: ablate list pushes (1024: of the sparse path only)
+              if (hit[mf] == 0ull) continue;
   #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 if (a[j] > thr[nf]) {
@@ -1024,7 +943,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
           for (int nf = 0; nf < NF; ++nf) over |= cseg[nf] > SEG;
           if (over) lds_store_u32(&flags[0], 1u);
         }
-        MRAG_STAMP(22);
         if (attempt == 0 && certify && ti != 0) {
           // fold this tile's maxima into the running certificate used from the NEXT tile on
           // (the four columns as four independent chains: all loads, then all stores, then the shuffles --
@@ -1050,7 +968,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
           for (int nf = 0; nf < NF; ++nf)
             if (elane < 16) lds_min_u32(&stat_cur[q0 + nf * 16], f32_ord(x[nf]));
         }
-        MRAG_STAMP(12 + (ti == 0 ? 0 : 100));
         // This barrier also publishes the stage prefetched during the last K step (every wave waited
         // for its own LDS-DMA loads at the top of the epilogue), so the common path needs no second
         // barrier per tile.  It is a RAW barrier behind an LDS-only wait: the list stores of this tile
@@ -1060,7 +977,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        MRAG_STAMP(13 + (ti == 0 ? 0 : 100));
         if (attempt == 0) {
           if (!flags[0]) {
 #pragma unroll
@@ -1147,7 +1063,6 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
         for (int qq = 0; qq < QPW; qq += 4)
           tail_compact<4>(wg_list, w * QPW + qq, p.k, elane, scr, (uint2*)(scr + 768), tau_c);
       }
-      MRAG_STAMP(14 + (ti == 0 ? 0 : 100));
       if (resync) __syncthreads();
       // (the accumulators are not cleared: the first K step of the next tile starts from a zero C operand)
       // The K loop's lane constants may have been spilled around the epilogue.  Touch them HERE so
@@ -1155,19 +1070,13 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
       // prefetch it cannot see) sits at the end of the epilogue, not inside the next K step.
       asm volatile("" :: "v"(a_rd), "v"(b_rd), "v"(ph0), "v"(voff_e), "v"(voff_o));
     }
-    if (MRAG_DBG(1)) kstep_sync();
   }
 
-  if (MRAG_DBG(16384)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); asm volatile("" :: "v"(dbg_sink0), "v"(dbg_sink1)); }
   __syncthreads();
-#ifdef MRAG_DIAG
-  stamp_on = true;
-#endif
-  MRAG_STAMP(98);
   // ---- end of the split: every query's list is cut to its k best (sorted) so that K4 only has to
   // merge S x k entries.  Entries below the final certified threshold are dropped before ranking
   // (typically ~25 of ~170 survive), which is what keeps this tail at ~1 % of the workgroup's time.
-  if (n_tiles > 0 && !MRAG_DBG(2048)) {   // dbg 2048: ablate the end-of-split compaction
+  if (n_tiles > 0) {
     const uint32_t* stat_last = stat + ((n_tiles - 1) & 1) * TQ;
     uint64_t* scratch = (uint64_t*)(smem + w * 8192);
     // 16 queries per pass: two memory latencies per wave for its 32 lists (they are spread over GBs of
@@ -1178,18 +1087,9 @@ __global__ __launch_bounds__(64 * 2 * (16 / NF), NF == 4 ? 2 : 1) void bf_gemm_t
     }
     constexpr int TB = 16;
     uint2* park = (uint2*)(smem + NW * 8192 + w * 8192);
-#ifdef MRAG_DIAG
-    long long tt[12] = {0};
-    for (int qq = 0; qq < QPW; qq += TB)
-      tail_compact<TB, true>(wg_list, w * QPW + qq, p.k, lane, scratch, park, tau_c, (((MRAG_DIAG) & 16) && qq == 0) ? tt : nullptr);
-    if (((MRAG_DIAG) & 16) && blockIdx.x == 0 && tid == 0 && p.stamps)
-      for (int i = 0; i < 12; ++i) p.stamps[100 + i] = tt[i] - tt[0];
-#else
     for (int qq = 0; qq < QPW; qq += TB) tail_compact<TB, true>(wg_list, w * QPW + qq, p.k, lane, scratch, park, tau_c);
-#endif
   }
   __syncthreads();
-  MRAG_STAMP(99);
   if (!DESC && p.clock && blockIdx.x == 0 && tid == 0) {
     p.clock[2] = (long long)__builtin_amdgcn_s_memtime();
     p.clock[3] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -1304,10 +1204,10 @@ __global__ __launch_bounds__(NTHR, 2) void bf_stream_topk_kernel(StreamParams p)
     uint32_t keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %4" MRAG_S_POLICY "\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5" MRAG_S_POLICY "\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %6" MRAG_S_POLICY "\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %7" MRAG_S_POLICY "\n\t"
+        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %4 nt\n\t"
+        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5 nt\n\t"
+        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %6 nt\n\t"
+        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %7 nt\n\t"
         "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %8\n\t"
         "s_mov_b32 m0, %0"
         : "=&s"(keep)
@@ -2089,25 +1989,6 @@ struct BfIndex : Object {
   }
 };
 
-#ifdef MRAG_DIAG
-static long long* g_stamps = nullptr;  // diagnostic s_memtime stamps (MRAG_DEBUG_FLAGS & 16)
-#endif
-
-#ifdef MRAG_DIAG
-static int dump_stamps(int dbg, hipStream_t stream) {
-  if (!g_stamps || !(dbg & 16)) return MRAG_OK;
-  long long hs[128];
-  MRAG_HIP(hipStreamSynchronize(stream));
-  MRAG_HIP(hipMemcpy(hs, g_stamps, sizeof(hs), hipMemcpyDeviceToHost));
-  fprintf(stderr, "[mrag tail] first pass of 16 queries, cycles from its start: loads issued %lld, parked %lld; query 0 staged %lld ranked %lld; q1 %lld %lld; q2 %lld %lld; q3 %lld %lld; pass done %lld\n",
-          hs[101], hs[102], hs[103], hs[104], hs[105], hs[106], hs[107], hs[108], hs[109], hs[110], hs[111]);
-  fprintf(stderr, "[mrag stamps]");
-  for (int i = 0; i < 64 && (i == 0 || hs[2 * i + 1]); ++i) fprintf(stderr, " %lld:%lld", hs[2 * i], hs[2 * i + 1] - hs[1]);
-  fprintf(stderr, "\n");
-  return MRAG_OK;
-}
-#endif
-
 static size_t dtype_size(int dt) {
   switch (dt) { case MRAG_F32: return 4; case MRAG_F16: case MRAG_BF16: return 2; case MRAG_F64: return 8; default: return 0; }
 }
@@ -2167,9 +2048,7 @@ static void choose_split(int T, int n_ctiles, int* S_out, int* xcd_out) {
     n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
                ? pr.multiProcessorCount : 256;
   }
-  int S = std::max(1, std::min(n_ctiles, n_cu / std::max(1, T)));
-  { const char* fs = getenv("MRAG_S");   // experiment: force the split count
-    if (fs && atoi(fs) > 0) S = std::min(atoi(fs), n_ctiles); }
+  const int S = std::max(1, std::min(n_ctiles, n_cu / std::max(1, T)));
   *S_out = S;
   // the XCD-aware block map needs a grid that splits evenly over the 8 XCDs, and pays when an XCD then holds
   // >= 2 whole query tiles (their workgroups share the corpus streams); with fewer it measured 3-6 % slower
@@ -2192,9 +2071,8 @@ constexpr int MAX_QTILES_PER_LAUNCH = 64;
 // The regime of a dense search of nq queries over n_rows rows: bf_launch runs it, AUTO's filter rule plans for it.
 enum BfRegime { BF_STREAM, BF_WIDE_BATCH, BF_BATCH };
 static BfRegime bf_regime(int64_t nq, int k, int64_t n_rows, bool force_stream) {
-  static const bool wide_off = [] { const char* e = getenv("MRAG_NO_WIDE_BATCH"); return e && atoi(e) != 0; }();   // test knob: every k > 64 search through the streaming kernel
   const int64_t n_ctiles = (n_rows + TM - 1) / TM;
-  if (k > KMAX && nq > 32 && n_ctiles >= 64 && !wide_off) return BF_WIDE_BATCH;
+  if (k > KMAX && nq > 32 && n_ctiles >= 64) return BF_WIDE_BATCH;
   if (k > KMAX || force_stream || (nq <= (k > 32 ? 8 : SQ) && n_ctiles >= 8)) return BF_STREAM;
   return BF_BATCH;
 }
@@ -2213,67 +2091,52 @@ static int set_max_lds(const void* fn, int bytes) {
 // K2 launcher.  The kernel is templated on the wave tiling; only the 8-wave form (NF = 4) is built:
 // the 4-wave / one-wave-per-SIMD form (NF = 8, 256 accumulator registers per lane) is correct but
 // hipcc's allocation of the 256-AGPR tile spills into the K loop (98 ms vs 13.6 ms, round-1 measurement).
-// Column 2 = the filtered dense instance (FILT), picked only when p.allow is set.
-// Row 2 = the fp8 scan copy (mrag_index_search_fp8): dense instance only.
+// The instance follows p: column 1 = descriptor mode (p.wg_desc), 2 = filtered dense (FILT, p.allow), 3 = range (RANGE,
+// p.rcounts), 4 = range + filtered.  Row 2 = the fp8 scan copy (mrag_index_search_fp8): plain dense instance only.
 static int dtype_slot(int dtype) { return dtype == MRAG_F16 ? 0 : (dtype == MRAG_BF16 ? 1 : 2); }
 static int launch_k2(int dtype, size_t grid, hipStream_t stream, const BfParams& p) {
   typedef void (*K2Fn)(BfParams);
-  static const K2Fn fns[3][3] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>,
-                                  bf_gemm_topk_kernel<MRAG_F16, 4, false, true>},
+  static const K2Fn fns[3][5] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false>, bf_gemm_topk_kernel<MRAG_F16, 4, true>,
+                                  bf_gemm_topk_kernel<MRAG_F16, 4, false, true>, bf_gemm_topk_kernel<MRAG_F16, 4, false, false, true>,
+                                  bf_gemm_topk_kernel<MRAG_F16, 4, false, true, true>},
                                  {bf_gemm_topk_kernel<MRAG_BF16, 4, false>, bf_gemm_topk_kernel<MRAG_BF16, 4, true>,
-                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>},
-                                 {bf_gemm_topk_kernel<MRAG_DT_FP8, 4, false>, nullptr, nullptr}};
-  const int di = dtype_slot(dtype), de = p.wg_desc ? 1 : (p.allow ? 2 : 0);
+                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true>, bf_gemm_topk_kernel<MRAG_BF16, 4, false, false, true>,
+                                  bf_gemm_topk_kernel<MRAG_BF16, 4, false, true, true>},
+                                 {bf_gemm_topk_kernel<MRAG_DT_FP8, 4, false>, nullptr, nullptr, nullptr, nullptr}};
+  const bool range = p.rcounts != nullptr;
+  const int di = dtype_slot(dtype), de = range ? (p.allow ? 4 : 3) : (p.wg_desc ? 1 : (p.allow ? 2 : 0));
+  if (range && (di > 1 || p.wg_desc)) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
   if (!fns[di][de]) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
-  MRAG_TRY(set_max_lds((const void*)fns[di][de], LDS_TOTAL));
+  const int lds = range ? LDS_TOTAL_RANGE : LDS_TOTAL;
+  MRAG_TRY(set_max_lds((const void*)fns[di][de], lds));
   if (!grid) return MRAG_OK;
-  hipLaunchKernelGGL(fns[di][de], dim3((unsigned)grid), dim3(NTHR), LDS_TOTAL, stream, p);
-  MRAG_HIP(hipGetLastError());
-  return MRAG_OK;
-}
-// the RANGE instances (range search): [16-bit dtype slot][filtered (path M)]
-static int launch_k2_range(int dtype, size_t grid, hipStream_t stream, const BfParams& p) {
-  typedef void (*K2Fn)(BfParams);
-  static const K2Fn fns[2][2] = {{bf_gemm_topk_kernel<MRAG_F16, 4, false, false, true>, bf_gemm_topk_kernel<MRAG_F16, 4, false, true, true>},
-                                 {bf_gemm_topk_kernel<MRAG_BF16, 4, false, false, true>, bf_gemm_topk_kernel<MRAG_BF16, 4, false, true, true>}};
-  const int di = dtype_slot(dtype);
-  if (di > 1 || p.wg_desc) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
-  const K2Fn fn = fns[di][p.allow ? 1 : 0];
-  MRAG_TRY(set_max_lds((const void*)fn, LDS_TOTAL_RANGE));
-  if (!grid) return MRAG_OK;
-  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(NTHR), LDS_TOTAL_RANGE, stream, p);
+  hipLaunchKernelGGL(fns[di][de], dim3((unsigned)grid), dim3(NTHR), lds, stream, p);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
 
-// K2s instances: [dtype slot][filtered (path M)][512-entry lists (k > 32)]; the fp8 row serves the plain search only.
+// K2s instances: [dtype slot][filtered (path M)][range][512-entry lists (k > 32)]; the fp8 row serves the plain search only.
 // The 512-entry-list instance also wins for 32 < k <= 64: with 128-entry lists a list of k = 64 is compacted after every
 // 64-row chunk (1 x 1M x 768: 0.431 ms at k = 64 against 0.332 ms at k = 100 on the wide instance)
 typedef void (*K2sFn)(StreamParams);
-static int k2s_instance(int dtype, bool filt, bool wide, K2sFn* fn, int* lds) {
-  static const K2sFn fns[3][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
-                                      {bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>}},
-                                     {{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
-                                      {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>}},
-                                     {{bf_stream_topk_kernel<MRAG_DT_FP8, 2, 128>, bf_stream_topk_kernel<MRAG_DT_FP8, 1, 512>},
-                                      {nullptr, nullptr}}};
-  static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
-  *fn = fns[dtype_slot(dtype)][filt][wide];
-  *lds = slds[wide];
-  if (!*fn) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
-  return set_max_lds((const void*)*fn, *lds);
-}
-// the RANGE instances of K2s: [16-bit dtype slot][filtered][512-entry lists]
-static int k2s_range_instance(int dtype, bool filt, bool wide, K2sFn* fn, int* lds) {
-  static const K2sFn fns[2][2][2] = {{{bf_stream_topk_kernel<MRAG_F16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, false, true>},
-                                      {bf_stream_topk_kernel<MRAG_F16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true, true>}},
-                                     {{bf_stream_topk_kernel<MRAG_BF16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, false, true>},
-                                      {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true, true>}}};
+static int k2s_instance(int dtype, bool filt, bool range, bool wide, K2sFn* fn, int* lds) {
+  static const K2sFn fns[3][2][2][2] = {
+      {{{bf_stream_topk_kernel<MRAG_F16, 2, 128>, bf_stream_topk_kernel<MRAG_F16, 1, 512>},
+        {bf_stream_topk_kernel<MRAG_F16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, false, true>}},
+       {{bf_stream_topk_kernel<MRAG_F16, 2, 128, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true>},
+        {bf_stream_topk_kernel<MRAG_F16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_F16, 1, 512, true, true>}}},
+      {{{bf_stream_topk_kernel<MRAG_BF16, 2, 128>, bf_stream_topk_kernel<MRAG_BF16, 1, 512>},
+        {bf_stream_topk_kernel<MRAG_BF16, 2, 128, false, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, false, true>}},
+       {{bf_stream_topk_kernel<MRAG_BF16, 2, 128, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true>},
+        {bf_stream_topk_kernel<MRAG_BF16, 2, 128, true, true>, bf_stream_topk_kernel<MRAG_BF16, 1, 512, true, true>}}},
+      {{{bf_stream_topk_kernel<MRAG_DT_FP8, 2, 128>, bf_stream_topk_kernel<MRAG_DT_FP8, 1, 512>}, {nullptr, nullptr}},
+       {{nullptr, nullptr}, {nullptr, nullptr}}}};
   static const int slds[2] = {StreamLds<2, 128>::TOTAL, StreamLds<1, 512>::TOTAL};
   const int di = dtype_slot(dtype);
-  if (di > 1) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
-  *fn = fns[di][filt][wide];
+  if (range && di > 1) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense 16-bit index only");
+  *fn = fns[di][filt][range][wide];
   *lds = slds[wide];
+  if (!*fn) return fail(MRAG_ERR_UNSUPPORTED, "the fp8 scan serves the plain dense search only");
   return set_max_lds((const void*)*fn, *lds);
 }
 // range search: the per-query sums of the count slots of one launch (T query tiles x S splits) -> out[0 .. nq)
@@ -2306,23 +2169,11 @@ int bf_launch(const BfLaunch& a) {
   p.ld = a.ld;
   p.ksteps = a.ld / BK;
   p.k = a.k;
-  p.dbg = 0;
-  p.stamps = nullptr;
   p.clock = a.clock;
   p.allow = a.wg_desc ? nullptr : a.allow;
   p.floor = a.floor;
   p.rcounts = nullptr;
   if (a.range && (a.wg_desc || !a.rslots)) return fail(MRAG_ERR_UNSUPPORTED, "range search serves the dense mode only");
-#ifdef MRAG_DIAG
-  {
-    p.dbg = MRAG_DIAG;
-    if (p.dbg & 16) {
-      if (!g_stamps) MRAG_HIP(hipMalloc((void**)&g_stamps, 128 * 8));
-      MRAG_HIP(hipMemsetAsync(g_stamps, 0, 128 * 8, stream));
-      p.stamps = g_stamps;
-    }
-  }
-#endif
   if (a.ev_k2_begin) MRAG_HIP(hipEventRecord(a.ev_k2_begin, stream));
   if (a.wg_desc) {
     // ---- descriptor mode: one launch, one merge -------------------------------------------
@@ -2336,9 +2187,6 @@ int bf_launch(const BfLaunch& a) {
     p.counts = (int*)a.counts->p;
     MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
     if (a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
-#ifdef MRAG_DIAG
-    MRAG_TRY(dump_stamps(p.dbg, stream));
-#endif
     if (a.nq) {
       const MergeParams mp = merge_params(a, p.list, p.counts, 0, 0, a.nq, a.out_scores, a.out_ids);
       hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)a.nq), dim3(64), (size_t)mp.cap * 8, stream, mp);
@@ -2355,8 +2203,7 @@ int bf_launch(const BfLaunch& a) {
     const bool wi = a.k > 32;
     K2sFn fn;
     int lds;
-    if (a.range) MRAG_TRY(k2s_range_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
-    else MRAG_TRY(k2s_instance(a.dtype, a.allow != nullptr, wi, &fn, &lds));
+    MRAG_TRY(k2s_instance(a.dtype, a.allow != nullptr, a.range, wi, &fn, &lds));
     const int grp = wi ? 8 : SQ;
     const int S = std::max(1, std::min(n_ctiles, 256));
     if (!extra_counts) {    // (a caller with extra_counts has sized both workspaces itself: ensure() does not keep contents)
@@ -2443,12 +2290,8 @@ int bf_launch(const BfLaunch& a) {
     p.wg_desc = nullptr;
     p.list = (uint2*)a.lists->p;
     p.counts = (int*)a.counts->p;
-    if (a.range) {
-      p.rcounts = (int*)a.rslots->p;
-      MRAG_TRY(launch_k2_range(a.dtype, grid, stream, p));
-    } else {
-      MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
-    }
+    p.rcounts = a.range ? (int*)a.rslots->p : nullptr;
+    MRAG_TRY(launch_k2(a.dtype, grid, stream, p));
     if (t0 + T_max >= T_all && a.ev_k2_end) MRAG_HIP(hipEventRecord(a.ev_k2_end, stream));
     if (a.range) MRAG_TRY(launch_range_sum(a, S, nq, a.out_counts ? a.out_counts + q0 : nullptr));
     const MergeParams mp = merge_params(a, p.list, p.counts, T, S, nq, a.out_scores + (size_t)q0 * a.k, a.out_ids + (size_t)q0 * a.k);
@@ -2462,9 +2305,6 @@ int bf_launch(const BfLaunch& a) {
       hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)nq), dim3(64), (size_t)mp.cap * 8, stream, mp);
     }
     MRAG_HIP(hipGetLastError());
-#ifdef MRAG_DIAG
-    if (!wide) MRAG_TRY(dump_stamps(p.dbg, stream));
-#endif
   }
   if (!wide) return MRAG_OK;
   // the flagged queries, exactly, eight per streaming launch (their rows staged contiguously)
@@ -2637,38 +2477,18 @@ struct DenseSearch {
 // Path C pays a gather of the m allowed rows (read + write of m x ld x 2 B) and searches m rows; path M searches all n.
 // In the streaming regime (a handful of queries, HBM-bound) a search costs ~ its corpus bytes, so C costs ~ 3m against n;
 // the batch regime is MFMA-bound and C's gather is small next to the search.  Fractions from tools/perf_filter.py
-// (DESIGN.md "Filtered search"); env overrides for experiments: MRAG_FILTER_PATH=mask|compact (AUTO only),
-// MRAG_FILTER_STREAM_FRAC, MRAG_FILTER_BATCH_FRAC, MRAG_FILTER_SCRATCH_MB (cap on path C's compacted corpus).
-struct FilterRule {
-  int force = MRAG_FILTER_AUTO;
-  double stream_frac = 0.25;     // streaming regime: C when m <= stream_frac * n
-  double batch_frac = 0.80;      // batch regime: C when m <= batch_frac * n
-  double scratch_mb = 4096.0;    // C only when the compacted corpus fits this many MiB
-};
-static const FilterRule& filter_rule() {
-  static const FilterRule r = [] {
-    FilterRule f;
-    if (const char* e = getenv("MRAG_FILTER_PATH")) {
-      if (!strcmp(e, "mask")) f.force = MRAG_FILTER_MASK;
-      else if (!strcmp(e, "compact")) f.force = MRAG_FILTER_COMPACT;
-    }
-    if (const char* e = getenv("MRAG_FILTER_STREAM_FRAC")) f.stream_frac = atof(e);
-    if (const char* e = getenv("MRAG_FILTER_BATCH_FRAC")) f.batch_frac = atof(e);
-    if (const char* e = getenv("MRAG_FILTER_SCRATCH_MB")) f.scratch_mb = atof(e);
-    return f;
-  }();
-  return r;
-}
+// (DESIGN.md "Filtered search").
+constexpr double FILTER_STREAM_FRAC = 0.25;     // streaming regime: C when m <= FILTER_STREAM_FRAC * n
+constexpr double FILTER_BATCH_FRAC = 0.80;      // batch regime: C when m <= FILTER_BATCH_FRAC * n
+constexpr double FILTER_SCRATCH_MB = 4096.0;    // C only when the compacted corpus fits this many MiB
 int filter_choose_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
-  const FilterRule& r = filter_rule();
-  if (r.force != MRAG_FILTER_AUTO) return r.force;
-  if ((double)round_up(m, TM) * ld * 2 > r.scratch_mb * 1048576.0) return MRAG_FILTER_MASK;
+  if ((double)round_up(m, TM) * ld * 2 > FILTER_SCRATCH_MB * 1048576.0) return MRAG_FILTER_MASK;
   // the regime bf_launch runs for the unfiltered search over n rows
   const BfRegime regime = bf_regime(nq, k, n, false);
   // k > 64 over fewer than 64 compacted tiles leaves the wide-batch path for the streaming kernel, 8 queries per launch:
   // 1 000 queries x 1M x 768 at k = 200 and 1 % of the rows measured 6.0 ms compacted against 2.4 ms masked
   if (regime == BF_WIDE_BATCH && bf_regime(nq, k, m, false) != BF_WIDE_BATCH) return MRAG_FILTER_MASK;
-  return (double)m <= (regime == BF_STREAM ? r.stream_frac : r.batch_frac) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
+  return (double)m <= (regime == BF_STREAM ? FILTER_STREAM_FRAC : FILTER_BATCH_FRAC) * (double)n ? MRAG_FILTER_COMPACT : MRAG_FILTER_MASK;
 }
 
 // ---- filtered search over prepared operands (mrag_index_search_filtered, and the exact path of mrag_ivf_search_filtered)
@@ -2780,6 +2600,67 @@ int filter_search(FilterWork& w, BfLaunch a, int path, int64_t m, hipStream_t st
                      id_base);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
+}
+
+// the allow-set arguments of a filtered search over n rows: one row each, a known format, a known path (`kind` names the
+// path enum in the message: the dense and the IVF enums both run 0..2 with AUTO = 0)
+int check_allow_args(int64_t allow_rows, int64_t n, int allow_format, int path, const char* kind) {
+  static_assert((int)MRAG_IVF_FILTER_AUTO == (int)MRAG_FILTER_AUTO && (int)MRAG_IVF_FILTER_PROBE == (int)MRAG_FILTER_MASK &&
+                (int)MRAG_IVF_FILTER_EXACT == (int)MRAG_FILTER_COMPACT, "one range check serves both path enums");
+  if (allow_rows != n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)n);
+  if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
+  if (path != MRAG_FILTER_AUTO && path != MRAG_FILTER_MASK && path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown %s path %d", kind, path);
+  return MRAG_OK;
+}
+
+// mrag_index_search_filtered (floor NULL) and mrag_index_search_range (floor = &min_score).  The filtered search needs an
+// allow-set over a non-empty index; the range search takes NULL for "every row" and then runs the plain search, and
+// records its filter path only when it had an allow-set.
+static int search_allowed(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int k, const float* floor, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
+                          int path, float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_nq_k(nq, k));
+  if (floor && !std::isfinite(*floor)) return fail(MRAG_ERR_INVALID, "min_score must be finite, got %g", (double)*floor);
+  const bool filtered = allow || !floor;
+  if (filtered) MRAG_TRY(check_allow_args(allow_rows, ix->n, allow_format, path, "filter"));
+  if (nq == 0) return MRAG_OK;
+  if (floor && !out_counts) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_, out_counts};
+  MRAG_TRY(s.begin(queries, q_dtype, !allow && !floor && ix->n > 0, filtered ? &ix->last_fpath : nullptr));
+  const int64_t n = ix->n;
+  int64_t m = n;                      // rows searched (allow-set: allowed rows when known on the host, else -1)
+  int chosen = -1;
+  if (filtered) {
+    // the whole-search figure (ev[0] .. ev[3]) covers the device work: with a host allow-set it starts after the
+    // host-side packing and count, at the bitset's upload
+    MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_FILTER_MASK, &m, ix->ev[0], s.stream));
+    chosen = path != MRAG_FILTER_AUTO ? path : filter_choose_path(nq, k, n, m, ix->ld);
+  } else {
+    MRAG_HIP(hipEventRecord(ix->ev[0], s.stream));
+  }
+  if (n == 0 || m == 0) {
+    MRAG_TRY(s.fill_empty());         // nothing to search: every slot (-inf, -1), every count 0
+  } else {
+    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
+    BfLaunch a;
+    MRAG_TRY(s.exact_launch(&a));
+    if (floor) {
+      a.range = true;
+      a.floor = *floor;
+      a.out_counts = s.d_cnt;
+      a.rslots = &ix->rslots;
+    }
+    if (filtered) MRAG_TRY(filter_search(ix->fw, a, chosen, m, s.stream));
+    else MRAG_TRY(bf_launch(a));
+  }
+  MRAG_TRY(s.end());
+  if (filtered) {
+    ix->last_fpath = chosen;
+    ix->last_fallowed = m;
+  }
+  return s.copy_back();
 }
 
 }  // namespace mrag
@@ -2940,80 +2821,16 @@ int mrag_index_search_filtered(mrag_handle h, const void* queries, int64_t nq, i
                                int queries_is_device, int k, const void* allow, int64_t allow_rows, int allow_format,
                                int allow_is_device, int path, float* out_scores, int64_t* out_ids, int out_is_device,
                                void* stream_) {
-  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
-  if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(check_nq_k(nq, k));
-  if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
-  if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
-  if (path != MRAG_FILTER_AUTO && path != MRAG_FILTER_MASK && path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown filter path %d", path);
-  if (nq == 0) return MRAG_OK;
-  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_};
-  MRAG_TRY(s.begin(queries, q_dtype, !allow && ix->n > 0, &ix->last_fpath));
-  const int64_t n = ix->n;
-  int64_t m = -1;                     // allowed rows, when known on the host
-  // the whole-search figure (ev[0] .. ev[3]) covers the device work: with a host allow-set it starts after the
-  // host-side packing and count, at the bitset's upload
-  MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_FILTER_MASK, &m, ix->ev[0], s.stream));
-  const int chosen = path != MRAG_FILTER_AUTO ? path : filter_choose_path(nq, k, n, m, ix->ld);
-  if (m == 0) {
-    MRAG_TRY(s.fill_empty());         // nothing allowed: no search kernel
-  } else {
-    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
-    BfLaunch a;
-    MRAG_TRY(s.exact_launch(&a));
-    MRAG_TRY(filter_search(ix->fw, a, chosen, m, s.stream));
-  }
-  MRAG_TRY(s.end());
-  ix->last_fpath = chosen;
-  ix->last_fallowed = m;
-  return s.copy_back();
+  return search_allowed(h, queries, nq, q_dtype, normalize, queries_is_device, k, nullptr, allow, allow_rows, allow_format,
+                        allow_is_device, path, out_scores, out_ids, nullptr, out_is_device, stream_);
 }
 
 int mrag_index_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
                             int k, float min_score, const void* allow, int64_t allow_rows, int allow_format, int allow_is_device,
                             int filter_path, float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device,
                             void* stream_) {
-  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
-  if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(check_nq_k(nq, k));
-  if (!std::isfinite(min_score)) return fail(MRAG_ERR_INVALID, "min_score must be finite, got %g", (double)min_score);
-  if (allow) {
-    if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
-    if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
-    if (filter_path != MRAG_FILTER_AUTO && filter_path != MRAG_FILTER_MASK && filter_path != MRAG_FILTER_COMPACT) return fail(MRAG_ERR_INVALID, "unknown filter path %d", filter_path);
-  }
-  if (nq == 0) return MRAG_OK;
-  if (!out_counts) return fail(MRAG_ERR_INVALID, "NULL buffer");
-  DenseSearch s{ix, nq, k, out_scores, out_ids, out_is_device, (hipStream_t)stream_, out_counts};
-  MRAG_TRY(s.begin(queries, q_dtype, false, allow ? &ix->last_fpath : nullptr));
-  const int64_t n = ix->n;
-  int64_t m = n;                      // rows searched (allow-set: allowed rows when known on the host, else -1)
-  int chosen = -1;
-  if (allow) {
-    MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, filter_path != MRAG_FILTER_MASK, &m, ix->ev[0], s.stream));
-    chosen = filter_path != MRAG_FILTER_AUTO ? filter_path : filter_choose_path(nq, k, n, m, ix->ld);
-  } else {
-    MRAG_HIP(hipEventRecord(ix->ev[0], s.stream));
-  }
-  if (n == 0 || m == 0) {
-    MRAG_TRY(s.fill_empty());         // nothing to search: every slot (-inf, -1), every count 0
-  } else {
-    MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
-    BfLaunch a;
-    MRAG_TRY(s.exact_launch(&a));
-    a.range = true;
-    a.floor = min_score;
-    a.out_counts = s.d_cnt;
-    a.rslots = &ix->rslots;
-    if (allow) MRAG_TRY(filter_search(ix->fw, a, chosen, m, s.stream));
-    else MRAG_TRY(bf_launch(a));
-  }
-  MRAG_TRY(s.end());
-  if (allow) {
-    ix->last_fpath = chosen;
-    ix->last_fallowed = m;
-  }
-  return s.copy_back();
+  return search_allowed(h, queries, nq, q_dtype, normalize, queries_is_device, k, &min_score, allow, allow_rows, allow_format,
+                        allow_is_device, filter_path, out_scores, out_ids, out_counts, out_is_device, stream_);
 }
 
 int mrag_index_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed) {

@@ -113,6 +113,9 @@ struct FilterWork {
   bool counted = false;               // fwork holds the counts of the current allow-set
   void release();
 };
+// the allow-set arguments of a filtered search over n rows: allow_rows == n, a known format, a known path of the
+// MRAG_FILTER_* / MRAG_IVF_FILTER_* enum (`kind` names it in the message: "filter" / "IVF filter")
+int check_allow_args(int64_t allow_rows, int64_t n, int allow_format, int path, const char* kind);
 // allow-set (host or device, MRAG_ALLOW_BITS32 / _BYTES) over n rows -> w.fbits.  *m_out = allowed rows when known on
 // the host (host allow-set; device allow-set with want_count: one read-back), else -1 (the count is in fwork word 0).
 // ev_begin is recorded where the device work of the search starts.
@@ -136,16 +139,13 @@ int launch_fill_empty(float* sc, int64_t* ids, int64_t n, hipStream_t stream);
 //   [5],[6] float offset of the workgroup's score block S[slot][pitch] (low, high)        [7] pitch (floats, % 32 == 0)
 constexpr int IVFS_DESC_WORDS = 8;
 constexpr int IVFS_QUERIES = 128;       // queries per scan workgroup
-#ifndef MRAG_IVFS_CHUNK_ROWS
-#define MRAG_IVFS_CHUNK_ROWS 128
-#endif
-constexpr int IVFS_CHUNK_ROWS = MRAG_IVFS_CHUNK_ROWS;   // rows of a list one scan descriptor covers = one tile of the scan kernel (longer lists are cut: no single-workgroup tails)
+constexpr int IVFS_CHUNK_ROWS = 128;    // rows of a list one scan descriptor covers = one tile of the scan kernel (longer lists are cut: no single-workgroup tails)
 constexpr int IVFS_PITCH_ALIGN = 32;    // floats: every query's score segment starts on a 128-byte line
 static inline int64_t ivfs_pitch(int64_t rows) { return (rows + IVFS_PITCH_ALIGN - 1) / IVFS_PITCH_ALIGN * IVFS_PITCH_ALIGN; }
 constexpr int IVFS_DENSE_ROWS = 128;    // corpus rows per descriptor of the dense (probe selection) case: one tile, so that the persistent grid balances
 // (n_desc_dev != nullptr: the descriptor count lives on the device and n_desc is its host-side upper bound = the grid)
 int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype, int64_t zero_row, const int* desc, int n_desc,
-              const int* n_desc_dev, const int64_t* gq, float* S, hipStream_t stream, long long* dbg = nullptr);
+              const int* n_desc_dev, const int64_t* gq, float* S, hipStream_t stream);
 // pinfo: int4 per (query, probe) = (float offset of the pair's score segment: low, high; its rows; its first stored row)
 // stored_bits != nullptr: filtered selection, a stored position whose bit is clear is never selected
 int ivfs_select_lists(const float* S, const void* pinfo, int nprobe, int64_t nq, int k, const int64_t* row_ids,

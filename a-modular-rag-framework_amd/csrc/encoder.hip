@@ -367,14 +367,6 @@ __global__ __launch_bounds__(256) void enc_gemm_skinny_kernel(const uint16_t* __
 // The WEIGHT rows are the MFMA A operand and the token rows the B operand, so a lane's four accumulator
 // values are four consecutive OUTPUT columns of one token: bias / GELU / residual apply to 8-byte
 // groups and the stores are 8 bytes per lane (the 128 x 128 kernel above stores 2 bytes at a time).
-// Timing-only ablations of the 256 x 256 GEMM (make ENCDIAG=<flags>; results are wrong by design):
-//   1 no epilogue at all | 2 epilogue without the global stores | 4 no GELU | 8 no residual / bias loads
-//   16 only odd workgroups store | 32 only pass 0 stores (is the store phase bound per CU or chip-wide?)
-#ifdef MRAG_ENC_DIAG
-#define ENC_DBG(bit) ((MRAG_ENC_DIAG) & (bit))
-#else
-#define ENC_DBG(bit) 0
-#endif
 constexpr int G2_T = 256, G2_THR = 512;
 constexpr int G2_A_BYTES = G2_T * GK * 2;            // 32 KiB: weight rows of a stage
 constexpr int G2_STAGE = 2 * G2_A_BYTES;             // 64 KiB
@@ -382,19 +374,12 @@ constexpr int G2_PAD = 4096;                          // between the two stage b
 constexpr int G2_BUF1 = G2_STAGE + G2_PAD;            // epilogue's 128 x 528-byte output slab
 constexpr int G2_VEC = 2048;                          // behind the stage buffers: bias / gamma of the tile's 256 columns (LNR epilogue)
 constexpr int G2_CPITCH = 528;                        // output row pitch in LDS: 256 columns x 2 B + 16 (bank shift per row)
-// Wave roles (MRAG_ENC_ROLES=1): waves 0-3 (one per SIMD) issue every LDS-DMA of the K loop, waves 4-7 every global store of
-// the epilogue.  vmcnt counts a wave's loads and stores in issue order, so a wave that does both sits out its output stores
-// (128 KiB per CU, all CUs at once: the HBM write rate) at the next stage wait; with the roles split the loading waves never
-// have a store outstanding and the storing waves never wait on vmcnt inside the K loop.
-#ifndef MRAG_ENC_ROLES
-#define MRAG_ENC_ROLES 1
-#endif
-constexpr bool G2_ROLES = MRAG_ENC_ROLES != 0;
-#ifndef MRAG_ENC_STORE_POLICY
-#define MRAG_ENC_STORE_POLICY "nt"                    // cache policy bits of the output stores (experiment: "sc1", "sc0 sc1", "")
-#endif
-constexpr int G2_CPW = G2_ROLES ? 8 : 4;              // 1-KiB chunks of each operand stage a loading wave fills
-constexpr int G2_PS = G2_ROLES ? 2048 : 0;            // roles: the loading waves' LayerNorm partial sums pass through LDS to the storing waves
+// Wave roles: waves 0-3 (one per SIMD) issue every LDS-DMA of the K loop, waves 4-7 every global store of the epilogue.
+// vmcnt counts a wave's loads and stores in issue order, so a wave that does both sits out its output stores (128 KiB per
+// CU, all CUs at once: the HBM write rate) at the next stage wait; with the roles split the loading waves never have a
+// store outstanding and the storing waves never wait on vmcnt inside the K loop.
+constexpr int G2_CPW = 8;                             // 1-KiB chunks of each operand stage a loading wave fills
+constexpr int G2_PS = 2048;                           // the loading waves' LayerNorm partial sums pass through LDS to the storing waves
 constexpr int G2_LDS = 2 * G2_STAGE + G2_PAD + G2_VEC + G2_PS;   // 134 KiB
 
 // LayerNorm folded into the GEMMs around it (LNF flags; forward_impl, "fused LayerNorm" flow):
@@ -416,23 +401,11 @@ template <int DT, int EPI, int LNF>
 __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
                                                                 const float* __restrict__ bias, const uint16_t* __restrict__ R,
                                                                 uint16_t* __restrict__ C, int N, int K, int tiles_m, int tiles_n,
-                                                                int stagger, LnArgs ln) {
+                                                                LnArgs ln) {
   typedef typename EMfma<DT>::frag frag;
   typedef typename EMfma<DT>::elem elem;
   typedef elem e4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) char sm2[];
-  // Experiment knob (MRAG_ENC_STAGGER, 0 in production): every workgroup walks tiles of the same length, so all 256
-  // reach their epilogue together; starting the XCDs `stagger` cycles apart was tried to spread the store bursts
-  // and did not help (see run_gemm).
-  if (stagger != 0) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    // > 0: XCDs apart; < 0: the workgroups of one XCD apart (blockIdx >> 3 = position inside the XCD)
-    // <= -1000000: two phase groups per XCD (positions 0-15 / 16-31), the second -(stagger + 1000000) cycles behind
-    const unsigned long long wait = stagger > 0 ? (unsigned long long)(blockIdx.x & 7) * (unsigned long long)stagger
-                                    : stagger <= -1000000 ? ((blockIdx.x >> 3) >= 16 ? (unsigned long long)(-stagger - 1000000) : 0ull)
-                                                : (unsigned long long)(blockIdx.x >> 3) * (unsigned long long)(-stagger);
-    while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 2, wn = w & 3;     // wave tile: 128 weight rows (output columns) x 64 tokens
@@ -446,9 +419,9 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
   const uint32_t voff_e = (uint32_t)(lane >> 3) * row_b + (uint32_t)(((lane & 7) ^ (lane >> 4)) * 16);
   const uint32_t voff_o = (uint32_t)(lane >> 3) * row_b + (uint32_t)(((lane & 7) ^ (4 + (lane >> 4))) * 16);
   const uint32_t chunk_b = 8u * row_b;
-  const bool loader = !G2_ROLES || w < 4;                // (wave-uniform)
-  const bool storer = !G2_ROLES || w >= 4;
-  const size_t wave_off = (size_t)(G2_CPW * (w & (G2_ROLES ? 3 : 7))) * chunk_b;     // wave w fills 1-KiB chunks 4w..4w+3 of each operand (roles: 8w..8w+7)
+  const bool loader = w < 4;                             // (wave-uniform)
+  const bool storer = w >= 4;
+  const size_t wave_off = (size_t)(G2_CPW * (w & 3)) * chunk_b;     // loading wave w fills 1-KiB chunks 8w..8w+7 of each operand
   auto tile_ptrs = [&](int lin, const char*& a, const char*& b) {
     const int tm = lin / tiles_n, tn = lin - tm * tiles_n;
     a = (const char*)(W + (size_t)tn * G2_T * K) + wave_off;
@@ -461,7 +434,7 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
       const char* base = op ? b : a;
 #pragma unroll
       for (int i = 0; i < G2_CPW; i += 2) {
-        const uint32_t la = (uint32_t)(buf * G2_BUF1 + op * G2_A_BYTES + (G2_CPW * (w & (G2_ROLES ? 3 : 7)) + i) * 1024);
+        const uint32_t la = (uint32_t)(buf * G2_BUF1 + op * G2_A_BYTES + (G2_CPW * (w & 3) + i) * 1024);
         const char* c0 = base + (size_t)i * chunk_b;
         const char* c1 = c0 + chunk_b;
         uint32_t keep;
@@ -536,15 +509,10 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
   auto kstep_sync = [&]() {
-    if (G2_ROLES) {
-      if (loader) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the storing waves' output stores stay in flight
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    if (loader) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the storing waves' output stores stay in flight
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
   };
 
   for (int lin = first; lin < n_tiles; lin += nwg) {
@@ -570,16 +538,6 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
     const int n_l = wm * 128 + (lane >> 4) * 4;             // + mf*16: column inside the tile
     const int n_b = tn * G2_T + n_l;
     const int t_b = tm * G2_T + wn * 64 + (lane & 15);
-    if (ENC_DBG(1)) {   // ablation: keep the accumulators observable, skip the epilogue
-      float xs = 0.f;
-#pragma unroll
-      for (int mf = 0; mf < 8; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < 4; ++nf) xs += acc[mf][nf][0] + acc[mf][nf][1] + acc[mf][nf][2] + acc[mf][nf][3];
-      if (xs == 123456.789f) C[0] = 1;
-      __builtin_amdgcn_s_barrier();
-      continue;
-    }
     // Every global load of the epilogue is issued HERE, back to back, and waited for once: written inside the
     // passes, hipcc puts an s_waitcnt vmcnt(0) behind each of them (8 bias + 32 residual loads = up to 40 serial
     // L2 round trips per tile), and in pass 1 that wait also sits out pass 0's stores (vmcnt counts in order).
@@ -611,13 +569,13 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
       const int n0 = n_b + mf * 16;
       if (!VEC_LDS) {
         bv[mf] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n0 < N && !ENC_DBG(8)) bv[mf] = *(const float4*)(bias + n0);
+        if (n0 < N) bv[mf] = *(const float4*)(bias + n0);
       }
       if ((LNF & 3) && !VEC_LDS) {
         xv[mf] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (n0 < N) xv[mf] = *(const float4*)(ln.s_vec + n0);
       }
-      if (EPI == EPI_RESID && !ENC_DBG(8)) {
+      if (EPI == EPI_RESID) {
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf) {
           rr[mf][nf] = (e4){(elem)0.f, (elem)0.f, (elem)0.f, (elem)0.f};
@@ -646,11 +604,11 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = acc[mf][nf][r] + bq[r];
           }
-          if (EPI == EPI_GELU && !ENC_DBG(4)) {
+          if (EPI == EPI_GELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
           }
-          if (EPI == EPI_RESID && !ENC_DBG(8)) {
+          if (EPI == EPI_RESID) {
             if (LNF & 2) {
               const float4 g4 = *(const float4*)(vec + 256 + n_l + mf * 16);
               const float xq[4] = {g4.x, g4.y, g4.z, g4.w};
@@ -677,52 +635,33 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if constexpr (G2_ROLES) {
-        // roles: the 256 threads of waves 4-7 store the slab, 16 pieces each.  Thread -> (row r0 + 8 i, piece): the piece and r0
-        // are fixed per thread, so every store is lane offset + a wave-uniform base (no per-store address registers: the
-        // hoisted 64-bit addresses of the plain loop spill).  The stores are asm so that hipcc neither counts them nor waits.
-        if (storer) {
-          const int r0 = (tid - 256) >> 5, piece = tid & 31;
-          const int n0 = tn * G2_T + piece * 8;
-          const uint32_t lane_off = ((uint32_t)r0 * (uint32_t)N + (uint32_t)(piece * 8)) * 2u;
-          const char* srow = slab + r0 * G2_CPITCH + piece * 16;
-          if (n0 < N) {
+      // roles: the 256 threads of waves 4-7 store the slab, 16 pieces each.  Thread -> (row r0 + 8 i, piece): the piece and r0
+      // are fixed per thread, so every store is lane offset + a wave-uniform base (no per-store address registers: the
+      // hoisted 64-bit addresses of a plain store loop spill).  The stores are asm so that hipcc neither counts them nor waits.
+      if (storer) {
+        const int r0 = (tid - 256) >> 5, piece = tid & 31;
+        const int n0 = tn * G2_T + piece * 8;
+        const uint32_t lane_off = ((uint32_t)r0 * (uint32_t)N + (uint32_t)(piece * 8)) * 2u;
+        const char* srow = slab + r0 * G2_CPITCH + piece * 16;
+        if (n0 < N) {
 #pragma unroll
-            for (int g = 0; g < 16; g += 4) {          // four slab reads in flight, then their four stores
-              typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-              u32x4 vv[4];
+          for (int g = 0; g < 16; g += 4) {          // four slab reads in flight, then their four stores
+            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            u32x4 vv[4];
 #pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const uint4 val = *(const uint4*)(srow + (g + j) * 8 * G2_CPITCH);
-                vv[j] = (u32x4){val.x, val.y, val.z, val.w};
-              }
+            for (int j = 0; j < 4; ++j) {
+              const uint4 val = *(const uint4*)(srow + (g + j) * 8 * G2_CPITCH);
+              vv[j] = (u32x4){val.x, val.y, val.z, val.w};
+            }
 #pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const int i = g + j;
-                const int tok0 = tm * G2_T + (i >> 2) * 64 + pass * 32 + 8 * (i & 3);      // + r0: in lane_off
-                const char* base = (const char*)(C + (size_t)tok0 * N + (size_t)tn * G2_T);
-                if (!ENC_DBG(2))
-                  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 " MRAG_ENC_STORE_POLICY "\n\ts_nop 1" ::"v"(lane_off), "v"(vv[j]), "s"(base) : "memory");
-                else if (vv[j][0] == 0x12345678u && vv[j][1] == 0x9abcdef0u) C[0] = 1;
-              }
+            for (int j = 0; j < 4; ++j) {
+              const int i = g + j;
+              const int tok0 = tm * G2_T + (i >> 2) * 64 + pass * 32 + 8 * (i & 3);      // + r0: in lane_off
+              const char* base = (const char*)(C + (size_t)tok0 * N + (size_t)tn * G2_T);
+              // non-temporal: the output is streamed once, it must not evict the operand panels from L2
+              asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(lane_off), "v"(vv[j]), "s"(base) : "memory");
             }
           }
-        }
-      } else
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int c = tid + G2_THR * i;                      // 128 rows x 32 sixteen-byte pieces
-        const int row = c >> 5, piece = c & 31;
-        const int n0 = tn * G2_T + piece * 8;
-        if (n0 < N) {
-          const int token = tm * G2_T + (row >> 5) * 64 + pass * 32 + (row & 31);
-          const uint4 val = *(const uint4*)(slab + row * G2_CPITCH + piece * 16);
-          typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-          const u32x4 vv = {val.x, val.y, val.z, val.w};
-          if (ENC_DBG(64)) *(uint4*)(C + (size_t)token * N + n0) = val;                      // diag 64: plain (L2-allocating) stores
-          else if (!ENC_DBG(2) && !(ENC_DBG(16) && !(blockIdx.x & 1)) && !(ENC_DBG(32) && pass == 1))
-            __builtin_nontemporal_store(vv, (u32x4*)(C + (size_t)token * N + n0));           // streamed once: do not evict the operand panels from L2
-          else if (val.x == 0x12345678u && val.y == 0x9abcdef0u) C[0] = 1;
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // slab reads done (pass 1 rewrites it; after pass 1 the next stage lands in it)
@@ -737,29 +676,23 @@ __global__ __launch_bounds__(G2_THR, 2) void enc_gemm256_kernel(const uint16_t* 
         ps1[nf] += __shfl_xor(ps1[nf], 16); ps1[nf] += __shfl_xor(ps1[nf], 32);
         ps2[nf] += __shfl_xor(ps2[nf], 16); ps2[nf] += __shfl_xor(ps2[nf], 32);
       }
-      if (G2_ROLES) {
-        // waves w and w + 4 hold the two column halves (wm = 0 / 1) of the same 64 tokens: the loading wave hands its sums
-        // over through LDS and the storing wave writes both slots (the loading waves issue no global store at all)
-        float2* psl = (float2*)(sm2 + 2 * G2_STAGE + G2_PAD + G2_VEC);
-        if (!storer && lane < 16) {
+      // waves w and w + 4 hold the two column halves (wm = 0 / 1) of the same 64 tokens: the loading wave hands its sums
+      // over through LDS and the storing wave writes both slots (the loading waves issue no global store at all)
+      float2* psl = (float2*)(sm2 + 2 * G2_STAGE + G2_PAD + G2_VEC);
+      if (!storer && lane < 16) {
 #pragma unroll
-          for (int nf = 0; nf < 4; ++nf) psl[wn * 64 + nf * 16 + lane] = make_float2(ps1[nf], ps2[nf]);
+        for (int nf = 0; nf < 4; ++nf) psl[wn * 64 + nf * 16 + lane] = make_float2(ps1[nf], ps2[nf]);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (storer && lane < 16) {
+#pragma unroll
+        for (int nf = 0; nf < 4; ++nf) {
+          float2* dst = (float2*)ln.partials + (size_t)(t_b + nf * 16) * ln.np + 2 * tn;
+          dst[0] = psl[wn * 64 + nf * 16 + lane];
+          dst[1] = make_float2(ps1[nf], ps2[nf]);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (storer && lane < 16) {
-#pragma unroll
-          for (int nf = 0; nf < 4; ++nf) {
-            float2* dst = (float2*)ln.partials + (size_t)(t_b + nf * 16) * ln.np + 2 * tn;
-            dst[0] = psl[wn * 64 + nf * 16 + lane];
-            dst[1] = make_float2(ps1[nf], ps2[nf]);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int nf = 0; nf < 4; ++nf)
-          if (lane < 16) ((float2*)ln.partials)[(size_t)(t_b + nf * 16) * ln.np + 2 * tn + wm] = make_float2(ps1[nf], ps2[nf]);
       }
     }
   }
@@ -1231,14 +1164,11 @@ static int upload_f32(const float* src, int is_device, int64_t n, float* dst, hi
   return MRAG_OK;
 }
 
-// development switch (MRAG_ENC_GEMM128=1): force the 128 x 128 kernel, for A/B timing
-static const int g_stagger_override = [] { const char* e = getenv("MRAG_ENC_STAGGER"); return e ? atoi(e) : 0; }();   // experiment knob
 static int device_cus() {   // CU count of the current device, read once
   static int n = 0;
   if (!n) { hipDeviceProp_t pr; int dev = 0; n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
   return n;
 }
-static const bool g_force_gemm128 = [] { const char* e = getenv("MRAG_ENC_GEMM128"); return e && atoi(e) != 0; }();
 
 template <int DT, int NFR>
 static void launch_skinny(const uint16_t* A, const Linear& l, const uint16_t* R, uint16_t* C, int epi, hipStream_t stream) {
@@ -1250,8 +1180,7 @@ static void launch_skinny(const uint16_t* A, const Linear& l, const uint16_t* R,
 
 template <int DT>
 static int run_gemm(const uint16_t* A, const Linear& l, const uint16_t* R, uint16_t* C, int M, int M_pad, int epi, hipStream_t stream) {
-  static const bool skinny_off = [] { const char* e = getenv("MRAG_ENC_NO_SKINNY"); return e && atoi(e) != 0; }();   // development switch (A/B)
-  if (M <= 64 && l.K % 384 == 0 && l.N % 4 == 0 && !skinny_off) {
+  if (M <= 64 && l.K % 384 == 0 && l.N % 4 == 0) {
     if (M <= 16) launch_skinny<DT, 1>(A, l, R, C, epi, stream);
     else if (M <= 32) launch_skinny<DT, 2>(A, l, R, C, epi, stream);
     else launch_skinny<DT, 4>(A, l, R, C, epi, stream);
@@ -1262,8 +1191,8 @@ static int run_gemm(const uint16_t* A, const Linear& l, const uint16_t* R, uint1
   // time) leaves most CUs idle with 9-72 such tiles, the 128 x 128 kernel gives it four times the workgroups
   const int n_cus = device_cus();
   const bool fills = (int64_t)(M_pad / G2_T) * (l.N_pad / G2_T) >= n_cus / 2;
-  if (M_pad % G2_T == 0 && l.N_pad % G2_T == 0 && fills && !g_force_gemm128) {
-    typedef void (*Fn)(const uint16_t*, const uint16_t*, const float*, const uint16_t*, uint16_t*, int, int, int, int, int, LnArgs);
+  if (M_pad % G2_T == 0 && l.N_pad % G2_T == 0 && fills) {
+    typedef void (*Fn)(const uint16_t*, const uint16_t*, const float*, const uint16_t*, uint16_t*, int, int, int, int, LnArgs);
     const Fn fn = epi == EPI_BIAS ? (Fn)enc_gemm256_kernel<DT, EPI_BIAS, 0> : epi == EPI_GELU ? (Fn)enc_gemm256_kernel<DT, EPI_GELU, 0>
                                                                                              : (Fn)enc_gemm256_kernel<DT, EPI_RESID, 0>;
     static std::map<const void*, bool> attr_done;
@@ -1274,14 +1203,9 @@ static int run_gemm(const uint16_t* A, const Linear& l, const uint16_t* R, uint1
     const int tm2 = M_pad / G2_T, tn2 = l.N_pad / G2_T;
     const int cus = device_cus();
     const int nwg = std::min(tm2 * tn2, cus);
-    const int per_wg = (tm2 * tn2 + nwg - 1) / nwg;
-    // (experiment knob, off by default: starting the XCDs an eighth of a tile apart did NOT shorten the store phase --
-    // 960 -> 970 -> 984 us for the QKV GEMM at 0 / 4500 / 12000 cycles per XCD; what did was streaming the output
-    // with non-temporal stores so that it stops evicting the operand panels from L2, see the epilogue)
-    int stagger = 0;
-    (void)per_wg;
-    if (g_stagger_override != 0) stagger = (nwg % 8 == 0) ? g_stagger_override : 0;
-    hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(G2_THR), G2_LDS, stream, A, l.w, l.b, R, C, l.N, l.K, tm2, tn2, stagger, LnArgs{});
+    // (starting the XCDs an eighth of a tile apart did not shorten the store phase -- 960 -> 970 -> 984 us for the QKV GEMM
+    // at 0 / 4500 / 12000 cycles per XCD; non-temporal stores did, see the epilogue)
+    hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(G2_THR), G2_LDS, stream, A, l.w, l.b, R, C, l.N, l.K, tm2, tn2, LnArgs{});
     MRAG_HIP(hipGetLastError());
     return MRAG_OK;
   }
@@ -1304,8 +1228,7 @@ static int run_gemm_ln(const uint16_t* A, const uint16_t* W, const float* bias, 
   const int tm2 = M_pad / G2_T, tn2 = N_pad / G2_T;
   const int cus = device_cus();   // (cached: this launcher runs ~48 times per bge-base forward)
   const int nwg = std::min(tm2 * tn2, cus);
-  const int stagger = (g_stagger_override != 0 && nwg % 8 == 0) ? g_stagger_override : 0;   // experiment knob, 0 in production
-  hipLaunchKernelGGL((enc_gemm256_kernel<DT, EPI, LNF>), dim3((unsigned)nwg), dim3(G2_THR), G2_LDS, stream, A, W, bias, R, C, N, K, tm2, tn2, stagger, ln);
+  hipLaunchKernelGGL((enc_gemm256_kernel<DT, EPI, LNF>), dim3((unsigned)nwg), dim3(G2_THR), G2_LDS, stream, A, W, bias, R, C, N, K, tm2, tn2, ln);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;
 }
@@ -1380,7 +1303,7 @@ static int forward_impl(Encoder* e, int B, int S, float* d_out, int pool, int no
   // (read per forward, not once per process: the A/B test flips it between two calls)
   const bool fused_off = [] { const char* v = getenv("MRAG_ENC_NO_FUSED_LN"); return v && atoi(v) != 0; }();
   const int n_cus_f = device_cus();
-  const bool fused = !fused_off && !g_force_gemm128 && M_pad % G2_T == 0 && H % 16 == 0 && round_up(H, G2_T) / G2_T * (M_pad / G2_T) >= n_cus_f / 2;
+  const bool fused = !fused_off && M_pad % G2_T == 0 && H % 16 == 0 && round_up(H, G2_T) / G2_T * (M_pad / G2_T) >= n_cus_f / 2;
   uint16_t *y1 = y, *y2 = nullptr;
   float2 *st1 = nullptr, *st2 = nullptr;
   float* partials = nullptr;
@@ -1409,8 +1332,7 @@ static int forward_impl(Encoder* e, int B, int S, float* d_out, int pool, int no
     MRAG_TRY(run_gemm<DT>(x, L.qkv, nullptr, qkv, (int)M, M_pad, EPI_BIAS, stream));
     const int32_t* am = (const int32_t*)e->mask.p;
     if (dh != 32 && dh != 64) return fail(MRAG_ERR_UNSUPPORTED, "head dim %d not supported (32 or 64)", dh);
-    static const bool s128_off = [] { const char* e = getenv("MRAG_ENC_ATTN_GENERIC"); return e && atoi(e) != 0; }();   // development switch: A/B against the generic kernel
-    if (S <= 256 && !s128_off) {
+    if (S <= 256) {
       // whole-sequence kernel: K / V of a head staged once, keys padded to 64 / 128 / 256
       const dim3 g128((unsigned)(B * c.heads));
 #define MRAG_ATTN(DHV, SPV, NWV) hipLaunchKernelGGL((enc_attention_s128_kernel<DT, DHV, SPV, NWV>), g128, dim3(64 * NWV), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale)

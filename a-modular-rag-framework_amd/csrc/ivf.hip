@@ -748,23 +748,11 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     MRAG_HIP(hipGetLastError());
     // 3) scores of every (query, probed list) pair, then the k best per query
     MRAG_HIP(hipEventRecord(ev_scan0, stream));
-    static const char* stamp_path = getenv("MRAG_IVFS_STAMPS");   // diagnostic builds (MRAG_IVFS_DIAG & 128): per-workgroup clock stamps -> file
-    long long* dbg = nullptr;
-    if (stamp_path) { MRAG_TRY(ix->qg.ensure((size_t)desc_bound * 64)); MRAG_HIP(hipMemsetAsync(ix->qg.p, 0, (size_t)desc_bound * 64, stream)); dbg = (long long*)ix->qg.p; }
-    if (no_sync) {
-      MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p, (int)desc_bound, d_nwg,
-                         (const int64_t*)ix->gq.p, (float*)ix->scores.p, stream, dbg));
-      if (stamp_path) {
-        std::vector<long long> h((size_t)desc_bound * 8);
-        MRAG_HIP(hipStreamSynchronize(stream));
-        MRAG_HIP(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(stamp_path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-      }
-    } else {
-      n_wg = plan_out[0];
-      MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p, n_wg, nullptr,
-                         (const int64_t*)ix->gq.p, (float*)ix->scores.p, stream));
-    }
+    // (no_sync: the workgroup count stays on the device, the grid is its bound)
+    if (!no_sync) n_wg = plan_out[0];
+    MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p,
+                       no_sync ? (int)desc_bound : n_wg, no_sync ? d_nwg : nullptr, (const int64_t*)ix->gq.p, (float*)ix->scores.p,
+                       stream));
     MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
                                stored_bits));
     MRAG_HIP(hipEventRecord(ev_scan1, stream));
@@ -892,34 +880,15 @@ namespace mrag {
 // ---- filtered search: AUTO's choice between path P (probe the live lists) and path E (filtered brute force) ------------
 // P scans ~ nprobe * n / nlist rows per query whatever the allow-set; E scans the m allowed rows (the dense filtered search
 // over ix->raw, itself masked or compacted).  E when m <= c * nprobe * n / nlist: c_batch for batches, c_stream for a few
-// queries (the streaming regime, HBM-bound).  Constants from tools/perf_ivf_filter.py (DESIGN.md "Filtered IVF search");
-// env overrides for experiments: MRAG_IVF_FILTER_PATH=probe|exact (AUTO only), MRAG_IVF_FILTER_C, MRAG_IVF_FILTER_C_STREAM.
-struct IvfFilterRule {
-  int force = MRAG_IVF_FILTER_AUTO;
-  double c_batch = 8.0;          // 10 000 queries: E and P cross at 5-10 % of the rows (c ~ 9)
-  double c_stream = 24.0;        // 1 and 16 queries: they cross at ~20-25 % (c ~ 25)
-  int64_t stream_nq = 16;        // batches up to this many queries count as the streaming regime
-};
-static const IvfFilterRule& ivf_filter_rule() {
-  static const IvfFilterRule r = [] {
-    IvfFilterRule f;
-    if (const char* e = getenv("MRAG_IVF_FILTER_PATH")) {
-      if (!strcmp(e, "probe")) f.force = MRAG_IVF_FILTER_PROBE;
-      else if (!strcmp(e, "exact")) f.force = MRAG_IVF_FILTER_EXACT;
-    }
-    if (const char* e = getenv("MRAG_IVF_FILTER_C")) f.c_batch = atof(e);
-    if (const char* e = getenv("MRAG_IVF_FILTER_C_STREAM")) f.c_stream = atof(e);
-    return f;
-  }();
-  return r;
-}
+// queries (the streaming regime, HBM-bound).  Constants from tools/perf_ivf_filter.py (DESIGN.md "Filtered IVF search").
+constexpr double IVF_FILTER_C_BATCH = 8.0;     // 10 000 queries: E and P cross at 5-10 % of the rows (c ~ 9)
+constexpr double IVF_FILTER_C_STREAM = 24.0;   // 1 and 16 queries: they cross at ~20-25 % (c ~ 25)
+constexpr int64_t IVF_FILTER_STREAM_NQ = 16;   // batches up to this many queries count as the streaming regime
 static int ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t n, int64_t m, int dim) {
   (void)k; (void)dim;            // (both paths pay them alike: the dot products per row, the top-k per query)
   if (nprobe >= nlist) return MRAG_IVF_FILTER_EXACT;
-  const IvfFilterRule& r = ivf_filter_rule();
-  if (r.force != MRAG_IVF_FILTER_AUTO) return r.force;
   const double probed = (double)nprobe * (double)n / (double)nlist;
-  return (double)m <= (nq <= r.stream_nq ? r.c_stream : r.c_batch) * probed ? MRAG_IVF_FILTER_EXACT : MRAG_IVF_FILTER_PROBE;
+  return (double)m <= (nq <= IVF_FILTER_STREAM_NQ ? IVF_FILTER_C_STREAM : IVF_FILTER_C_BATCH) * probed ? MRAG_IVF_FILTER_EXACT : MRAG_IVF_FILTER_PROBE;
 }
 
 // flist layout (ints): counts [nlist] | live-list count (+ 3 pad) | live bits [round256(nlist) / 32] | caller counts [nlist]
@@ -939,9 +908,8 @@ static int ivf_filter_stored(IvfIndex* ix, hipStream_t stream) {
   return MRAG_OK;
 }
 
-static int check_allow_args(IvfIndex* ix, const void* allow, int64_t allow_rows, int allow_format) {
-  if (allow_rows != ix->n) return fail(MRAG_ERR_INVALID, "allow-set covers %lld rows, the index holds %lld", (long long)allow_rows, (long long)ix->n);
-  if (allow_format != MRAG_ALLOW_BITS32 && allow_format != MRAG_ALLOW_BYTES) return fail(MRAG_ERR_INVALID, "unknown allow format %d", allow_format);
+static int check_ivf_allow_args(IvfIndex* ix, const void* allow, int64_t allow_rows, int allow_format, int path) {
+  MRAG_TRY(check_allow_args(allow_rows, ix->n, allow_format, path, "IVF filter"));
   if (!allow && ix->n > 0) return fail(MRAG_ERR_INVALID, "allow is NULL");
   return MRAG_OK;
 }
@@ -962,7 +930,7 @@ int mrag_ivf_allowed_per_list(mrag_handle h, const void* allow, int64_t allow_ro
                               int32_t* out_counts, int out_is_device, void* stream_) {
   IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
   if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(check_allow_args(ix, allow, allow_rows, allow_format));
+  MRAG_TRY(check_ivf_allow_args(ix, allow, allow_rows, allow_format, MRAG_IVF_FILTER_AUTO));
   if (!out_counts) return fail(MRAG_ERR_INVALID, "out_counts is NULL");
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
@@ -987,9 +955,7 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
   IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
   if (!ix) return MRAG_ERR_INVALID;
   MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
-  MRAG_TRY(check_allow_args(ix, allow, allow_rows, allow_format));
-  if (path != MRAG_IVF_FILTER_AUTO && path != MRAG_IVF_FILTER_PROBE && path != MRAG_IVF_FILTER_EXACT)
-    return fail(MRAG_ERR_INVALID, "unknown IVF filter path %d", path);
+  MRAG_TRY(check_ivf_allow_args(ix, allow, allow_rows, allow_format, path));
   hipStream_t stream = (hipStream_t)stream_;
   int64_t chunk = 0;
   MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));

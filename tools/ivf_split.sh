@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-kernel times of one IVF search leg under rocprofv3 --kernel-trace: tools/ivf_split.sh <tag> <script args...>
-# e.g. tools/ivf_split.sh new5m tools/perf_ivf5m.py 5000000 ; MRAG_IVFS_SCAN=128 tools/ivf_split.sh old5m tools/perf_ivf5m.py 5000000
+# e.g. tools/ivf_split.sh new5m tools/perf_ivf5m.py 5000000
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 tag=$1; shift
