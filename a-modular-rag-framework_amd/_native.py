@@ -92,6 +92,8 @@ SIGNATURES = {
     "mrag_ivf_get_assignments": [_h, _vp, _i, _vp],
     "mrag_ivf_search": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
     "mrag_ivf_search_filtered": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i, _vp],
+    "mrag_ivf_search_range": [_h, _vp, _i64, _i, _i, _i, _i, _i, C.c_float, _vp, _i, _vp, _vp, _vp, _i, _vp],
+    "mrag_ivf_self_join": [_h, _i64, _i64, _i, _i, C.c_float, _vp, _vp, _vp, _vp],
     "mrag_ivf_allowed_per_list": [_h, _vp, _i64, _i, _i, _vp, _i, _vp],
     "mrag_ivf_choose_filter_path": [_i64, _i, _i, _i, _i64, _i64, _i, C.POINTER(_i)],
     "mrag_ivf_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i)],

@@ -148,8 +148,16 @@ int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype
               const int* n_desc_dev, const int64_t* gq, float* S, hipStream_t stream);
 // pinfo: int4 per (query, probe) = (float offset of the pair's score segment: low, high; its rows; its first stored row)
 // stored_bits != nullptr: filtered selection, a stored position whose bit is clear is never selected
+// range != nullptr: range selection -- only entries scoring >= floor, the entry at stored position excl_pos[q] (-1 or a
+// NULL array: none) left out, counts[q] = the entries that remain (all device pointers; not combined with stored_bits)
+struct IvfsRange {
+  float floor;
+  const int64_t* excl_pos;
+  int64_t* counts;
+};
 int ivfs_select_lists(const float* S, const void* pinfo, int nprobe, int64_t nq, int k, const int64_t* row_ids,
-                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits = nullptr);
+                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits = nullptr,
+                      const IvfsRange* range = nullptr);
 int ivfs_dense_n_desc(int64_t nq, int n_rows);
 // count_out != nullptr: every selected row r with row_weight[r] > 0 also bumps count_out[r] (the IVF search's
 // "queries per list" histogram, otherwise a kernel of its own)

@@ -55,7 +55,13 @@ struct IvfIndex : Object {
   int last_fpath = -1;            // MRAG_IVF_FILTER_PROBE / _EXACT of the last filtered search, -1 = none
   int64_t last_fallowed = -1;     // its allowed rows (-1: still on the device, flast word 0)
   int last_flive = -1;            // its live lists (-1: on the device, flast word 1; -2: not computed, path E)
+  // range search (mrag_ivf_search_range, mrag_ivf_self_join)
+  DevBuf inv_pos;                 // int64 [n]: original row -> stored position (built on the first exclusion after a regroup)
+  bool inv_valid = false;
+  DevBuf excl;                    // int64 [nq] excluded rows of a host caller | int64 [nq] their stored positions
+  DevBuf out_cnt;                 // int64 [nq] counts of a chunk with host outputs
   ~IvfIndex() override {
+    inv_pos.release(); excl.release(); out_cnt.release();
     fw.release(); fstored.release(); flist.release(); flast.release();
     if (ev_lallow) (void)hipEventDestroy(ev_lallow);
     if (h_lallow) (void)hipHostFree(h_lallow);
@@ -298,6 +304,23 @@ __global__ void ivf_live_bits_kernel(const int* __restrict__ counts, int nlist, 
   if (lane == 32) live[l >> 5] = (uint32_t)(b >> 32);
 }
 
+// ---- range search: the excluded rows as stored positions --------------------------------------------------------
+// inv[row_ids[p]] = p over the stored positions (padding positions hold -1)
+__global__ void ivf_inverse_pos_kernel(const int64_t* __restrict__ row_ids, int64_t n_sorted, int64_t n, int64_t* __restrict__ inv) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_sorted) return;
+  const int64_t r = row_ids[p];
+  if (r >= 0 && r < n) inv[r] = p;
+}
+// query i excludes row rows[i] (rows == nullptr: row0 + i, the self-join) -> its stored position, -1 for none / not a row
+__global__ void ivf_excl_pos_kernel(const int64_t* __restrict__ rows, int64_t row0, int64_t nq, int64_t n,
+                                    const int64_t* __restrict__ inv, int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const int64_t r = rows ? rows[i] : row0 + i;
+  out[i] = (r >= 0 && r < n) ? inv[r] : -1;
+}
+
 __global__ void ids_to_i32_kernel(const int64_t* __restrict__ ids, int64_t n, int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (int32_t)ids[i];
@@ -417,6 +440,7 @@ static int ivf_finalize(IvfIndex* ix, hipStream_t stream) {
   MRAG_HIP(hipStreamSynchronize(stream));
   ix->n_sorted = ns;
   ix->max_list_rows = ix->list_count.empty() ? 0 : *std::max_element(ix->list_count.begin(), ix->list_count.end());
+  ix->inv_valid = false;
   ix->dirty = false;
   return MRAG_OK;
 }
@@ -653,18 +677,46 @@ static int ivf_prep_queries(IvfIndex* ix, const void* queries, int64_t nq, int q
   return ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream);
 }
 
+// What a range search adds to a search: the floor, per query the stored position of its excluded row (device, or NULL) and
+// the counts (in the memory space of the other outputs).  stored_rows: `queries` are rows of ix->raw (storage dtype, ld
+// apart: the self-join), copied as they are.  The range select has no fused form: a chunk that would take the fused regime
+// is refused.
+struct IvfRangeArgs {
+  float floor = 0.f;
+  const int64_t* excl_pos = nullptr;
+  int64_t* out_counts = nullptr;
+  bool stored_rows = false;
+};
+
+static int ivf_range_unsupported(const char* why) {
+  return fail(MRAG_ERR_UNSUPPORTED, "IVF range search runs in the score-segment regime only: %s", why);
+}
+
 // one chunk of a search (<= 2^20 queries whose score segments fit the buffer): probe selection, plan, list scan, selection
 // live_bits / stored_bits (filtered search, path P): probe only live lists, select only allowed stored positions
+// rg (range search): the selection lists and counts the rows >= rg->floor (pointers already moved to this chunk's queries)
 static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
                             int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx,
-                            const uint32_t* live_bits, const uint32_t* stored_bits) {
+                            const uint32_t* live_bits, const uint32_t* stored_bits, const IvfRangeArgs* rg = nullptr) {
   hipEvent_t ev_scan0 = ix->cev[2 * chunk_idx], ev_scan1 = ix->cev[2 * chunk_idx + 1];
   unsigned long long* d_stats = (unsigned long long*)ix->stats.p;
 
   float* d_sc; int64_t* d_id;
   MRAG_TRY(ivf_stage_outputs(ix, nq, k, out_scores, out_ids, out_is_device, &d_sc, &d_id));
+  int64_t* d_cnt = nullptr;
+  if (rg) {
+    d_cnt = rg->out_counts;
+    if (!out_is_device) { MRAG_TRY(ix->out_cnt.ensure((size_t)nq * 8)); d_cnt = (int64_t*)ix->out_cnt.p; }
+  }
   // 1) queries -> storage dtype; probe lists
-  MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
+  if (rg && rg->stored_rows) {
+    const int64_t nq_pad = bf_query_rows(nq);
+    MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
+    MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));
+    MRAG_HIP(hipMemcpyAsync(ix->qbuf.p, queries, (size_t)nq * ix->ld * 2, hipMemcpyDeviceToDevice, stream));
+  } else {
+    MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
+  }
   MRAG_TRY(ix->tmp_id.ensure((size_t)nq * nprobe * 8));
   MRAG_TRY(ix->tmp_sc.ensure((size_t)nq * nprobe * 4));
   // The list scan (and the probe selection before it) runs as "score segments + select" (ivf_scan.hip) whenever the
@@ -715,6 +767,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     hipLaunchKernelGGL(ivf_count_kernel, dim3(pgrid), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs,
                        (const int*)ix->d_list_count.p, d_lcount);
   bool use_scores = scores_cap > 0 && nprobe <= 256;   // (the select kernel holds <= 256 segments per query; exhaustive probing takes the fused path)
+  if (rg && !use_scores) return ivf_range_unsupported(scores_cap > 0 ? "more than 256 probed lists per query" : "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
   // Score floats of this search: known exactly only on the device (sum over the probed lists of queries x rows).  When
   // even the bound "every pair probes the longest list" fits the buffer, nothing comes back to the host at all: the
   // scan is launched over the BOUND of the workgroup count and reads the real one from device memory.
@@ -735,6 +788,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
       MRAG_HIP(hipStreamSynchronize(stream));
       const int64_t floats = (int64_t)(uint32_t)plan_out[1] | ((int64_t)plan_out[2] << 32);
       if (plan_out[0] < 0 || plan_out[0] > desc_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", plan_out[0], (long long)desc_bound);
+      if (floats * 4 > scores_cap && rg) return ivf_range_unsupported("the score segments of one chunk exceed the score buffer (MRAG_IVF_SCORES_MB)");
       if (floats * 4 > scores_cap) use_scores = false;
       else MRAG_TRY(ix->scores.ensure((size_t)std::max<int64_t>(floats, 4) * 4));
     }
@@ -753,8 +807,10 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p,
                        no_sync ? (int)desc_bound : n_wg, no_sync ? d_nwg : nullptr, (const int64_t*)ix->gq.p, (float*)ix->scores.p,
                        stream));
+    IvfsRange sel_range{0.f, nullptr, nullptr};
+    if (rg) sel_range = IvfsRange{rg->floor, rg->excl_pos, d_cnt};
     MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
-                               stored_bits));
+                               stored_bits, rg ? &sel_range : nullptr));
     MRAG_HIP(hipEventRecord(ev_scan1, stream));
   } else {
     MRAG_HIP(hipMemsetAsync(ix->gq.p, 0xFF, (size_t)wg_bound * 256 * 8, stream));   // (the gather below reads whole 256-slot slabs)
@@ -790,6 +846,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
   }
   ix->last_scores_path = use_scores;
   (void)n_wg;
+  if (rg && !out_is_device) MRAG_HIP(hipMemcpyAsync(rg->out_counts, d_cnt, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
   return ivf_copy_back(nq, k, out_scores, out_ids, out_is_device, d_sc, d_id, stream);
 }
 
@@ -806,14 +863,17 @@ static int ivf_grow_cev(IvfIndex* ix, int n_chunks) {
 // the chunks of a search of nq queries, chunk queries each, one after another (live_bits / stored_bits: as ivf_search_chunk)
 static int ivf_run_chunks(IvfIndex* ix, const void* queries, int64_t nq, int64_t chunk, int q_dtype, int normalize, int queries_is_device,
                           int nprobe, int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream,
-                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr) {
+                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr, const IvfRangeArgs* rg = nullptr) {
   const int n_chunks = (int)((nq + chunk - 1) / chunk);
   MRAG_TRY(ivf_grow_cev(ix, n_chunks));
-  const size_t qrow = (size_t)ix->dim * esize(q_dtype);
+  const size_t qrow = rg && rg->stored_rows ? (size_t)ix->ld * 2 : (size_t)ix->dim * esize(q_dtype);
   for (int c = 0; c < n_chunks; ++c) {
     const int64_t off = (int64_t)c * chunk, m = std::min(chunk, nq - off);
+    IvfRangeArgs crg;
+    if (rg) { crg = *rg; if (crg.excl_pos) crg.excl_pos += off; crg.out_counts += off; }
     MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, m, q_dtype, normalize, queries_is_device, nprobe, k,
-                              out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c, live_bits, stored_bits));
+                              out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c, live_bits, stored_bits,
+                              rg ? &crg : nullptr));
   }
   ix->n_chunks = n_chunks;
   return MRAG_OK;
@@ -871,6 +931,102 @@ int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype,
   // queries and results in device memory the search is fully asynchronous on `stream`
   if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
+}
+
+}  // extern "C"
+
+namespace mrag {
+
+// ---- range search ---------------------------------------------------------------------------------------------------------
+// What mrag_ivf_search_range and mrag_ivf_self_join share once their arguments are checked and ivf_search_begin has run:
+// the refusals known before any chunk runs, the excluded rows as stored positions (rows: device int64 [nq], or NULL with
+// self_row0 >= 0 for "query i excludes row self_row0 + i", or neither: no exclusion), the chunks, the timing record.
+static int ivf_range_run(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
+                         int k, float floor, const int64_t* d_excl_rows, int64_t self_row0, int64_t chunk, float* out_scores,
+                         int64_t* out_ids, int64_t* out_counts, int out_is_device, hipStream_t stream) {
+  if (ivf_scores_cap() <= 0) return ivf_range_unsupported("the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
+  if (nprobe > 256) return ivf_range_unsupported("more than 256 probed lists per query (exhaustive probing with nlist > 256)");
+  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  MRAG_TRY(ix->stats.ensure(16));
+  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
+  IvfRangeArgs rg;
+  rg.floor = floor; rg.out_counts = out_counts; rg.stored_rows = self_row0 >= 0;
+  if (d_excl_rows || self_row0 >= 0) {
+    if (!ix->inv_valid) {
+      MRAG_TRY(ix->inv_pos.ensure((size_t)std::max<int64_t>(ix->n, 1) * 8));
+      hipLaunchKernelGGL(ivf_inverse_pos_kernel, dim3((unsigned)((ix->n_sorted + 255) / 256)), dim3(256), 0, stream,
+                         (const int64_t*)ix->row_ids, ix->n_sorted, ix->n, (int64_t*)ix->inv_pos.p);
+      MRAG_HIP(hipGetLastError());
+      ix->inv_valid = true;
+    }
+    int64_t* d_pos = (int64_t*)ix->excl.p + nq;
+    hipLaunchKernelGGL(ivf_excl_pos_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_excl_rows, self_row0, nq, ix->n,
+                       (const int64_t*)ix->inv_pos.p, d_pos);
+    MRAG_HIP(hipGetLastError());
+    rg.excl_pos = d_pos;
+  }
+  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device,
+                          stream, nullptr, nullptr, &rg));
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->end_recorded = true;
+  ix->timed = true;
+  return MRAG_OK;
+}
+
+static int ivf_check_range_args(int64_t nq, int k, int nprobe, float min_score, const void* out_counts) {
+  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
+  if (k > 256) return fail(MRAG_ERR_INVALID, "range search: k = %d, supported are 1..256 (the per-query selection's limit)", k);
+  if (!(min_score == min_score) || min_score - min_score != 0.f) return fail(MRAG_ERR_INVALID, "min_score must be finite");
+  if (nq > 0 && !out_counts) return fail(MRAG_ERR_INVALID, "out_counts is NULL");
+  return MRAG_OK;
+}
+
+}  // namespace mrag
+
+extern "C" {
+
+int mrag_ivf_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int nprobe, int k, float min_score, const int64_t* exclude_rows, int exclude_is_device,
+                          float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(ivf_check_range_args(nq, k, nprobe, min_score, out_counts));
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t chunk = 0;
+  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  if (nq == 0) return MRAG_OK;
+  const int64_t* d_excl = nullptr;
+  if (exclude_rows) {
+    MRAG_TRY(ix->excl.ensure((size_t)nq * 16));
+    if (exclude_is_device) {
+      d_excl = exclude_rows;
+    } else {
+      for (int64_t i = 0; i < nq; ++i)
+        if (exclude_rows[i] < -1 || exclude_rows[i] >= ix->n)
+          return fail(MRAG_ERR_INVALID, "exclude_rows[%lld] = %lld: a local row 0..%lld or -1", (long long)i, (long long)exclude_rows[i], (long long)ix->n - 1);
+      MRAG_HIP(hipMemcpyAsync(ix->excl.p, exclude_rows, (size_t)nq * 8, hipMemcpyHostToDevice, stream));
+      d_excl = (const int64_t*)ix->excl.p;
+    }
+  }
+  MRAG_TRY(ivf_range_run(ix, queries, nq, q_dtype, normalize, queries_is_device, nprobe, k, min_score, d_excl, -1, chunk, out_scores,
+                         out_ids, out_counts, out_is_device, stream));
+  if (!out_is_device || !queries_is_device || (exclude_rows && !exclude_is_device)) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_ivf_self_join(mrag_handle h, int64_t row0, int64_t n, int nprobe, int k, float min_score, float* out_scores, int64_t* out_ids,
+                       int64_t* out_counts, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(ivf_check_range_args(n, k, nprobe, min_score, out_counts));
+  if (row0 < 0 || row0 + n > ix->n) return fail(MRAG_ERR_INVALID, "self-join rows [%lld, %lld) outside the %lld stored rows", (long long)row0, (long long)(row0 + n), (long long)ix->n);
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t chunk = 0;
+  const void* rows = n ? (const void*)(ix->raw + (size_t)row0 * ix->ld) : nullptr;
+  MRAG_TRY(ivf_search_begin(ix, rows, n, ix->dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  if (n == 0) return MRAG_OK;
+  MRAG_TRY(ix->excl.ensure((size_t)n * 16));
+  return ivf_range_run(ix, rows, n, ix->dtype, 0, 1, nprobe, k, min_score, nullptr, row0, chunk, out_scores, out_ids, out_counts, 1, stream);
 }
 
 }  // extern "C"

@@ -236,6 +236,15 @@ struct SelParamsF {
   SelParams p;
   const uint32_t* bits;
 };
+// the range (RANGE) instances: SelParams + a score floor, an optional excluded stored position per query and the per-query
+// counts.  An entry whose fp32 score is below the floor, or that sits at the excluded position, is never selected and never
+// counted.  (Again a struct of its own: the other instances keep their kernel arguments.)
+struct SelParamsR {
+  SelParams p;
+  float floor;                // finite; compared on the fp32 score (score >= floor)
+  const int64_t* excl_pos;    // [nq] stored position of the query's excluded row (-1: none), or nullptr
+  int64_t* counts;            // [nq] entries of the query's probed segments that reach the floor (the excluded one left out)
+};
 
 // Selection = (score desc, original row asc), exact.
 //   fast path  every thread keeps its <= 32 scores in registers (entry e = tid + 256 i).  The k-th largest of the 256
@@ -247,8 +256,13 @@ struct SelParamsF {
 //              arg-max over the segments, rows looked up only for entries tied with the current score.
 // FILT: entries whose bit in `bits` is clear get the "empty" key 0 and never enter a shortlist or an arg-max round; fewer
 // selectable entries than k leave the tail (-inf, -1).
-template <bool DENSE, bool FILT = false>
-__device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint32_t* __restrict__ bits = nullptr) {
+// RANGE: the same for entries below the floor and for the query's excluded entry; the entries that are left are counted
+// (per thread, one workgroup sum at the end: the workgroup owns its query, no global atomics) in the pass that visits every
+// entry -- the register fill, pass 2 of the streamed path, or a pass of its own when the serial path is entered directly.
+// Fewer than k thread maxima with a key leave the bound P at 0: every entry that reaches the floor is shortlisted.
+template <bool DENSE, bool FILT = false, bool RANGE = false>
+__device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint32_t* __restrict__ bits = nullptr,
+                                                 const SelParamsR* rg = nullptr) {
   __shared__ const float* seg_ptr[SEL_MAXP];
   __shared__ int seg_cnt[SEL_MAXP];
   __shared__ int seg_pre[SEL_MAXP + 1];
@@ -258,6 +272,7 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
   __shared__ int64_t cand_row[SEL_CAND];
   __shared__ unsigned long long red[2][SEL_THR / 64];
   __shared__ int n_cand;
+  __shared__ int excl_entry;                         // RANGE: the excluded row's entry index among the query's candidates, -1: none
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t q = blockIdx.x;
   const int k = p.k;
@@ -295,6 +310,7 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
     seg_ptr[tid] = ptr; seg_cnt[tid] = cnt; seg_row0[tid] = r0;
   }
   if (tid == 0) n_cand = 0;
+  if constexpr (RANGE) { if (tid == 0) excl_entry = -1; }
   __syncthreads();
   if (w == 0) {                                      // prefix sums of the <= 256 segment lengths: 4 per lane + a wave scan
     int c[4], sum = 0;
@@ -312,6 +328,24 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
   }
   __syncthreads();
   const int total = seg_pre[np];
+  float floor = 0.f;
+  int excl_e = -1;
+  int my_cnt = 0;                                  // RANGE: this thread's entries that reach the floor
+  bool counted = false;                            // RANGE: my_cnt covers every entry
+  if constexpr (RANGE) {
+    // the excluded row sits in at most one of the probed lists: the thread of that segment turns its stored position
+    // into an entry index, so that no entry pays a row lookup for the exclusion
+    floor = rg->floor;
+    const int64_t xp = rg->excl_pos ? rg->excl_pos[q] : -1;
+    if (tid < np && xp >= 0) {
+      const int64_t off = xp - seg_row0[tid];
+      if (off >= 0 && off < seg_cnt[tid]) excl_entry = seg_pre[tid] + (int)off;
+    }
+    __syncthreads();
+    excl_e = excl_entry;
+  }
+  // RANGE: the entry e with score s takes part (reaches the floor, is not the excluded one; a NaN score never does)
+  auto in_range = [&](float s, int e) -> bool { return s >= floor && e != excl_e; };
   auto row_at = [&](int j, int t) -> int64_t { return DENSE ? (int64_t)t : p.row_ids[seg_row0[j] + t]; };
   auto selectable = [&](int j, int t) -> bool {   // FILT: the entry's bit (dense: row t; lists: stored position)
     const int64_t pos = DENSE ? (int64_t)t : seg_row0[j] + t;
@@ -407,11 +441,13 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
 #pragma unroll
       for (int i = 0; i < SEL_EPT; ++i) {
         const int e = tid + i * SEL_THR;
-        const bool ok = e < total && (!FILT || ((okm >> i) & 1u));
+        const bool ok = e < total && (!FILT || ((okm >> i) & 1u)) && (!RANGE || in_range(raw[i], e));
         const uint32_t key = ok ? s_f32_ord(raw[i]) : 0u;   // 0: below every real key (s_f32_ord never returns 0 for a non-NaN score)
         kr[i] = key;
         tmax = key > tmax ? key : tmax;
+        if constexpr (RANGE) my_cnt += ok ? 1 : 0;
       }
+      if constexpr (RANGE) counted = true;
     }
     // k <= 16: every WAVE bounds its own quarter of the entries -- the k-th largest of its 64 lane maxima, found with ballots
     // only (no LDS, no workgroup barrier: the block-wide bisection costs 16 barriers per query).  A wave's top k all reach its
@@ -422,10 +458,10 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
 #pragma unroll
     for (int i = 0; i < SEL_EPT; ++i) {
       const int e = tid + i * SEL_THR;
-      shortlist_append(e < total && kr[i] >= P && (!FILT || kr[i] != 0u), kr[i], e);
+      shortlist_append(e < total && kr[i] >= P && (!(FILT || RANGE) || kr[i] != 0u), kr[i], e);
     }
     if (!rank_shortlist()) serial = true;
-    else if (FILT) n_out = n_cand < k ? n_cand : k;
+    else if (FILT || RANGE) n_out = n_cand < k ? n_cand : k;
   }
   if (streamed) {
     // ---- more than 8192 candidates (long lists: C5's whole 5 M rows on one GPU give ~39 000 per query): the same
@@ -442,10 +478,13 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
     for (int j = 0; j < np && seen < want; ++j) {
       const float* sp = seg_ptr[j];
       const int cnt = seg_cnt[j];
+      [[maybe_unused]] const int pre = seg_pre[j];
       seen += cnt;
 #pragma unroll 8
       for (int t = tid; t < cnt; t += SEL_THR) {
-        const uint32_t key = (!FILT || selectable(j, t)) ? s_f32_ord(sp[t]) : 0u;
+        uint32_t key;
+        if constexpr (RANGE) { const float s = sp[t]; key = in_range(s, pre + t) ? s_f32_ord(s) : 0u; }
+        else key = (!FILT || selectable(j, t)) ? s_f32_ord(sp[t]) : 0u;
         tmax = key > tmax ? key : tmax;
       }
     }
@@ -460,13 +499,15 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int t = t0 + u * SEL_THR + tid;
-          const uint32_t key = (t < cnt && (!FILT || selectable(j, t))) ? s_f32_ord(raw[u]) : 0u;
-          shortlist_append(t < cnt && key >= P && (!FILT || key != 0u), key, pre + t);
+          const uint32_t key = (t < cnt && (!FILT || selectable(j, t)) && (!RANGE || in_range(raw[u], pre + t))) ? s_f32_ord(raw[u]) : 0u;
+          if constexpr (RANGE) my_cnt += key != 0u ? 1 : 0;
+          shortlist_append(t < cnt && key >= P && (!(FILT || RANGE) || key != 0u), key, pre + t);
         }
       }
     }
+    if constexpr (RANGE) counted = true;
     if (!rank_shortlist()) serial = true;
-    else if (FILT) n_out = n_cand < k ? n_cand : k;
+    else if (FILT || RANGE) n_out = n_cand < k ? n_cand : k;
   }
   if (serial) {
     // ---- serial path: kk rounds of arg-max in (score desc, row asc) order, strictly after the previous winner
@@ -482,22 +523,30 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
     };
     uint32_t last_key = 0u;
     int64_t last_row = -1;
+    if constexpr (RANGE) {
+      if (!counted) {                                                   // (workgroup-uniform) entered directly: fewer candidates than k
+        for_each([&](int j, int t) { my_cnt += in_range(seg_ptr[j][t], seg_pre[j] + t) ? 1 : 0; });
+        counted = true;
+      }
+    }
     for (int it = 0; it < kk; ++it) {
       unsigned long long best = 0ull;                                   // key + 1 (0 = none)
       for_each([&](int j, int t) {
         if (FILT && !selectable(j, t)) return;
+        if (RANGE && !in_range(seg_ptr[j][t], seg_pre[j] + t)) return;
         const uint32_t key = s_f32_ord(seg_ptr[j][t]);
         bool ok = it == 0 || key < last_key;
         if (!ok && key == last_key) ok = row_at(j, t) > last_row;
         if (ok && (unsigned long long)key + 1ull > best) best = (unsigned long long)key + 1ull;
       });
       best = block_reduce(best, true);
-      if (FILT && best == 0ull) { n_out = it; break; }                 // (workgroup-uniform) no selectable entry left
+      if ((FILT || RANGE) && best == 0ull) { n_out = it; break; }      // (workgroup-uniform) no selectable entry left
       const uint32_t kmax = (uint32_t)(best - 1ull);
       unsigned long long br = ~0ull;                                    // row << 32 | position inside the workgroup's walk is not needed: rows are distinct
       for_each([&](int j, int t) {
         if (s_f32_ord(seg_ptr[j][t]) != kmax) return;
         if (FILT && !selectable(j, t)) return;
+        if (RANGE && seg_pre[j] + t == excl_e) return;                  // (same key as the winner: it reaches the floor)
         const int64_t r = row_at(j, t);
         if (it == 0 || kmax < last_key || r > last_row) br = (unsigned long long)r < br ? (unsigned long long)r : br;
       });
@@ -511,6 +560,17 @@ __device__ __forceinline__ void ivfs_select_body(const SelParams& p, const uint3
     if (p.out_scores) p.out_scores[q * k + i] = -INFINITY;
     p.out_ids[q * k + i] = -1;
   }
+  if constexpr (RANGE) {
+    int c = my_cnt;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if (lane == 0) red[red_slot][w] = (unsigned long long)c;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long t = 0;
+      for (int i = 0; i < SEL_THR / 64; ++i) t += red[red_slot][i];
+      rg->counts[q] = (int64_t)t;
+    }
+  }
 }
 
 // (two entry points: the single-segment form fits 64 registers and runs 8 waves per SIMD -- 88 -> 71 us for 10 000 probe
@@ -521,6 +581,8 @@ __global__ __launch_bounds__(SEL_THR) void ivfs_select_lists_kernel(SelParams p)
 // allowed stored rows only
 __global__ __launch_bounds__(SEL_THR) __attribute__((amdgpu_waves_per_eu(8, 8))) void ivfs_select_dense_filt_kernel(SelParamsF f) { ivfs_select_body<true, true>(f.p, f.bits); }
 __global__ __launch_bounds__(SEL_THR) void ivfs_select_lists_filt_kernel(SelParamsF f) { ivfs_select_body<false, true>(f.p, f.bits); }
+// range instance (mrag_ivf_search_range, mrag_ivf_self_join): the rows of the probed lists that reach the floor, and their count
+__global__ __launch_bounds__(SEL_THR) void ivfs_select_lists_range_kernel(SelParamsR f) { ivfs_select_body<false, false, true>(f.p, nullptr, &f); }
 
 // ------------------------------------------------------------------ descriptors of the dense (probe selection) case
 __global__ void ivfs_dense_desc_kernel(int* __restrict__ desc, int n_qt, int n_chunks, int64_t nq, int n_rows, int rows_per_wg, int pitch) {
@@ -555,13 +617,16 @@ int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype
 }
 
 int ivfs_select_lists(const float* S, const void* pinfo, int nprobe, int64_t nq, int k, const int64_t* row_ids,
-                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits) {
+                      int64_t id_base, float* out_scores, int64_t* out_ids, hipStream_t stream, const uint32_t* stored_bits,
+                      const IvfsRange* range) {
   if (nq <= 0) return MRAG_OK;
   if (nprobe > SEL_MAXP || k > SEL_MAXK) return fail(MRAG_ERR_UNSUPPORTED, "ivfs_select: nprobe %d / k %d above %d / %d", nprobe, k, SEL_MAXP, SEL_MAXK);
+  if (range && stored_bits) return fail(MRAG_ERR_UNSUPPORTED, "ivfs_select: no filtered range instance");
   SelParams p{};
   p.S = S; p.pinfo = (const int4*)pinfo; p.row_ids = row_ids; p.nprobe = nprobe; p.k = k;
   p.id_base = id_base; p.out_scores = out_scores; p.out_ids = out_ids;
-  if (stored_bits) hipLaunchKernelGGL(ivfs_select_lists_filt_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, SelParamsF{p, stored_bits});
+  if (range) hipLaunchKernelGGL(ivfs_select_lists_range_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, SelParamsR{p, range->floor, range->excl_pos, range->counts});
+  else if (stored_bits) hipLaunchKernelGGL(ivfs_select_lists_filt_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, SelParamsF{p, stored_bits});
   else hipLaunchKernelGGL(ivfs_select_lists_kernel, dim3((unsigned)nq), dim3(SEL_THR), 0, stream, p);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;

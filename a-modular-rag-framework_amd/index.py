@@ -567,6 +567,7 @@ class IVFFlatIndex:
         N.check(self._lib.mrag_ivf_create(self.dim, self.nlist, N.METRIC_COSINE if metric == "cosine" else N.METRIC_IP,
                                           N.MRAG_F16 if dtype == "f16" else N.MRAG_BF16, self.device, C.byref(h)))
         self._h = h
+        self.id_base = 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -608,6 +609,7 @@ class IVFFlatIndex:
 
     def set_id_base(self, base: int):
         N.check(self._lib.mrag_ivf_set_id_base(self._h, int(base)))
+        self.id_base = int(base)
 
     def assignments(self) -> np.ndarray:
         out = np.empty(len(self), dtype=np.int32)
@@ -642,6 +644,102 @@ class IVFFlatIndex:
         def call(sc, ids, out_dev, st):
             return self._lib.mrag_ivf_search(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), sc, ids, out_dev, st)
         return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev))
+
+    @staticmethod
+    def _check_nprobe(nprobe) -> int:
+        if isinstance(nprobe, (bool, np.bool_)) or not isinstance(nprobe, numbers.Integral) or int(nprobe) < 1:
+            raise ValueError(f"nprobe must be a positive integer, got {nprobe!r}")
+        return int(nprobe)
+
+    def _exclude_buffer(self, exclude, nq: int):
+        """-> (keepalive, pointer, is_device): one excluded local row per query (int64 [nq], -1 = none)."""
+        if _is_torch(exclude) and exclude.is_cuda:
+            import torch
+            if exclude.dim() != 1 or exclude.shape[0] != nq:
+                raise ValueError(f"exclude must be 1-D with one row per query ({nq}), got shape {tuple(exclude.shape)}")
+            if exclude.dtype != torch.int64:
+                raise ValueError(f"a device exclude must be int64, got {exclude.dtype}")
+            if exclude.device.index != self.device:
+                raise ValueError(f"exclude is on {exclude.device}, the index on cuda:{self.device}")
+            t = exclude.contiguous()
+            return t, t.data_ptr(), 1
+        a = exclude.cpu().numpy() if _is_torch(exclude) else np.asarray(exclude)
+        if a.ndim != 1 or a.shape[0] != nq:
+            raise ValueError(f"exclude must be 1-D with one row per query ({nq}), got shape {a.shape}")
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"exclude must hold integer row positions (-1 = none), got dtype {a.dtype}")
+        if a.size and int(a.min()) < -1:
+            raise ValueError(f"exclude rows must be >= -1, got {int(a.min())}")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        return a, a.ctypes.data, 0
+
+    def range_search(self, queries, min_score: float, k: int, nprobe: int, normalize: Optional[bool] = None, exclude=None,
+                     stream=None, out=None):
+        """Rows of the probed lists scoring >= ``min_score`` (``mrag_ivf_search_range``) -> (scores [nq,k] fp32, ids [nq,k]
+        int64, counts [nq] int64).
+
+        Per query, over the rows of its ``nprobe`` probed lists only (the lists :meth:`search` probes), with c = the number
+        of those rows scoring >= ``min_score`` (inclusive; the floor is the smallest float32 >= ``min_score``, see
+        :func:`range_floor`): the best ``min(k, c)`` of them, (score desc, row asc), then (-inf, -1) slots; ``counts[q] = c``
+        exactly, so a query is truncated when ``counts[q] > k``.  ``counts`` is a lower bound of
+        :meth:`DenseIndex.range_search`'s and equal to it when every list is probed.  Scores are the ones :meth:`search`
+        returns.  ``min_score`` must be finite, ``1 <= k <= 256``, ``nprobe >= 1`` (``ValueError`` otherwise, before any
+        GPU work).  ``exclude``: one local row (before ``id_base``) per query, int64 [nq], -1 for none, on the host or on
+        this index's device; that row is neither listed nor counted, rows holding the same values stay.  Host queries give
+        numpy arrays; CUDA tensors give CUDA tensors written on ``stream``; ``out=(scores, ids, counts)`` reuses buffers.
+
+        The search runs in the score-segment regime only: ``nprobe = nlist > 256``, ``MRAG_IVF_SCORES_MB=0`` or segments
+        beyond the score buffer raise :class:`MragError` (``MRAG_ERR_UNSUPPORTED``); no answer comes back without the
+        floor applied.  There is no ``allow=`` parameter: a floor does not combine with an allow-set on this index."""
+        floor = range_floor(min_score)
+        k = _check_k(k, 256)
+        nprobe = self._check_nprobe(nprobe)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        xkeep, xptr, xdev = (None, None, 0) if exclude is None else self._exclude_buffer(exclude, nq)
+        if out is not None:
+            counts = out[2]
+        elif is_dev:
+            import torch
+            counts = torch.empty(nq, dtype=torch.int64, device=keep.device)
+        else:
+            counts = np.empty(nq, dtype=np.int64)
+        norm = self._norm(normalize)
+
+        def call(sc, ids, out_dev, st):
+            cptr = counts.data_ptr() if out_dev else counts.ctypes.data
+            return self._lib.mrag_ivf_search_range(self._h, ptr, nq, dt, norm, is_dev, nprobe, k, float(floor), xptr, xdev,
+                                                   sc, ids, cptr, out_dev, st)
+        sc, ids = _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or xdev),
+                              None if out is None else (out[0], out[1]))
+        del xkeep
+        return sc, ids, counts
+
+    def self_join(self, min_score: float, nprobe: int, k: int = 64, batch: int = 65536):
+        """Every stored row as a query against the rows of its ``nprobe`` probed lists, itself left out
+        (``mrag_ivf_self_join``) -> CUDA tensors on this index's device (scores [n,k] fp32, ids [n,k] int64, counts [n]
+        int64): row ``i``'s result is ``range_search(stored row i, min_score, k, nprobe, exclude=i)``.
+
+        The stored 16-bit rows are the queries as they are (device to device, no renormalisation).  The row itself is
+        excluded inside the selection kernel by its position, so duplicates of it stay, ``counts`` never includes it and
+        ``1 <= k <= 256``.  Batches of ``batch`` rows run in order on torch's current stream; the result does not depend on
+        ``batch``.  A pair of rows is found only from a side whose probed lists hold the other row."""
+        import torch
+        floor = range_floor(min_score)
+        k = _check_k(k, 256)
+        nprobe = self._check_nprobe(nprobe)
+        if isinstance(batch, (bool, np.bool_)) or not isinstance(batch, numbers.Integral) or int(batch) < 1:
+            raise ValueError(f"batch must be a positive integer, got {batch!r}")
+        n, dev = len(self), torch.device("cuda", self.device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        st = _stream_ptr(torch.cuda.current_stream(dev))
+        b = int(batch)
+        for r0 in range(0, n, b):
+            m = min(b, n - r0)
+            N.check(self._lib.mrag_ivf_self_join(self._h, r0, m, nprobe, k, float(floor), scores[r0:r0 + m].data_ptr(),
+                                                 ids[r0:r0 + m].data_ptr(), counts[r0:r0 + m].data_ptr(), st))
+        return scores, ids, counts
 
     def _list_allowed_buffer(self, list_allowed, adev: int):
         if list_allowed is None:

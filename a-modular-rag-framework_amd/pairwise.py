@@ -69,14 +69,22 @@ def neighbor_lists_to_edges(scores, ids, id_base: int = 0) -> List[Tuple[int, in
     return [(int(a), int(b), float(v)) for a, b, v in zip(i[first], j[first], sim[first])]
 
 
-def semantic_edges_index(index, threshold: float = 0.9, k: int = 64, batch: int = 16384):
+def semantic_edges_index(index, threshold: float = 0.9, k: int = 64, batch: int = 16384, nprobe: Optional[int] = None):
     """``semantic_edges`` over the rows of a :class:`~mrag_amd.index.DenseIndex` at corpus scale -> (edges,
     truncated_rows): the range self-join (:meth:`DenseIndex.self_join`) lists up to ``k`` neighbours >= ``threshold`` per
     row (fp32 scores over the stored 16-bit rows) and :func:`neighbor_lists_to_edges` turns the lists into the
     [(i, j, sim)] form of ``semantic_edges`` (local rows, i < j, (i, j) order).  ``truncated_rows`` (int64 array) lists
     the rows with more than ``k`` neighbours >= ``threshold``: their edge sets may be incomplete.  ``semantic_edges``
-    stays the fp64 path."""
-    sc, ids, counts = index.self_join(threshold, k=k, batch=batch)
+    stays the fp64 path.
+
+    With ``nprobe`` given, ``index`` is an :class:`~mrag_amd.index.IVFFlatIndex` and the join is
+    :meth:`IVFFlatIndex.self_join` over each row's ``nprobe`` probed lists.  That form is approximate in WHICH pairs it
+    finds: a pair whose rows do not probe each other's lists is missed (it is found when either side probes the other's
+    list); the similarities of the pairs it lists are the exact join's.  ``nprobe=None`` is the exact join above."""
+    if nprobe is None:
+        sc, ids, counts = index.self_join(threshold, k=k, batch=batch)
+    else:
+        sc, ids, counts = index.self_join(threshold, nprobe, k=k, batch=batch)
     edges = neighbor_lists_to_edges(sc.cpu().numpy(), ids.cpu().numpy(), index.id_base)
     truncated = np.nonzero(counts.cpu().numpy() > k)[0].astype(np.int64)
     return edges, truncated

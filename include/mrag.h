@@ -270,8 +270,32 @@ int mrag_ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_
 /* path (PROBE / EXACT), allowed rows and live lists of the LAST filtered search on this handle; live lists is -2 when the
  * search ran path E (lists are not consulted there).  Blocks until that search is done when a figure is still on the device. */
 int mrag_ivf_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed, int* out_live_lists);
+/* Range search over the probed lists (the IVF form of mrag_index_search_range; serves the semantic_sim edge pass,
+ * edge_builder.py:146-169: every pair of rows with cosine >= a threshold, at corpus sizes where the exact join is too slow).
+ * Per query, over the rows of its `nprobe` probed lists ONLY (probe selection as mrag_ivf_search), with c = the number of
+ * those rows whose fp32 score is >= min_score (inclusive): out_scores / out_ids hold the best min(k, c) of them, (score desc,
+ * original row asc), ids = row + id_base; the slots after them are (-inf, -1); out_counts[q] = c exactly (int64, in the memory
+ * space of the other outputs).  c is a lower bound of the dense index's count and equals it when every list is probed.
+ * The scores are the ones mrag_ivf_search returns; a floor below every score returns exactly its result.
+ * exclude_rows (optional, NULL = none): int64 [nq] in host or device memory (exclude_is_device), a LOCAL row (before id_base)
+ * per query or -1.  That row is neither listed nor counted; other rows with the same values stay.  A host value outside
+ * [-1, size) is MRAG_ERR_INVALID; a device value outside [0, size) means none.
+ * 1 <= k <= 256, min_score finite, nprobe as mrag_ivf_search (MRAG_ERR_INVALID otherwise).  The search runs in the
+ * score-segment regime only: with more than 256 probed lists per query (nprobe = nlist > 256), with MRAG_IVF_SCORES_MB = 0,
+ * or when the score segments of one chunk exceed the score buffer it returns MRAG_ERR_UNSUPPORTED and writes no answer.
+ * There is no allow-set form.  Batches are cut into chunks as in mrag_ivf_search; sync behaviour as there (device queries,
+ * device exclude_rows or none, and device outputs: asynchronous on `stream`). */
+int mrag_ivf_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int nprobe, int k, float min_score, const int64_t* exclude_rows, int exclude_is_device,
+                          float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device, void* stream);
+/* Neighbour join (edge_builder.py:146-169 over an indexed corpus): the stored rows [row0, row0 + n) as the queries of
+ * mrag_ivf_search_range, each excluding itself (exclude = row0 + i).  The rows are taken device to device from the index's
+ * copy in insertion order, in the storage dtype as stored: no normalisation, no fp32 round trip.  Outputs are device
+ * buffers [n][k], [n][k], [n]; asynchronous on `stream`.  Limits and refusals as mrag_ivf_search_range. */
+int mrag_ivf_self_join(mrag_handle h, int64_t row0, int64_t n, int nprobe, int k, float min_score,
+                       float* out_scores, int64_t* out_ids, int64_t* out_counts, void* stream);
 /* measurement hooks for bench.py (like mrag_index_last_timing): device ms of the list scan (scan + per-query selection kernels, or the fused kernel) and of the
- * whole LAST mrag_ivf_search or mrag_ivf_search_filtered (hipEvents on its stream; filtered: the list scan + selection on
+ * whole LAST mrag_ivf_search, mrag_ivf_search_filtered, mrag_ivf_search_range or mrag_ivf_self_join (hipEvents on its stream; filtered: the list scan + selection on
  * path P, the search kernel on path E), the rows that scan streamed (sum over its
  * workgroups of their list's length: x ld x 2 = the algorithmic HBM bytes) and its workgroup count. */
 int mrag_ivf_last_timing(mrag_handle h, float* out_scan_ms, float* out_total_ms, int64_t* out_scanned_rows, int* out_n_wg);
