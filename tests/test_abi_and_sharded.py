@@ -103,6 +103,15 @@ assert np.array_equal(ip, i) and np.array_equal(vp, v)
 assert set(sh.last_phases) >= {"local_ms", "pack_ms", "gather_ms", "merge_ms"}, sh.last_phases
 vp1, ip1 = sh.search(q16[:1], k, pipeline=True)      # a single query cannot be cut: falls back to one shot
 assert np.array_equal(ip1, i[:1])
+# changing batch sizes and k, one shot and pipeline in turn, on the SAME index: every answer is the unsharded one ...
+turn = 0
+for k2 in (10, 3):
+    for nq2 in (37, 5, 2, 36, 19):
+        v2, i2 = sh.search(q16[:nq2], k2, pipeline=bool(turn & 1)); turn += 1
+        rv2, ri2 = ds.brute_force_topk(q16[:nq2], c16, k2)
+        assert (i2 == ri2).all() and np.array_equal(v2, rv2.astype(np.float32)), (k2, nq2)
+# ... and the exchange keeps gather buffers for the last call's shape only (here: 19 rows cut 9 + 10), not one set per batch size
+assert [tuple(g.shape) for g in sh._exchange.gather] == [(world, 9, 3), (world, 10, 3)], [g.shape for g in sh._exchange.gather]
 # ADVICE r2: one caller-kept `bufs` reused with ANOTHER n_total (same world / q / k) must not reuse stale bases
 from mrag_amd.sharded import gather_and_merge
 bufs = {}

@@ -6,8 +6,7 @@ import sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np, torch
-from mrag_amd.index import DenseIndex
-from mrag_amd.sharded import merge_gathered
+from mrag_amd.index import DenseIndex, topk_merge, topk_merge_device
 d, nq, k = 768, 10000, 10
 g = torch.Generator(device="cuda").manual_seed(1)
 q = torch.randn(nq, d, device="cuda", generator=g)
@@ -19,15 +18,22 @@ for world in (1, 2, 4, 8):
     sc, ids = ix.search(q, k); torch.cuda.synchronize()
     gs = torch.stack([sc - 0.001 * r for r in range(world)]).contiguous()
     gi = torch.stack([ids + n * r for r in range(world)]).contiguous()
+    # the merge leg as the exchange does it: merged on the device + pinned D2H of [Q,k], or pinned D2H of everything + host merge
+    ms, mi = torch.empty_like(sc), torch.empty_like(ids)
+    hms, hmi, hgs, hgi = (torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (ms, mi, gs, gi))
     out = {}
     for mode in (["host", "device"] if world > 1 else ["local"]):
-        bufs = {}
         ts = []
         for it in range(12):
             torch.cuda.synchronize(); t = time.perf_counter()
             sc, ids = ix.search(q, k)
-            if world > 1:
-                merge_gathered(gs, gi, bufs, merge=mode)
+            if mode == "device":
+                topk_merge_device(gs, gi, ms, mi)
+                hms.copy_(ms, non_blocking=True); hmi.copy_(mi, non_blocking=True)
+            elif mode == "host":
+                hgs.copy_(gs, non_blocking=True); hgi.copy_(gi, non_blocking=True)
+                torch.cuda.synchronize()
+                topk_merge(hgs.numpy(), hgi.numpy())
             else:
                 sc.cpu(); ids.cpu()
             torch.cuda.synchronize(); ts.append(time.perf_counter() - t)
