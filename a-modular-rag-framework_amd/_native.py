@@ -97,6 +97,10 @@ SIGNATURES = {
     "mrag_ivf_allowed_per_list": [_h, _vp, _i64, _i, _i, _vp, _i, _vp],
     "mrag_ivf_choose_filter_path": [_i64, _i, _i, _i, _i64, _i64, _i, C.POINTER(_i)],
     "mrag_ivf_last_filter": [_h, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i)],
+    "mrag_ivf_enable_fp8": [_h],
+    "mrag_ivf_get_rows_fp8": [_h, _i64, _i64, _vp, _i, _vp],
+    "mrag_ivf_search_fp8": [_h, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "mrag_ivf_last_fp8": [_h, C.POINTER(_i)],
     "mrag_ivf_last_timing": [_h, _fp, _fp, C.POINTER(_i64), C.POINTER(_i)],
     "mrag_bm25_create": [_i, _i64, _i64, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(_h)],
     "mrag_bm25_destroy": [_h],

@@ -64,10 +64,7 @@ namespace mrag {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef const __attribute__((address_space(1))) void* glb_vptr;
 
@@ -153,18 +150,8 @@ template <> struct Mfma<MRAG_BF16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   }
 };
-// fp8 scan copy: the block-scaled 16x16x128 form (2x the fp16 MFMA rate; the unscaled _fp8_fp8 forms run at the fp16
-// rate) with e4m3 A and B (format 0) and neutral E8M0 scales (127 = 2^0).  A 128-element K step is the 128 bytes per row a
-// 16-bit K step stages, so the stage layout and the two 16-byte fragment reads (k halves ph0 / ph1) stay; the two reads
-// form one 32-byte operand.  Which k a register byte stands for does not matter as long as A and B read alike.
-template <> struct Mfma<MRAG_DT_FP8> {
-  typedef i32x4 frag;
-  static __device__ __forceinline__ f32x4 run2(frag a0, frag a1, frag b0, frag b1, f32x4 c) {
-    const i32x8 a = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-    const i32x8 b = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
-  }
-};
+// fp8 scan copy: the block-scaled 16x16x128 form, one MFMA per two 16-byte fragment reads (common.h)
+template <> struct Mfma<MRAG_DT_FP8> : MfmaFp8 {};
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1856,8 +1843,7 @@ __global__ void remap_ids_kernel(int64_t* __restrict__ ids, int64_t tot, const i
 //   A search quantises each prepared query with its own power of two (max |q~| in [128, 256)), picks the top-`refine`
 //   rows by fp8 score with the fp8 instances of K2 / K2s + the unchanged merges, then re-scores those rows exactly.
 // ------------------------------------------------------------------------------------------
-constexpr int FP8_K = 128;            // elements per fp8 K step (the 128 bytes per row a 16-bit K step stages)
-constexpr int FP8_MAX_REFINE = KMAX;  // candidates per query: the batch kernel's list limit
+static_assert(FP8_MAX_REFINE == KMAX, "the refine pool is the batch kernel's list limit");
 
 __device__ __forceinline__ float bits_f32(uint16_t b, int is_bf16) {
   if (is_bf16) return __uint_as_float((uint32_t)b << 16);
@@ -1959,6 +1945,30 @@ __global__ __launch_bounds__(256) void fp8_rerank_kernel(const uint16_t* __restr
   if (tid >= nvalid && tid < k) { out_sc[q * k + tid] = -INFINITY; out_id[q * k + tid] = -1; }
 }
 
+int launch_quant_rows_fp8(const uint16_t* src, int ld, int is_bf16, int64_t n, uint8_t* dst, int ld8, hipStream_t stream) {
+  const int64_t tot = n * (ld8 / 4);
+  if (tot <= 0) return MRAG_OK;
+  hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, src, ld, is_bf16, n, dst, ld8);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
+
+int launch_quant_queries_fp8(const uint16_t* src, int ld, int is_bf16, int64_t n, uint8_t* dst, int ld8, hipStream_t stream) {
+  if (n <= 0) return MRAG_OK;
+  hipLaunchKernelGGL(quant_queries_fp8_kernel, dim3((unsigned)n), dim3(64), 0, stream, src, ld, is_bf16, dst, ld8);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
+
+int launch_fp8_rerank(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const int64_t* cand, int64_t nq, int refine,
+                      int k, int64_t id_base, float* out_sc, int64_t* out_id, hipStream_t stream) {
+  if (nq <= 0) return MRAG_OK;
+  hipLaunchKernelGGL(fp8_rerank_kernel, dim3((unsigned)nq), dim3(256), 0, stream, rows, queries, ld, is_bf16, cand, refine, k, id_base,
+                     out_sc, out_id);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
+
 struct BfIndex : Object {
   int dim = 0, ld = 0, metric = 0, dtype = MRAG_F16;
   int64_t n = 0, cap_rows = 0, id_base = 0;
@@ -2026,12 +2036,8 @@ static int grow_rows(BfIndex* ix, int64_t need_rows, hipStream_t stream) {
 
 // stored rows [r0, r0 + n) -> their fp8 copy
 static int quant_rows_fp8(BfIndex* ix, int64_t r0, int64_t n, hipStream_t stream) {
-  const int64_t tot = n * (ix->ld8 / 4);
-  if (tot <= 0) return MRAG_OK;
-  hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, ix->rows + (size_t)r0 * ix->ld,
-                     ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, n, ix->rows8 + (size_t)r0 * ix->ld8, ix->ld8);
-  MRAG_HIP(hipGetLastError());
-  return MRAG_OK;
+  return launch_quant_rows_fp8(ix->rows + (size_t)r0 * ix->ld, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, n, ix->rows8 + (size_t)r0 * ix->ld8,
+                               ix->ld8, stream);
 }
 
 // choose the corpus split count for T query tiles
@@ -2962,9 +2968,8 @@ int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_
     MRAG_TRY(s.prep_queries(queries, q_dtype, normalize, queries_is_device));
     const int64_t nq_pad = bf_query_rows(nq);   // prep_queries keeps qbuf rows [nq, nq_pad) zero: so are their fp8 rows
     MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
-    hipLaunchKernelGGL(quant_queries_fp8_kernel, dim3((unsigned)nq_pad), dim3(64), 0, s.stream, (const uint16_t*)ix->qbuf.p, ix->ld,
-                       ix->dtype == MRAG_BF16 ? 1 : 0, (uint8_t*)ix->qbuf8.p, ix->ld8);
-    MRAG_HIP(hipGetLastError());
+    MRAG_TRY(launch_quant_queries_fp8((const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, nq_pad, (uint8_t*)ix->qbuf8.p,
+                                      ix->ld8, s.stream));
     MRAG_TRY(ix->cand.ensure((size_t)nq * refine * 12));
     int64_t* c_id = (int64_t*)ix->cand.p;
     float* c_sc = (float*)(c_id + (size_t)nq * refine);
@@ -2976,9 +2981,8 @@ int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_
     a.id_base = 0;                   // local rows for the re-rank
     a.force_stream = stream_regime;
     MRAG_TRY(bf_launch(a));
-    hipLaunchKernelGGL(fp8_rerank_kernel, dim3((unsigned)nq), dim3(256), 0, s.stream, (const uint16_t*)ix->rows, (const uint16_t*)ix->qbuf.p,
-                       ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)c_id, refine, k, ix->id_base, s.d_sc, s.d_id);
-    MRAG_HIP(hipGetLastError());
+    MRAG_TRY(launch_fp8_rerank((const uint16_t*)ix->rows, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0,
+                               (const int64_t*)c_id, nq, refine, k, ix->id_base, s.d_sc, s.d_id, s.stream));
   }
   MRAG_TRY(s.end());
   ix->last_refine = refine;

@@ -68,6 +68,38 @@ int launch_prep_rows(const void* src, int src_dtype, int64_t n, int dim, void* d
 // with this dtype carries `ld` in 16-bit units (bytes per row / 2), so every stage and tile offset stays as it is.
 constexpr int MRAG_DT_FP8 = 16;
 
+#if defined(__HIPCC__)
+// The block-scaled 16x16x128 MFMA (2x the fp16 MFMA rate; the unscaled _fp8_fp8 forms run at the fp16 rate) with e4m3 A
+// and B (format 0) and neutral E8M0 scales (127 = 2^0), shared by the fp8 instances of the dense kernels (bf_index.hip) and
+// of the IVF list scan (ivf_scan.hip).  A 128-element K step is the 128 bytes per row a 16-bit K step stages, so the stage
+// layout and the two 16-byte fragment reads (k halves ph0 / ph1) stay; the two reads form one 32-byte operand.  Which k a
+// register byte stands for does not matter as long as A and B read alike.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+struct MfmaFp8 {
+  typedef i32x4 frag;
+  static __device__ __forceinline__ f32x4 run2(frag a0, frag a1, frag b0, frag b1, f32x4 c) {
+    const i32x8 a = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+    const i32x8 b = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+  }
+};
+#endif
+
+// The fp8 quantisers and the exact re-rank (bf_index.hip), shared by mrag_index_search_fp8 and mrag_ivf_search_fp8; all
+// pointers are device pointers.
+constexpr int FP8_K = 128;            // elements per fp8 K step (the 128 bytes per row a 16-bit K step stages)
+constexpr int FP8_MAX_REFINE = 64;    // candidates per query: the batch kernel's list limit
+// rows [0, n) of a 16-bit matrix (pitch ld) -> e4m3fn(clamp(256 x, +-448)) at pitch ld8 bytes, columns >= ld zero
+int launch_quant_rows_fp8(const uint16_t* src, int ld, int is_bf16, int64_t n, uint8_t* dst, int ld8, hipStream_t stream);
+// prepared query rows [0, n) -> e4m3fn(q * 2^e), max |q * 2^e| in [128, 256) per row; a zero row stays zero
+int launch_quant_queries_fp8(const uint16_t* src, int ld, int is_bf16, int64_t n, uint8_t* dst, int ld8, hipStream_t stream);
+// per query the fp32 dot products of its 16-bit row with the stored 16-bit rows cand[q][0 .. refine) (-1: none) -> the k
+// best, (score desc, row asc), ids = row + id_base, slots past the candidates (-inf, -1)
+int launch_fp8_rerank(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const int64_t* cand, int64_t nq, int refine,
+                      int k, int64_t id_base, float* out_sc, int64_t* out_id, hipStream_t stream);
+
 // One fused similarity + top-k pass (K2) and the candidate merge (K4) over PREPARED operands
 // (storage dtype, padded to `ld`, query buffer padded to a multiple of 256 rows).
 struct BfLaunch {

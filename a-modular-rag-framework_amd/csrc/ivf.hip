@@ -60,7 +60,15 @@ struct IvfIndex : Object {
   bool inv_valid = false;
   DevBuf excl;                    // int64 [nq] excluded rows of a host caller | int64 [nq] their stored positions
   DevBuf out_cnt;                 // int64 [nq] counts of a chunk with host outputs
+  // fp8 scan copy (mrag_ivf_enable_fp8): sorted8 [n_sorted][ld8] next to `sorted`, rebuilt with it by ivf_finalize
+  bool fp8 = false;
+  int ld8 = 0;
+  uint8_t* sorted8 = nullptr;
+  DevBuf qbuf8, cand;             // quantised queries [nq padded][ld8]; candidates of a chunk: int64 [nq][refine] local rows
+  int last_refine = -1;           // of the last mrag_ivf_search_fp8
   ~IvfIndex() override {
+    if (sorted8) (void)hipFree(sorted8);
+    qbuf8.release(); cand.release();
     inv_pos.release(); excl.release(); out_cnt.release();
     fw.release(); fstored.release(); flist.release(); flast.release();
     if (ev_lallow) (void)hipEventDestroy(ev_lallow);
@@ -85,6 +93,15 @@ __global__ void gather_rows_kernel(const uint16_t* __restrict__ src, const int64
   const uint4* sp = (const uint4*)(src + (size_t)(s < 0 ? 0 : s) * ld);
   uint4* dp = (uint4*)(dst + (size_t)r * ld);
   for (int i = lane; i < ld / 8; i += 64) dp[i] = s < 0 ? make_uint4(0, 0, 0, 0) : sp[i];
+}
+
+// fp8 bytes of the original rows [row0, row0 + n) (mrag_ivf_get_rows_fp8): out [n][dim] from the regrouped copy through inv
+__global__ void gather_rows8_kernel(const uint8_t* __restrict__ sorted8, int ld8, const int64_t* __restrict__ inv, int64_t row0,
+                                    int64_t n, int dim, uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * dim) return;
+  const int64_t r = i / dim;
+  out[i] = sorted8[(size_t)inv[row0 + r] * ld8 + (i - r * dim)];
 }
 
 // ---- search-time regrouping on the device: list -> the (query, probe) pairs that hit it -------------
@@ -408,6 +425,17 @@ static uint64_t splitmix64(uint64_t& s) {
   return z ^ (z >> 31);
 }
 
+// the fp8 copy of the regrouped rows: every byte of sorted8 [n_sorted][ld8] is written (pad rows of `sorted` are zero,
+// pad columns are zeroed by the kernel)
+static int ivf_build_sorted8(IvfIndex* ix, hipStream_t stream) {
+  if (ix->sorted8) (void)hipFree(ix->sorted8);
+  ix->sorted8 = nullptr;
+  const size_t bytes8 = (size_t)ix->n_sorted * ix->ld8;
+  hipError_t e = hipMalloc((void**)&ix->sorted8, bytes8);
+  if (e != hipSuccess) { (void)hipGetLastError(); ix->sorted8 = nullptr; return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for the fp8 rows failed: %s", bytes8, hipGetErrorString(e)); }
+  return launch_quant_rows_fp8(ix->sorted, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, ix->n_sorted, ix->sorted8, ix->ld8, stream);
+}
+
 // regroup rows by list: stable by original row, each list padded to a multiple of 256 rows
 static int ivf_finalize(IvfIndex* ix, hipStream_t stream) {
   if (!ix->dirty) return MRAG_OK;
@@ -427,18 +455,20 @@ static int ivf_finalize(IvfIndex* ix, hipStream_t stream) {
   for (int64_t i = 0; i < n; ++i) perm[cur[a[i]]++] = i;
   if (ix->sorted) (void)hipFree(ix->sorted);
   if (ix->row_ids) (void)hipFree(ix->row_ids);
-  ix->sorted = nullptr; ix->row_ids = nullptr;
+  if (ix->sorted8) (void)hipFree(ix->sorted8);
+  ix->sorted = nullptr; ix->row_ids = nullptr; ix->sorted8 = nullptr;
   MRAG_HIP(hipMalloc((void**)&ix->sorted, (size_t)ns * ix->ld * 2));
   MRAG_HIP(hipMalloc((void**)&ix->row_ids, (size_t)ns * 8));
   MRAG_HIP(hipMemcpyAsync(ix->row_ids, perm.data(), (size_t)ns * 8, hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, stream, ix->raw ? ix->raw : ix->sorted, ix->row_ids, ns, ix->ld, ix->sorted, 1);
   MRAG_HIP(hipGetLastError());
+  ix->n_sorted = ns;
+  if (ix->fp8) MRAG_TRY(ivf_build_sorted8(ix, stream));
   MRAG_TRY(ix->d_list_count.ensure((size_t)ix->nlist * 4));
   MRAG_TRY(ix->d_list_tile_lo.ensure((size_t)ix->nlist * 4));
   MRAG_HIP(hipMemcpyAsync(ix->d_list_count.p, ix->list_count.data(), (size_t)ix->nlist * 4, hipMemcpyHostToDevice, stream));
   MRAG_HIP(hipMemcpyAsync(ix->d_list_tile_lo.p, ix->list_tile_lo.data(), (size_t)ix->nlist * 4, hipMemcpyHostToDevice, stream));
   MRAG_HIP(hipStreamSynchronize(stream));
-  ix->n_sorted = ns;
   ix->max_list_rows = ix->list_count.empty() ? 0 : *std::max_element(ix->list_count.begin(), ix->list_count.end());
   ix->inv_valid = false;
   ix->dirty = false;
@@ -459,6 +489,7 @@ int mrag_ivf_create(int dim, int nlist, int metric, int storage_dtype, int devic
   MRAG_TRY(use_device(device));
   IvfIndex* ix = new IvfIndex();
   ix->kind = KIND_IVF; ix->device = device; ix->dim = dim; ix->ld = (int)round_up(dim, 64);
+  ix->ld8 = (int)round_up(dim, FP8_K);
   ix->nlist = nlist; ix->metric = metric; ix->dtype = storage_dtype;
   const size_t cb = (size_t)bf_round_rows(nlist) * ix->ld * 2;
   if (hipMalloc((void**)&ix->cen, cb) != hipSuccess) { delete ix; return fail(MRAG_ERR_OOM, "centroid allocation failed"); }
@@ -590,12 +621,14 @@ int mrag_ivf_add(mrag_handle h, const void* rows, int64_t n, int src_dtype, int 
   if (ix->n + n > 0x7FFFFF00ll) return fail(MRAG_ERR_UNSUPPORTED, "more than 2^31 rows per index; shard the corpus");
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
-  MRAG_TRY(ivf_grow(ix, ix->n + n, stream));
+  // the assignment below reads the new rows in place as a prepared query buffer: whole 256-row tiles + 16 rows from `dst` on,
+  // wherever the stored rows end (not on a tile boundary after an add of any other size), so the capacity covers that read
+  MRAG_TRY(ivf_grow(ix, ix->n + bf_query_rows(n), stream));
   uint16_t* dst = ix->raw + (size_t)ix->n * ix->ld;
   MRAG_TRY(ivf_prepare(ix, rows, n, src_dtype, normalize, rows_is_device, dst, stream));
   MRAG_TRY(ix->tmp_id.ensure((size_t)n * 8));
   MRAG_TRY(ix->tmp_sc.ensure((size_t)n * 4));
-  // (the raw buffer is a multiple of 256 rows and zero beyond n: safe to read as padded queries)
+  // (the raw buffer is zero beyond the stored rows and holds bf_query_rows(n) rows from dst on: safe to read as padded queries)
   MRAG_TRY(ivf_assign_rows(ix, dst, n, (int64_t*)ix->tmp_id.p, (float*)ix->tmp_sc.p, stream));
   hipLaunchKernelGGL(ids_to_i32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, n, ix->assign + ix->n);
   MRAG_HIP(hipGetLastError());
@@ -688,16 +721,21 @@ struct IvfRangeArgs {
   bool stored_rows = false;
 };
 
-static int ivf_range_unsupported(const char* why) {
-  return fail(MRAG_ERR_UNSUPPORTED, "IVF range search runs in the score-segment regime only: %s", why);
+static int ivf_segments_only(const char* what, const char* why) {
+  return fail(MRAG_ERR_UNSUPPORTED, "IVF %s search runs in the score-segment regime only: %s", what, why);
 }
+static int ivf_range_unsupported(const char* why) { return ivf_segments_only("range", why); }
 
 // one chunk of a search (<= 2^20 queries whose score segments fit the buffer): probe selection, plan, list scan, selection
 // live_bits / stored_bits (filtered search, path P): probe only live lists, select only allowed stored positions
 // rg (range search): the selection lists and counts the rows >= rg->floor (pointers already moved to this chunk's queries)
+// fp8_refine > 0 (fp8 search): the scan runs over the fp8 copies of rows and queries, the selection keeps the top
+// fp8_refine local rows per query, and those are re-scored against the 16-bit rows in arrival order for the k best
 static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
                             int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx,
-                            const uint32_t* live_bits, const uint32_t* stored_bits, const IvfRangeArgs* rg = nullptr) {
+                            const uint32_t* live_bits, const uint32_t* stored_bits, const IvfRangeArgs* rg = nullptr, int fp8_refine = 0) {
+  const bool f8 = fp8_refine > 0;
+  const char* seg_what = f8 ? "fp8" : "range";
   hipEvent_t ev_scan0 = ix->cev[2 * chunk_idx], ev_scan1 = ix->cev[2 * chunk_idx + 1];
   unsigned long long* d_stats = (unsigned long long*)ix->stats.p;
 
@@ -716,6 +754,13 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     MRAG_HIP(hipMemcpyAsync(ix->qbuf.p, queries, (size_t)nq * ix->ld * 2, hipMemcpyDeviceToDevice, stream));
   } else {
     MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
+  }
+  if (f8) {   // (qbuf rows [nq, nq_pad) are zero, the scan's pad row nq among them: so are their fp8 rows)
+    const int64_t nq_pad = bf_query_rows(nq);
+    MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
+    MRAG_TRY(launch_quant_queries_fp8((const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, nq_pad, (uint8_t*)ix->qbuf8.p,
+                                      ix->ld8, stream));
+    MRAG_TRY(ix->cand.ensure((size_t)nq * fp8_refine * 8));
   }
   MRAG_TRY(ix->tmp_id.ensure((size_t)nq * nprobe * 8));
   MRAG_TRY(ix->tmp_sc.ensure((size_t)nq * nprobe * 4));
@@ -767,7 +812,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     hipLaunchKernelGGL(ivf_count_kernel, dim3(pgrid), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs,
                        (const int*)ix->d_list_count.p, d_lcount);
   bool use_scores = scores_cap > 0 && nprobe <= 256;   // (the select kernel holds <= 256 segments per query; exhaustive probing takes the fused path)
-  if (rg && !use_scores) return ivf_range_unsupported(scores_cap > 0 ? "more than 256 probed lists per query" : "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
+  if ((rg || f8) && !use_scores) return ivf_segments_only(seg_what, scores_cap > 0 ? "more than 256 probed lists per query" : "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
   // Score floats of this search: known exactly only on the device (sum over the probed lists of queries x rows).  When
   // even the bound "every pair probes the longest list" fits the buffer, nothing comes back to the host at all: the
   // scan is launched over the BOUND of the workgroup count and reads the real one from device memory.
@@ -788,7 +833,7 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
       MRAG_HIP(hipStreamSynchronize(stream));
       const int64_t floats = (int64_t)(uint32_t)plan_out[1] | ((int64_t)plan_out[2] << 32);
       if (plan_out[0] < 0 || plan_out[0] > desc_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", plan_out[0], (long long)desc_bound);
-      if (floats * 4 > scores_cap && rg) return ivf_range_unsupported("the score segments of one chunk exceed the score buffer (MRAG_IVF_SCORES_MB)");
+      if (floats * 4 > scores_cap && (rg || f8)) return ivf_segments_only(seg_what, "the score segments of one chunk exceed the score buffer (MRAG_IVF_SCORES_MB)");
       if (floats * 4 > scores_cap) use_scores = false;
       else MRAG_TRY(ix->scores.ensure((size_t)std::max<int64_t>(floats, 4) * 4));
     }
@@ -804,14 +849,21 @@ static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q
     MRAG_HIP(hipEventRecord(ev_scan0, stream));
     // (no_sync: the workgroup count stays on the device, the grid is its bound)
     if (!no_sync) n_wg = plan_out[0];
-    MRAG_TRY(ivfs_scan(ix->sorted, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype, nq, (const int*)ix->desc.p,
+    MRAG_TRY(ivfs_scan(f8 ? (const uint16_t*)ix->sorted8 : ix->sorted, (const uint16_t*)(f8 ? ix->qbuf8.p : ix->qbuf.p),
+                       f8 ? ix->ld8 / 2 : ix->ld, f8 ? MRAG_DT_FP8 : ix->dtype, nq, (const int*)ix->desc.p,
                        no_sync ? (int)desc_bound : n_wg, no_sync ? d_nwg : nullptr, (const int64_t*)ix->gq.p, (float*)ix->scores.p,
                        stream));
     IvfsRange sel_range{0.f, nullptr, nullptr};
     if (rg) sel_range = IvfsRange{rg->floor, rg->excl_pos, d_cnt};
-    MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
-                               stored_bits, rg ? &sel_range : nullptr));
+    if (f8)   // candidates: local rows in (fp8 score desc, row asc) order, -1 past the rows of the probed lists
+      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, fp8_refine, ix->row_ids, 0, nullptr, (int64_t*)ix->cand.p, stream));
+    else
+      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
+                                 stored_bits, rg ? &sel_range : nullptr));
     MRAG_HIP(hipEventRecord(ev_scan1, stream));
+    if (f8)
+      MRAG_TRY(launch_fp8_rerank(ix->raw, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)ix->cand.p, nq,
+                                 fp8_refine, k, ix->id_base, d_sc, d_id, stream));
   } else {
     MRAG_HIP(hipMemsetAsync(ix->gq.p, 0xFF, (size_t)wg_bound * 256 * 8, stream));   // (the gather below reads whole 256-slot slabs)
     hipLaunchKernelGGL(ivf_plan_kernel, dim3(1), dim3(1024), 0, stream, (const int*)d_lcount, (const int*)ix->d_list_count.p,
@@ -863,7 +915,8 @@ static int ivf_grow_cev(IvfIndex* ix, int n_chunks) {
 // the chunks of a search of nq queries, chunk queries each, one after another (live_bits / stored_bits: as ivf_search_chunk)
 static int ivf_run_chunks(IvfIndex* ix, const void* queries, int64_t nq, int64_t chunk, int q_dtype, int normalize, int queries_is_device,
                           int nprobe, int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream,
-                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr, const IvfRangeArgs* rg = nullptr) {
+                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr, const IvfRangeArgs* rg = nullptr,
+                          int fp8_refine = 0) {
   const int n_chunks = (int)((nq + chunk - 1) / chunk);
   MRAG_TRY(ivf_grow_cev(ix, n_chunks));
   const size_t qrow = rg && rg->stored_rows ? (size_t)ix->ld * 2 : (size_t)ix->dim * esize(q_dtype);
@@ -873,7 +926,7 @@ static int ivf_run_chunks(IvfIndex* ix, const void* queries, int64_t nq, int64_t
     if (rg) { crg = *rg; if (crg.excl_pos) crg.excl_pos += off; crg.out_counts += off; }
     MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, m, q_dtype, normalize, queries_is_device, nprobe, k,
                               out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c, live_bits, stored_bits,
-                              rg ? &crg : nullptr));
+                              rg ? &crg : nullptr, fp8_refine));
   }
   ix->n_chunks = n_chunks;
   return MRAG_OK;
@@ -937,6 +990,17 @@ int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype,
 
 namespace mrag {
 
+// inv_pos = original row -> stored position of the current regroup (built once after every regroup)
+static int ivf_ensure_inv_pos(IvfIndex* ix, hipStream_t stream) {
+  if (ix->inv_valid) return MRAG_OK;
+  MRAG_TRY(ix->inv_pos.ensure((size_t)std::max<int64_t>(ix->n, 1) * 8));
+  hipLaunchKernelGGL(ivf_inverse_pos_kernel, dim3((unsigned)((ix->n_sorted + 255) / 256)), dim3(256), 0, stream,
+                     (const int64_t*)ix->row_ids, ix->n_sorted, ix->n, (int64_t*)ix->inv_pos.p);
+  MRAG_HIP(hipGetLastError());
+  ix->inv_valid = true;
+  return MRAG_OK;
+}
+
 // ---- range search ---------------------------------------------------------------------------------------------------------
 // What mrag_ivf_search_range and mrag_ivf_self_join share once their arguments are checked and ivf_search_begin has run:
 // the refusals known before any chunk runs, the excluded rows as stored positions (rows: device int64 [nq], or NULL with
@@ -952,13 +1016,7 @@ static int ivf_range_run(IvfIndex* ix, const void* queries, int64_t nq, int q_dt
   IvfRangeArgs rg;
   rg.floor = floor; rg.out_counts = out_counts; rg.stored_rows = self_row0 >= 0;
   if (d_excl_rows || self_row0 >= 0) {
-    if (!ix->inv_valid) {
-      MRAG_TRY(ix->inv_pos.ensure((size_t)std::max<int64_t>(ix->n, 1) * 8));
-      hipLaunchKernelGGL(ivf_inverse_pos_kernel, dim3((unsigned)((ix->n_sorted + 255) / 256)), dim3(256), 0, stream,
-                         (const int64_t*)ix->row_ids, ix->n_sorted, ix->n, (int64_t*)ix->inv_pos.p);
-      MRAG_HIP(hipGetLastError());
-      ix->inv_valid = true;
-    }
+    MRAG_TRY(ivf_ensure_inv_pos(ix, stream));
     int64_t* d_pos = (int64_t*)ix->excl.p + nq;
     hipLaunchKernelGGL(ivf_excl_pos_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_excl_rows, self_row0, nq, ix->n,
                        (const int64_t*)ix->inv_pos.p, d_pos);
@@ -1212,6 +1270,92 @@ int mrag_ivf_last_filter(mrag_handle h, int* out_path, int64_t* out_allowed, int
   if (out_path) *out_path = ix->last_fpath;
   if (out_allowed) *out_allowed = ix->last_fallowed;
   if (out_live_lists) *out_live_lists = ix->last_flive;
+  return MRAG_OK;
+}
+
+// ---- fp8 scan copy + exact re-rank (contract in include/mrag.h) ---------------------------------------------------
+int mrag_ivf_enable_fp8(mrag_handle h) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->metric != MRAG_METRIC_COSINE) return fail(MRAG_ERR_INVALID, "the fp8 scan copy serves cosine indexes only");
+  if (ix->fp8) return MRAG_OK;
+  MRAG_TRY(use_device(ix->device));
+  ix->fp8 = true;
+  if (ix->n > 0) {
+    // rows already stored (adds and searches on any stream): settle them, build the copy on the null stream -- with the
+    // regroup when that is due anyway --, finish it here (a one-off)
+    int st = hipDeviceSynchronize() == hipSuccess ? MRAG_OK : fail(MRAG_ERR_HIP, "hipDeviceSynchronize failed");
+    if (st == MRAG_OK) st = ix->dirty ? ivf_finalize(ix, nullptr) : ivf_build_sorted8(ix, nullptr);
+    if (st == MRAG_OK && hipStreamSynchronize(nullptr) != hipSuccess) st = fail(MRAG_ERR_HIP, "building the fp8 rows failed");
+    if (st != MRAG_OK) { ix->fp8 = false; return st; }
+  }
+  return MRAG_OK;
+}
+
+int mrag_ivf_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (!ix->fp8) return fail(MRAG_ERR_INVALID, "no fp8 scan copy (mrag_ivf_enable_fp8)");
+  if (row0 < 0 || n < 0 || row0 + n > ix->n) return fail(MRAG_ERR_INVALID, "row range [%lld,%lld) outside [0,%lld)", (long long)row0, (long long)(row0 + n), (long long)ix->n);
+  if (n == 0) return MRAG_OK;
+  if (!out) return fail(MRAG_ERR_INVALID, "out is NULL");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  MRAG_TRY(ivf_finalize(ix, stream));
+  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  MRAG_TRY(ivf_ensure_inv_pos(ix, stream));
+  const int64_t tot = n * ix->dim;
+  uint8_t* d_out = out;
+  DevBuf tmp;
+  if (!out_is_device) { MRAG_TRY(tmp.ensure((size_t)tot)); d_out = (uint8_t*)tmp.p; }
+  hipLaunchKernelGGL(gather_rows8_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const uint8_t*)ix->sorted8, ix->ld8,
+                     (const int64_t*)ix->inv_pos.p, row0, n, ix->dim, d_out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && !out_is_device) e = hipMemcpyAsync(out, d_out, (size_t)tot, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && !out_is_device) e = hipStreamSynchronize(stream);
+  tmp.release();
+  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "reading the fp8 rows failed: %s", hipGetErrorString(e));
+  // (inv_pos is in use on `stream` until here: a later search on another stream waits for it)
+  ix->timed = false;
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->end_recorded = true;
+  return MRAG_OK;
+}
+
+int mrag_ivf_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
+                        int k, int refine, float* out_scores, int64_t* out_ids, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (!ix->fp8) return fail(MRAG_ERR_INVALID, "no fp8 scan copy on this index (mrag_ivf_enable_fp8)");
+  if (nq < 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / nprobe");
+  if (k < 1 || k > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "fp8 search serves 1 <= k <= %d, got %d", FP8_MAX_REFINE, k);
+  if (refine == 0) MRAG_TRY(mrag_index_fp8_default_refine(k, &refine));
+  if (refine < k || refine > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "refine = %d outside k..%d (k = %d)", refine, FP8_MAX_REFINE, k);
+  hipStream_t stream = (hipStream_t)stream_;
+  int64_t chunk = 0;
+  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  if (nq == 0) return MRAG_OK;
+  // the refusals known before any chunk runs
+  if (ivf_scores_cap() <= 0) return ivf_segments_only("fp8", "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
+  if (nprobe > 256) return ivf_segments_only("fp8", "more than 256 probed lists per query (exhaustive probing with nlist > 256)");
+  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+  MRAG_TRY(ix->stats.ensure(16));
+  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
+  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device, stream,
+                          nullptr, nullptr, nullptr, refine));
+  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
+  ix->end_recorded = true;
+  ix->timed = true;
+  ix->last_refine = refine;
+  if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_ivf_last_fp8(mrag_handle h, int* out_refine) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_refine < 0) return fail(MRAG_ERR_INVALID, "no completed fp8 search on this index");
+  if (out_refine) *out_refine = ix->last_refine;
   return MRAG_OK;
 }
 

@@ -44,6 +44,8 @@ template <> struct SMfma<MRAG_BF16> {
   typedef s_bf16x8 frag;
   static __device__ __forceinline__ s_f32x4 run(frag a, frag b, s_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 };
+// fp8 scan copy (mrag_ivf_search_fp8): the block-scaled 16x16x128 form, one MFMA per two 16-byte fragment reads (common.h)
+template <> struct SMfma<MRAG_DT_FP8> : MfmaFp8 {};
 
 __device__ __forceinline__ uint32_t s_f32_ord(float f) {          // order-preserving fp32 -> uint32
   const uint32_t u = __float_as_uint(f);
@@ -62,6 +64,9 @@ constexpr int S_STAGE = 2 * S_A_BYTES;          // 32 KiB
 // stamps show 1.85 us per K step per workgroup with two workgroups per CU = 35 GB/s per CU of L2 -> LDS traffic, the
 // same request-side bound as the fused kernel's stream.  What pays is not fetching padding: a workgroup
 // loads and multiplies only the 8-row chunks / 16-row fragments that hold real rows and real queries.
+// DT = MRAG_DT_FP8: corpus / queries are e4m3fn rows of 2 * ld bytes (ld in 16-bit units, as everywhere here).  A K step
+// stages the same 128 bytes per row -- 128 elements instead of 64, so half the steps and barriers --, and the two 16-byte
+// fragment reads of a step are ONE 32-byte operand of one block-scaled MFMA per (i, j) instead of one MFMA each.
 template <int DT>
 __global__ __launch_bounds__(STHR) void ivfs_scan_kernel(const uint16_t* __restrict__ corpus, const uint16_t* __restrict__ queries,
                                                          int ld, int64_t zero_row, const int* __restrict__ desc, int n_desc,
@@ -155,19 +160,35 @@ __global__ __launch_bounds__(STHR) void ivfs_scan_kernel(const uint16_t* __restr
     const int ni = min(4, (n_rows - tile * ST - wm * 64 + 15) >> 4);
     const int nj = min(4, (nq_local - wn * 64 + 15) >> 4);
     if (ni > 0 && nj > 0) {
+      if constexpr (DT == MRAG_DT_FP8) {   // one 16x16x128 MFMA per (i, j): the two k halves are one 32-byte operand
+        const int ph1 = ph0 ^ 64;
+        frag a0[4], a1[4], b0[4], b1[4];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int ph = ks ? (ph0 ^ 64) : ph0;
-        frag af[4], bf[4];
+        for (int i = 0; i < 4; ++i)
+          if (i < ni) { a0[i] = *(const frag*)(sb + a_rd + i * 2048 + ph0); a1[i] = *(const frag*)(sb + a_rd + i * 2048 + ph1); }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) if (i < ni) af[i] = *(const frag*)(sb + a_rd + i * 2048 + ph);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (j < nj) bf[j] = *(const frag*)(sb + b_rd + j * 2048 + ph);
+        for (int j = 0; j < 4; ++j)
+          if (j < nj) { b0[j] = *(const frag*)(sb + b_rd + j * 2048 + ph0); b1[j] = *(const frag*)(sb + b_rd + j * 2048 + ph1); }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (i < ni && j < nj) acc[i][j] = SMfma<DT>::run(af[i], bf[j], acc[i][j]);
+            if (i < ni && j < nj) acc[i][j] = SMfma<DT>::run2(a0[i], a1[i], b0[j], b1[j], acc[i][j]);
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int ph = ks ? (ph0 ^ 64) : ph0;
+          frag af[4], bf[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (i < ni) af[i] = *(const frag*)(sb + a_rd + i * 2048 + ph);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) if (j < nj) bf[j] = *(const frag*)(sb + b_rd + j * 2048 + ph);
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (i < ni && j < nj) acc[i][j] = SMfma<DT>::run(af[i], bf[j], acc[i][j]);
+        }
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's fragment reads of `buf` are done before it reaches the next barrier
@@ -611,6 +632,7 @@ int ivfs_scan(const uint16_t* corpus, const uint16_t* queries, int ld, int dtype
   // persistent grid: two workgroups per CU (whole XCD rounds), never more than the descriptors need
   const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(n_desc + 7) / 8 * 8, (int64_t)cus * 2 / 8 * 8);
   if (dtype == MRAG_F16) hipLaunchKernelGGL((ivfs_scan_kernel<MRAG_F16>), dim3(grid), dim3(STHR), 0, stream, corpus, queries, ld, zero_row, desc, n_desc, n_desc_dev, gq, S);
+  else if (dtype == MRAG_DT_FP8) hipLaunchKernelGGL((ivfs_scan_kernel<MRAG_DT_FP8>), dim3(grid), dim3(STHR), 0, stream, corpus, queries, ld, zero_row, desc, n_desc, n_desc_dev, gq, S);
   else hipLaunchKernelGGL((ivfs_scan_kernel<MRAG_BF16>), dim3(grid), dim3(STHR), 0, stream, corpus, queries, ld, zero_row, desc, n_desc, n_desc_dev, gq, S);
   MRAG_HIP(hipGetLastError());
   return MRAG_OK;

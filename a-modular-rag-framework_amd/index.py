@@ -124,6 +124,22 @@ def fp8_default_refine(k: int) -> int:
     return out.value
 
 
+def _check_precision(precision, refine, allow) -> Tuple[bool, int]:
+    """The ``precision`` / ``refine`` arguments of a search, checked before any library call -> (fp8, refine for the ABI:
+    0 = the default pool)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    if precision == "fp8" and allow is not None:
+        raise ValueError("precision='fp8' does not combine with allow= (filtered search is exact only)")
+    if refine is not None and precision != "fp8":
+        raise ValueError("refine applies to precision='fp8' only")
+    fp8 = precision == "fp8"
+    r = 0 if refine is None else int(refine)
+    if fp8 and r < 0:
+        raise ValueError(f"refine must be positive, got {refine}")
+    return fp8, r
+
+
 def range_floor(min_score) -> np.float32:
     """The fp32 floor a range search compares against: the smallest float32 >= ``min_score`` (so that "score >= floor"
     on the fp32 scores means "score >= min_score").  NaN, +-inf and values beyond the float32 range raise ``ValueError``."""
@@ -266,20 +282,11 @@ class DenseIndex:
         ``refine`` best rows per query (``k <= refine <= 64``; None: :func:`fp8_default_refine`) from the fp8 copy and
         re-scores them exactly against the 16-bit rows: the scores are exact, the row set is approximate (measured
         recall in DESIGN.md).  It does not combine with ``allow``."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
-        if precision == "fp8" and allow is not None:
-            raise ValueError("precision='fp8' does not combine with allow= (filtered search is exact only)")
-        if refine is not None and precision != "fp8":
-            raise ValueError("refine applies to precision='fp8' only")
+        fp8, r = _check_precision(precision, refine, allow)
         if normalize is None:
             normalize = self.metric == "cosine"
         if allow is not None:
             return self._search_filtered(queries, k, normalize, stream, out, allow, filter_path)
-        fp8 = precision == "fp8"
-        r = 0 if refine is None else int(refine)
-        if fp8 and r < 0:
-            raise ValueError(f"refine must be positive, got {refine}")
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         norm = int(bool(normalize))
         if fp8:
@@ -560,7 +567,8 @@ class IVFFlatIndex:
     search probes the ``nprobe`` best lists and scans them exactly.  Same id / tie-break
     conventions as :class:`DenseIndex`."""
 
-    def __init__(self, dim: int, nlist: int, metric: str = "cosine", dtype: str = "f16", device: int = 0):
+    def __init__(self, dim: int, nlist: int, metric: str = "cosine", dtype: str = "f16", device: int = 0,
+                 fp8_scan: bool = False):
         self._lib = N.load()
         self.dim, self.nlist, self.metric, self.dtype, self.device = int(dim), int(nlist), metric, dtype, int(device)
         h = C.c_uint64(0)
@@ -568,6 +576,28 @@ class IVFFlatIndex:
                                           N.MRAG_F16 if dtype == "f16" else N.MRAG_BF16, self.device, C.byref(h)))
         self._h = h
         self.id_base = 0
+        if fp8_scan:
+            self.enable_fp8()
+
+    def enable_fp8(self):
+        """Keep an fp8 (e4m3fn) copy of the regrouped rows for ``search(precision="fp8")`` (``mrag_ivf_enable_fp8``):
+        built from the rows already stored, then rebuilt with every regroup (the first search after an add).  Costs
+        ``round_up(dim, 128)`` bytes per stored position.  Cosine indexes only; idempotent."""
+        N.check(self._lib.mrag_ivf_enable_fp8(self._h))
+
+    def rows_fp8(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The fp8 copy of the original rows ``[row0, row0 + n)``, in insertion order, as raw e4m3fn bytes
+        ([n, dim] uint8); regroups first when rows were added since the last search."""
+        n = len(self) - row0 if n is None else n
+        out = np.empty((n, self.dim), dtype=np.uint8)
+        N.check(self._lib.mrag_ivf_get_rows_fp8(self._h, int(row0), int(n), out.ctypes.data, 0, None))
+        return out
+
+    def last_fp8(self) -> dict:
+        """Refine pool of the last fp8 search on this index (``mrag_ivf_last_fp8``): ``{"refine": r}``."""
+        r = C.c_int(0)
+        N.check(self._lib.mrag_ivf_last_fp8(self._h, C.byref(r)))
+        return {"refine": r.value}
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -624,10 +654,11 @@ class IVFFlatIndex:
         return {"scan_ms": g.value, "total_ms": t.value, "scanned_rows": rows.value, "n_wg": nwg.value}
 
     def search(self, queries, k: int, nprobe: int, normalize: Optional[bool] = None, allow=None, filter_path: str = "auto",
-               list_allowed=None, stream=None):
+               list_allowed=None, stream=None, precision: str = "exact", refine: Optional[int] = None, out=None):
         """-> (scores [nq,k], ids [nq,k]); host queries give numpy arrays (complete on return), CUDA tensors give CUDA
-        tensors filled asynchronously on ``stream`` (default: the current torch stream), like any torch op.  ``nprobe``:
-        1..256, or ``nlist`` (exhaustive).
+        tensors filled asynchronously on ``stream`` (default: the current torch stream), like any torch op;
+        ``out=(scores, ids)`` reuses caller tensors of a plain or fp8 search.  ``nprobe``: 1..256, or ``nlist``
+        (exhaustive).
 
         ``allow`` restricts the search to some rows (``mrag_ivf_search_filtered``), in the forms
         :meth:`DenseIndex.search` takes: a bool / uint8 mask over the ``len(self)`` local rows (numpy, or a torch tensor
@@ -635,15 +666,25 @@ class IVFFlatIndex:
         probes its ``nprobe`` best lists among those holding an allowed row), "exact" (filtered brute force) or "auto".
         ``list_allowed``: allowed rows per list (int32 [nlist], on the host for a host ``allow``, on the device for a
         device one) deciding which lists are live instead of this index's own counts (sharded search: the global
-        counts).  See :meth:`last_filter`."""
+        counts).  See :meth:`last_filter`.
+
+        ``precision="fp8"`` (index built with ``fp8_scan=True`` or :meth:`enable_fp8`; ``1 <= k <= 64``, at most 256
+        probed lists): the same lists are probed, their rows are scanned in the fp8 copy, and the ``refine`` best rows per
+        query (``k <= refine <= 64``; None: :func:`fp8_default_refine`) are re-scored exactly against the 16-bit rows.
+        The scores are exact, the row set is approximate (measured recall in DESIGN.md); a query whose probed lists hold
+        at most ``refine`` rows gets the exact search's answer.  It does not combine with ``allow``."""
+        fp8, r = _check_precision(precision, refine, allow)
         if allow is not None:
             return self._search_filtered(queries, k, nprobe, normalize, allow, filter_path, list_allowed, stream)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         norm = self._norm(normalize)
-
-        def call(sc, ids, out_dev, st):
-            return self._lib.mrag_ivf_search(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), sc, ids, out_dev, st)
-        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev))
+        if fp8:
+            def call(sc, ids, out_dev, st):
+                return self._lib.mrag_ivf_search_fp8(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), r, sc, ids, out_dev, st)
+        else:
+            def call(sc, ids, out_dev, st):
+                return self._lib.mrag_ivf_search(self._h, ptr, nq, dt, norm, is_dev, int(nprobe), int(k), sc, ids, out_dev, st)
+        return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev), out)
 
     @staticmethod
     def _check_nprobe(nprobe) -> int:

@@ -22,7 +22,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .index import pack_partial_device, topk_merge, topk_merge_packed_device
+from .index import _check_precision, pack_partial_device, topk_merge, topk_merge_packed_device
 
 
 def shard_bounds(n_total: int, world: int, rank: int) -> Tuple[int, int]:
@@ -409,16 +409,17 @@ class ShardedIVFIndex(_Sharded):
     GPU; tests inject a CPU searcher to exercise the exchange on ``gloo``.  A filtered search also calls it with
     ``allow=`` (local mask), ``filter_path=`` ("probe" / "exact") and ``list_allowed=`` (global per-list counts), and
     ``local_list_counts(local_mask) -> int [nlist]`` (default: :meth:`IVFFlatIndex.allowed_per_list`) is injectable the
-    same way."""
+    same way.  ``fp8_scan=True`` gives the local index its fp8 copy, so that ``search(..., precision="fp8", refine=...)``
+    (passed through to the local search as ``precision=`` / ``refine=``) runs the fp8 scan per shard."""
 
     def __init__(self, dim: int, nlist: int, n_total: int, rank: int, world: int, device: int = 0, group=None,
                  dtype: str = "f16", metric: str = "cosine", local_search: Optional[Callable] = None,
-                 local_list_counts: Optional[Callable] = None):
+                 local_list_counts: Optional[Callable] = None, fp8_scan: bool = False):
         super().__init__(n_total, rank, world, group)
         self.dim, self.nlist = dim, nlist
         if local_search is None:
             from .index import IVFFlatIndex
-            self.index = IVFFlatIndex(dim, nlist, metric=metric, dtype=dtype, device=device)
+            self.index = IVFFlatIndex(dim, nlist, metric=metric, dtype=dtype, device=device, fp8_scan=fp8_scan)
             self.index.set_id_base(self.lo)
             local_search = self.index.search
             if local_list_counts is None:
@@ -459,13 +460,19 @@ class ShardedIVFIndex(_Sharded):
         return t.cpu().numpy().astype(np.int32)
 
     def search(self, queries, k: int, nprobe: int, nthreads: int = 0, merge: str = "auto",
-               force_collective: bool = False, allow=None, filter_path: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
+               force_collective: bool = False, allow=None, filter_path: str = "auto", precision: str = "exact",
+               refine: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Local search over this rank's rows, then the exchange + merge; every rank returns the full result.
         ``allow`` (global rows: a mask over ``n_total`` or global row positions) restricts the search to those rows,
         with the semantics of :meth:`IVFFlatIndex.search`: every rank takes its slice, the per-list allowed counts are
         summed over the ranks so that all ranks agree on the live lists, and the path ("auto": decided once, from the
-        global counts) is passed explicitly to every rank.  Result = the single-index filtered result."""
-        kw = {}
+        global counts) is passed explicitly to every rank.  Result = the single-index filtered result.
+        ``precision="fp8"`` / ``refine`` (see :meth:`IVFFlatIndex.search`; not with ``allow``) go to the local search
+        unchanged: every rank picks and re-ranks the ``refine`` candidates of its OWN rows, and the exchange merges the
+        exact-scored results.  The ranks together re-rank up to ``world x refine`` candidates per query, so a multi-rank
+        answer can only contain more true neighbours than the one-index fp8 answer; it is not identical to it."""
+        fp8, _ = _check_precision(precision, refine, allow)
+        kw = dict(precision=precision, refine=refine) if fp8 else {}
         if allow is not None:
             from .index import IVF_FILTER_PATHS, ivf_choose_filter_path
             if filter_path not in IVF_FILTER_PATHS:

@@ -294,10 +294,37 @@ int mrag_ivf_search_range(mrag_handle h, const void* queries, int64_t nq, int q_
  * buffers [n][k], [n][k], [n]; asynchronous on `stream`.  Limits and refusals as mrag_ivf_search_range. */
 int mrag_ivf_self_join(mrag_handle h, int64_t row0, int64_t n, int nprobe, int k, float min_score,
                        float* out_scores, int64_t* out_ids, int64_t* out_counts, void* stream);
+/* fp8 scan copy + exact re-rank over the probed lists (cosine indexes): the contract of mrag_index_search_fp8, applied to
+ * the rows of the probed lists.  mrag_ivf_enable_fp8 keeps, next to the regrouped 16-bit rows the list scan streams, an OCP
+ * e4m3fn copy [stored positions][ld8], ld8 = dim rounded up to 128: byte = e4m3fn(clamp(256 * x, -448, 448)), x the STORED
+ * 16-bit value, rounded to nearest even; pad rows and pad columns are 0.  It is rebuilt wherever the rows are regrouped (the
+ * first search after an add), and built once by the call itself when rows are already there (the call synchronises the
+ * device; idempotent); it costs ld8 bytes per stored position.  A non-cosine index gets MRAG_ERR_INVALID.
+ * mrag_ivf_search_fp8: 1 <= k <= 64 and k <= refine <= 64 (refine = 0: mrag_index_fp8_default_refine(k)); anything else, or
+ * an index without the copy, is MRAG_ERR_INVALID.  Probe selection is that of mrag_ivf_search (16-bit centroids): the same
+ * lists are probed.  Each query is prepared as in mrag_ivf_search and quantised with its own power of two 2^e, max
+ * |q * 2^e| in [128, 256) (a zero query stays zero).  The top-`refine` rows of the query's probed lists by fp8 score
+ * (block-scaled MFMA, fp32 accumulation) are the candidates; each is re-scored as the fp32 dot product of the prepared
+ * 16-bit query with the stored 16-bit row.  Output: the k best by that score, (score desc, original row asc), ids = row +
+ * id_base; slots past the candidates are (-inf, -1).  Returned scores are never fp8 scores; the result is approximate only
+ * in WHICH rows are returned, and equals mrag_ivf_search's (up to fp32 summation order) when a query's probed lists hold
+ * at most `refine` rows.  The search runs in the score-segment regime only: with more than 256 probed lists per query
+ * (nprobe = nlist > 256), with MRAG_IVF_SCORES_MB = 0, or when the score segments of one chunk exceed the score buffer it
+ * returns MRAG_ERR_UNSUPPORTED and writes no answer.  There is no allow-set form and no range form.  Batches are cut into
+ * chunks as in mrag_ivf_search; sync behaviour as there (device queries and device outputs: asynchronous on `stream`).
+ * mrag_ivf_get_rows_fp8: fp8 bytes of the original rows [row0, row0 + n), in insertion order, as [n, dim] uint8, read from
+ * the regrouped copy through the row -> position map (regroups first if rows were added; for the tests).
+ * mrag_ivf_last_fp8: refine of the last fp8 search on the handle. */
+int mrag_ivf_enable_fp8(mrag_handle h);
+int mrag_ivf_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, int out_is_device, void* stream);
+int mrag_ivf_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                        int nprobe, int k, int refine, float* out_scores, int64_t* out_ids, int out_is_device, void* stream);
+int mrag_ivf_last_fp8(mrag_handle h, int* out_refine);
 /* measurement hooks for bench.py (like mrag_index_last_timing): device ms of the list scan (scan + per-query selection kernels, or the fused kernel) and of the
- * whole LAST mrag_ivf_search, mrag_ivf_search_filtered, mrag_ivf_search_range or mrag_ivf_self_join (hipEvents on its stream; filtered: the list scan + selection on
- * path P, the search kernel on path E), the rows that scan streamed (sum over its
- * workgroups of their list's length: x ld x 2 = the algorithmic HBM bytes) and its workgroup count. */
+ * whole LAST mrag_ivf_search, mrag_ivf_search_filtered, mrag_ivf_search_range, mrag_ivf_self_join or mrag_ivf_search_fp8 (hipEvents on its stream; filtered: the
+ * list scan + selection on path P, the search kernel on path E; fp8: the fp8 scan + the candidate selection, the total covers the query quantisation and the
+ * re-rank too), the rows that scan streamed (sum over its
+ * workgroups of their list's length: x ld x 2 = the algorithmic HBM bytes; x ld8 for an fp8 search) and its workgroup count. */
 int mrag_ivf_last_timing(mrag_handle h, float* out_scan_ms, float* out_total_ms, int64_t* out_scanned_rows, int* out_n_wg);
 
 /* ---- a5: sentence-encoder forward, fills the LLMProvider.embed slot ---------------
