@@ -736,10 +736,11 @@ __global__ void enc_add_vec_kernel(const float* __restrict__ a, const float* __r
 }
 
 // ------------------------------------------------------------------ attention
+constexpr float ENC_NO_KEY = -3.0e38f;   // score bias of a key slot beyond the sequence (finite: exp(ENC_NO_KEY - max) == 0 for any max >= -1e30)
 // QKV [M_pad][3H] (q | k | v per token), mask [B][S] (1 = token), out [M_pad][H].
 // grid = B * heads * ceil(S/64); 256 threads: wave w owns query rows 16w..16w+15 of the block.
-// NW waves = 16 * NW query rows per workgroup: 8 waves (128 rows) when S > 64, so that a 128-token passage stages its
-// K / V blocks once instead of once per 64-row half (attention 0.59 -> see DESIGN); 4 waves for shorter sequences.
+// NW waves = 16 * NW query rows per workgroup; the launcher uses 8 waves (128 rows), so that 128 queries stage their
+// K / V blocks once instead of once per 64-row half (attention 0.59 -> see DESIGN).
 template <int DT, int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void enc_attention_kernel(const uint16_t* __restrict__ qkv, const int32_t* __restrict__ mask,
                                                                 uint16_t* __restrict__ out, int B, int S, int H, int heads, float scale) {
@@ -794,7 +795,9 @@ __global__ __launch_bounds__(64 * NW) void enc_attention_kernel(const uint16_t* 
 #pragma unroll
       for (int j = 0; j < 8; ++j) sVt[c * 8 + j][key] = vv[j];
     }
-    if (tid < KB) sBias[tid] = (k0 + tid < S && mask[(size_t)bb * S + k0 + tid] != 0) ? 0.f : -1e30f;
+    // masked keys get -1e30 (a row with no valid key attends all S of them evenly, as the oracle does); slots beyond S get
+    // ENC_NO_KEY, far enough below that to vanish from that row's softmax as well
+    if (tid < KB) sBias[tid] = k0 + tid >= S ? ENC_NO_KEY : mask[(size_t)bb * S + k0 + tid] != 0 ? 0.f : -1e30f;
     __syncthreads();
     // S = Q K^T  (16 q rows x 64 keys per wave): B operand lane holds K[key = 16*nf + (lane&15)][k chunk]
     f32x4 sc[4];
@@ -949,7 +952,7 @@ __global__ __launch_bounds__(64 * NW) void enc_attention_s128_kernel(const uint1
       *(frag*)&sV[key][c * 8] = vv[i];
     }
   }
-  for (int i = tid; i < SP; i += NT_) sBias[i] = (i < S && mask[(size_t)bb * S + i] != 0) ? 0.f : -1e30f;
+  for (int i = tid; i < SP; i += NT_) sBias[i] = i >= S ? ENC_NO_KEY : mask[(size_t)bb * S + i] != 0 ? 0.f : -1e30f;   // (as above)
   __syncthreads();
   const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;   // tr read: lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3
   auto v_frag = [&](int ks, int d) -> frag {     // V[keys 32 ks + 8 g .. +7][dh 16 d + i16]
@@ -1121,8 +1124,11 @@ static int dev_alloc(Encoder* e, void** p, size_t bytes) {
 
 static int alloc_linear(Encoder* e, Linear& l, int N, int K) {
   l.N = N; l.K = K; l.N_pad = (int)round_up(N, N >= G2_T ? G2_T : GN);   // 256-row padding lets the 256 x 256 kernel serve it
-  MRAG_TRY(dev_alloc(e, (void**)&l.w, (size_t)l.N_pad * K * 2));
-  MRAG_TRY(dev_alloc(e, (void**)&l.b, (size_t)l.N_pad * 4));
+  // The fused-LayerNorm flow runs the 256 x 256 kernel on every Linear, those with N < 256 included (hidden 64 / 128: N_pad 128),
+  // and that kernel stages whole 256-row weight tiles: the allocation always holds a full tile of (zero) rows, whatever N_pad says.
+  const size_t rows = (size_t)round_up(N, G2_T);
+  MRAG_TRY(dev_alloc(e, (void**)&l.w, rows * K * 2));
+  MRAG_TRY(dev_alloc(e, (void**)&l.b, rows * 4));
   return MRAG_OK;
 }
 
@@ -1242,9 +1248,10 @@ static int fold_layernorms(Encoder* e, hipStream_t stream) {
   auto fold = [&](const Linear& src, Linear& dst, float*& svec, const float* g, const float* b) -> int {
     if (!dst.w) {
       dst.N = src.N; dst.K = src.K; dst.N_pad = src.N_pad;
-      MRAG_TRY(dev_alloc(e, (void**)&dst.w, (size_t)dst.N_pad * dst.K * 2));
-      MRAG_TRY(dev_alloc(e, (void**)&dst.b, (size_t)dst.N_pad * 4));
-      MRAG_TRY(dev_alloc(e, (void**)&svec, (size_t)dst.N_pad * 4));
+      const size_t rows = (size_t)round_up(src.N, G2_T);   // whole 256-row tiles, as alloc_linear (intermediate 64 / 128: N_pad 128)
+      MRAG_TRY(dev_alloc(e, (void**)&dst.w, rows * dst.K * 2));
+      MRAG_TRY(dev_alloc(e, (void**)&dst.b, rows * 4));
+      MRAG_TRY(dev_alloc(e, (void**)&svec, rows * 4));
     }
     hipLaunchKernelGGL((enc_fold_ln_kernel<elem>), dim3((unsigned)((src.N + 3) / 4)), dim3(256), 0, stream, (const elem*)src.w, src.b, g, b,
                        src.N, src.K, (elem*)dst.w, dst.b, svec);
@@ -1294,8 +1301,6 @@ static int forward_impl(Encoder* e, int B, int S, float* d_out, int pool, int no
   MRAG_HIP(hipGetLastError());
   const int dh = H / c.heads;
   const float scale = 1.0f / sqrtf((float)dh);
-  const bool wide_attn = S > 64;
-  const dim3 agrid((unsigned)(B * c.heads * (wide_attn ? (S + 127) / 128 : 1)));
   // Fused-LayerNorm flow (large batches: every GEMM of a layer on the 256 x 256 kernel): the two LayerNorms of a layer never
   // run as kernels -- the GEMM before one emits per-token partial sums, a tiny kernel turns them into (mu, rstd), and the GEMMs
   // after it take the PRE-LayerNorm tensor as operand / residual (LnArgs above).  Only the last layer's output LayerNorm is
@@ -1339,11 +1344,12 @@ static int forward_impl(Encoder* e, int B, int S, float* d_out, int pool, int no
       if (dh == 32) { if (S <= 64) MRAG_ATTN(32, 64, 4); else if (S <= 128) MRAG_ATTN(32, 128, 4); else MRAG_ATTN(32, 256, 8); }
       else { if (S <= 64) MRAG_ATTN(64, 64, 4); else if (S <= 128) MRAG_ATTN(64, 128, 4); else MRAG_ATTN(64, 256, 8); }
 #undef MRAG_ATTN
-    } else
-    if (dh == 32 && wide_attn) hipLaunchKernelGGL((enc_attention_kernel<DT, 32, 8>), agrid, dim3(512), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
-    else if (dh == 32) hipLaunchKernelGGL((enc_attention_kernel<DT, 32, 4>), agrid, dim3(256), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
-    else if (wide_attn) hipLaunchKernelGGL((enc_attention_kernel<DT, 64, 8>), agrid, dim3(512), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
-    else hipLaunchKernelGGL((enc_attention_kernel<DT, 64, 4>), agrid, dim3(256), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
+    } else {
+      // longer sequences: 128 query rows per workgroup, keys in blocks of 64 with an online softmax
+      const dim3 agrid((unsigned)(B * c.heads * ((S + 127) / 128)));
+      if (dh == 32) hipLaunchKernelGGL((enc_attention_kernel<DT, 32, 8>), agrid, dim3(512), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
+      else hipLaunchKernelGGL((enc_attention_kernel<DT, 64, 8>), agrid, dim3(512), 0, stream, qkv, am, ctx, B, S, H, c.heads, scale);
+    }
     MRAG_HIP(hipGetLastError());
     if (fused) {
       LnArgs a{}; a.partials = partials; a.np = np;

@@ -242,10 +242,13 @@ class HipSentenceEncoder:
 
     # -- forward ----------------------------------------------------------------------------------
     def forward(self, ids: np.ndarray, mask: np.ndarray, pool: Optional[str] = None, normalize: bool = True) -> np.ndarray:
-        """ids/mask int32 [B,S] -> float32 [B,hidden]."""
+        """ids/mask int32 [B,S] -> float32 [B,hidden].  Ids outside the vocabulary raise ValueError."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         mask = np.ascontiguousarray(mask, dtype=np.int32)
         B, S = ids.shape
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.spec.vocab_size):
+            # (the embedding kernel clamps for memory safety only: a clamped id is a wrong row of the table, not an error anyone sees)
+            raise ValueError(f"token ids must lie in [0, vocab_size = {self.spec.vocab_size}): got {int(ids.min())} .. {int(ids.max())}")
         out = np.empty((B, self.spec.hidden), dtype=np.float32)
         pool = pool or self.spec.pool
         N.check(self._lib.mrag_encoder_forward(self._h, ids.ctypes.data, mask.ctypes.data, B, S, out.ctypes.data,

@@ -13,6 +13,7 @@ import math
 from typing import Dict
 
 import numpy as np
+import torch
 
 SPECS = {
     # public model-card shapes; re-check against config.json when weights exist
@@ -66,7 +67,10 @@ def _ln(x, g, b, eps):
     return (x - mu) / np.sqrt(var + eps) * g + b
 
 
-_erf = np.vectorize(math.erf)
+def _erf(a):
+    """erf of an fp64 array (``torch.erf``: the S = 512 cases run millions of elements, ``np.vectorize(math.erf)`` calls
+    Python once per element)."""
+    return torch.erf(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).numpy()
 
 
 def forward(spec, w: Dict[str, np.ndarray], ids: np.ndarray, mask: np.ndarray, pool: str = "mean",

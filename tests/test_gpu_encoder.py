@@ -1,5 +1,7 @@
 """GPU parity of the HIP sentence encoder (K6) against the CPU oracle (itself pinned to HF BertModel in
-tests/test_encoder_oracle.py), within the north-star 1e-3; plus the provider / backend end to end."""
+tests/test_encoder_oracle.py), within the north-star 1e-3 and, on the seeded-weight cases, within 4 x the rounding noise of
+a 16-bit pipeline where that is tighter (oracle/encoder_cases.py); plus the provider / backend end to end.  The dispatch
+(attention instances, GEMM kernels, masks) is covered case by case in tests/test_gpu_encoder_paths.py."""
 import json
 import zlib
 
@@ -7,11 +9,22 @@ import numpy as np
 import pytest
 
 from oracle import encoder as oe
+from oracle import encoder_cases as ec
 from oracle import dense_search as ds
 from oracle import ref_semantics as rs
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
+
+
+def _assert_close(got, want, spec, w, ids, mask, pool, normalize=True, dtype="f16", cap=TOL):
+    """Within ``cap`` (the fixed bound these tests always had) AND within the batch's own tolerance: 4 x the deviation the
+    oracle shows when it rounds what a 16-bit pipeline stores (oracle.encoder_cases.expected)."""
+    tol = ec.expected(spec, w, ids, mask, dtype).tol[(pool, normalize)]
+    err = float(np.abs(got - want).max())
+    print(f"max |gpu - oracle| {err:.2e}  rounding-noise tolerance {tol:.2e}  fixed bound {cap:.0e}")
+    np.testing.assert_allclose(got, want, rtol=0, atol=cap)
+    np.testing.assert_allclose(got, want, rtol=0, atol=min(cap, tol))
 
 
 def _batch(spec, B, S, seed, lens=None):
@@ -36,9 +49,9 @@ def test_small_archs_match_oracle(arch, B, S, pool):
     got = enc.forward(ids, mask, pool=pool)
     want = oe.forward(spec, w, ids, mask, pool=pool)
     assert np.isfinite(got).all()
-    np.testing.assert_allclose(got, want, rtol=0, atol=TOL)
+    _assert_close(got, want, spec, w, ids, mask, pool)
     raw = enc.forward(ids, mask, pool=pool, normalize=False)
-    np.testing.assert_allclose(raw, oe.forward(spec, w, ids, mask, pool=pool, normalize=False), rtol=0, atol=5e-3)
+    _assert_close(raw, oe.forward(spec, w, ids, mask, pool=pool, normalize=False), spec, w, ids, mask, pool, normalize=False, cap=5e-3)
 
 
 def test_minilm_l6_shape_matches_oracle():
@@ -51,7 +64,7 @@ def test_minilm_l6_shape_matches_oracle():
     ids, mask = _batch(spec, 16, 64, 9)
     got = enc.forward(ids, mask, pool="mean")
     want = oe.forward(spec, w, ids, mask, pool="mean")
-    np.testing.assert_allclose(got, want, rtol=0, atol=TOL)
+    _assert_close(got, want, spec, w, ids, mask, "mean")
     assert np.abs(got - want).max() < 5e-4
 
 
@@ -64,7 +77,7 @@ def test_bge_base_shape_matches_oracle_cls():
     ids, mask = _batch(spec, 6, 48, 10)
     got = enc.forward(ids, mask, pool="cls")
     want = oe.forward(spec, w, ids, mask, pool="cls")
-    np.testing.assert_allclose(got, want, rtol=0, atol=TOL)
+    _assert_close(got, want, spec, w, ids, mask, "cls")
 
 
 @pytest.mark.parametrize("arch,B,S,pool", [("minilm-l6", 1, 20, "mean"), ("minilm-l6", 2, 16, "mean"), ("minilm-l6", 3, 20, "mean"),
@@ -79,7 +92,7 @@ def test_single_question_batches_match_oracle(arch, B, S, pool):
     ids, mask = _batch(spec, B, S, 13)
     got = enc.forward(ids, mask, pool=pool)
     want = oe.forward(spec, w, ids, mask, pool=pool)
-    np.testing.assert_allclose(got, want, rtol=0, atol=TOL)
+    _assert_close(got, want, spec, w, ids, mask, pool)
     # the same rows inside a larger batch (tiled GEMM path) agree to fp16-activation noise
     ids2, mask2 = _batch(spec, 40, S, 14)
     ids2[:B], mask2[:B] = ids, mask
@@ -100,11 +113,11 @@ def test_fused_layernorm_flow_matches_oracle(arch, B, S, pool, layers):
     got = enc.forward(ids, mask, pool=pool)
     sub = np.arange(0, B, B // 16)
     want = oe.forward(spec, w, ids[sub], mask[sub], pool=pool)
-    np.testing.assert_allclose(got[sub], want, rtol=0, atol=TOL)
+    _assert_close(got[sub], want, spec, w, ids[sub], mask[sub], pool)
     assert np.isfinite(got).all()
     if arch == "minilm-l6":                      # the same flow with bf16 weights / activations (coarser rounding: 8e-3, as the plain bf16 test)
         enc16 = HipSentenceEncoder(EncoderSpec(**dict(spec, max_length=128)), w, dtype="bf16")
-        np.testing.assert_allclose(enc16.forward(ids, mask, pool=pool)[sub], want, rtol=0, atol=8e-3)
+        _assert_close(enc16.forward(ids, mask, pool=pool)[sub], want, spec, w, ids[sub], mask[sub], pool, dtype="bf16", cap=8e-3)
 
 
 def test_fused_layernorm_flow_on_offset_and_outlier_activations(monkeypatch):
@@ -171,7 +184,7 @@ def test_bf16_compute_and_errors():
     w = oe.seeded_weights(spec, 2)
     enc = HipSentenceEncoder(EncoderSpec(**ARCHS["tiny"]), w, dtype="bf16")
     ids, mask = _batch(spec, 4, 32, 1)
-    np.testing.assert_allclose(enc.forward(ids, mask), oe.forward(spec, w, ids, mask), rtol=0, atol=8e-3)
+    _assert_close(enc.forward(ids, mask), oe.forward(spec, w, ids, mask), spec, w, ids, mask, "mean", dtype="bf16", cap=8e-3)
     with pytest.raises(MragError):
         enc.forward(np.zeros((1, 129), np.int32), np.ones((1, 129), np.int32))     # beyond max_position
     w2 = dict(w); w2.pop("encoder.layer.1.output.dense.bias")
