@@ -361,13 +361,20 @@ __global__ void kmeans_accum_kernel(const uint16_t* __restrict__ x, const int64_
   if (lane == 0) atomicAdd(&cnt[c], 1);
 }
 
-template <int BF16>
+// after the accumulation, one thread per (list, dim) element of sums: an empty list takes its centroid back (it keeps
+// it); MEAN (inner product) turns the sum of a non-empty list into the mean, (float)((double)sum / count), one rounding
+// to fp32 like K1's own.  Cosine leaves the sum: the normalisation that follows makes the division redundant.
+template <int BF16, int MEAN>
 __global__ void kmeans_keep_empty_kernel(const uint16_t* __restrict__ cen, int ld, int dim, int nlist, const int* __restrict__ cnt,
                                          float* __restrict__ sums) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)nlist * dim) return;
   const int c = (int)(i / dim), d = (int)(i % dim);
-  if (cnt[c] > 0) return;
+  const int m = cnt[c];
+  if (m > 0) {
+    if (MEAN) sums[i] = (float)((double)sums[i] / (double)m);
+    return;
+  }
   const uint16_t b = cen[(size_t)c * ld + d];
   float v;
   if (BF16) v = __uint_as_float((uint32_t)b << 16);
@@ -594,12 +601,19 @@ int mrag_ivf_train(mrag_handle h, const void* rows, int64_t n, int src_dtype, in
     (void)hipMemsetAsync(ix->cnts.p, 0, (size_t)ix->nlist * 4, stream);
     const dim3 g((unsigned)((n + 3) / 4)), b(256);
     const dim3 g2((unsigned)(((int64_t)ix->nlist * ix->dim + 255) / 256));
+    const bool mean = ix->metric != MRAG_METRIC_COSINE;   // inner product: centroid = mean of its rows, not their sum
+    const uint16_t* xr = (const uint16_t*)x.p;
+    const int64_t* idp = (const int64_t*)ids.p;
+    float* sums = (float*)ix->sums.p;
+    int* cnts = (int*)ix->cnts.p;
     if (ix->dtype == MRAG_BF16) {
-      hipLaunchKernelGGL((kmeans_accum_kernel<1>), g, b, 0, stream, (const uint16_t*)x.p, (const int64_t*)ids.p, n, ix->ld, ix->dim, (float*)ix->sums.p, (int*)ix->cnts.p);
-      hipLaunchKernelGGL((kmeans_keep_empty_kernel<1>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)ix->cnts.p, (float*)ix->sums.p);
+      hipLaunchKernelGGL((kmeans_accum_kernel<1>), g, b, 0, stream, xr, idp, n, ix->ld, ix->dim, sums, cnts);
+      if (mean) hipLaunchKernelGGL((kmeans_keep_empty_kernel<1, 1>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)cnts, sums);
+      else hipLaunchKernelGGL((kmeans_keep_empty_kernel<1, 0>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)cnts, sums);
     } else {
-      hipLaunchKernelGGL((kmeans_accum_kernel<0>), g, b, 0, stream, (const uint16_t*)x.p, (const int64_t*)ids.p, n, ix->ld, ix->dim, (float*)ix->sums.p, (int*)ix->cnts.p);
-      hipLaunchKernelGGL((kmeans_keep_empty_kernel<0>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)ix->cnts.p, (float*)ix->sums.p);
+      hipLaunchKernelGGL((kmeans_accum_kernel<0>), g, b, 0, stream, xr, idp, n, ix->ld, ix->dim, sums, cnts);
+      if (mean) hipLaunchKernelGGL((kmeans_keep_empty_kernel<0, 1>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)cnts, sums);
+      else hipLaunchKernelGGL((kmeans_keep_empty_kernel<0, 0>), g2, b, 0, stream, ix->cen, ix->ld, ix->dim, ix->nlist, (const int*)cnts, sums);
     }
     st = launch_prep_rows(ix->sums.p, MRAG_F32, ix->nlist, ix->dim, ix->cen, ix->ld, ix->dtype, ix->metric == MRAG_METRIC_COSINE, stream);
     if (st != MRAG_OK) { cleanup(); return st; }

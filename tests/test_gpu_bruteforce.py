@@ -69,6 +69,24 @@ def test_many_query_tiles_xcd_map(nq, n):
     _check(_index(c16), q16, c16, k)
 
 
+@pytest.mark.parametrize("k", [10, 64, 100])
+def test_batch_launch_loop_is_exact(k):
+    """16 641 queries = 64 query tiles + one tile + one query: the batch regimes cut them into launches of at most
+    MAX_QTILES_PER_LAUNCH tiles (csrc/bf_index.hip; fewer per launch in the wide-batch loop at k = 100).  Every query
+    against the oracle, and the first and last 300 result rows bit for bit against a search of those queries alone: a
+    wrong query or output offset of a later launch shows there."""
+    nq, n, d = 64 * 256 + 256 + 1, 777, 64
+    c16 = ds.normalize_round(ds.make_gaussian(n, d, 61))
+    q16 = ds.normalize_round(ds.make_gaussian(nq, d, 62))
+    ix = _index(c16)
+    assert k <= ix.max_k(nq)
+    sc, ids, _, _ = _check(ix, q16, c16, k)
+    for sl in (slice(0, 300), slice(nq - 300, nq)):
+        s1, i1 = ix.search(q16[sl], k, normalize=False)
+        assert np.array_equal(s1.view(np.uint32), sc[sl].view(np.uint32)) and np.array_equal(i1, ids[sl])
+    ix.close()
+
+
 def test_bf16_storage():
     import torch
     n, nq, d, k = 9000, 50, 256, 10
