@@ -17,6 +17,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <numeric>
 
 namespace mrag {
@@ -35,11 +36,10 @@ struct IvfIndex : Object {
   int64_t n_sorted = 0;
   std::vector<int> list_tile_lo, list_count;
   int max_list_rows = 0;
-  DevBuf qbuf, qg, lists, counts, stage_in, tmp_sc, tmp_id, out_sc, out_id, desc, ploc, gq, perm, sums, cnts;
+  DevBuf qbuf, qg, lists, counts, stage_in, tmp_sc, tmp_id, out_sc, out_id, desc, ploc, gq, sums, cnts;
   DevBuf d_list_count, d_list_tile_lo, plan;   // device copies of the list layout; plan = lcount | wg_first | cursor | n_wg
   DevBuf scores, sdesc;                        // "score segments + select" regime (ivf_scan.hip): fp32 segments, dense descriptors
-  bool last_scores_path = false;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // search start | (unused) | (unused) | search end
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // search start | start of mrag_ivf_allowed_per_list's upload | (unused) | search end
   std::vector<hipEvent_t> cev;    // per chunk of the last search: list scan begin, list scan end
   int n_chunks = 0;               // chunks of the last search (mrag_ivf_last_timing sums their scan brackets)
   DevBuf stats;                   // device accumulators of the last search: int64 rows streamed by the list scans, int64 workgroups
@@ -76,7 +76,7 @@ struct IvfIndex : Object {
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : cev) if (e) (void)hipEventDestroy(e);
     for (void* p : {(void*)cen, (void*)raw, (void*)assign, (void*)sorted, (void*)row_ids}) if (p) (void)hipFree(p);
-    for (DevBuf* b : {&qbuf, &qg, &lists, &counts, &stage_in, &tmp_sc, &tmp_id, &out_sc, &out_id, &desc, &ploc, &gq, &perm, &sums, &cnts, &d_list_count, &d_list_tile_lo, &plan, &scores, &sdesc, &stats}) b->release();
+    for (DevBuf* b : {&qbuf, &qg, &lists, &counts, &stage_in, &tmp_sc, &tmp_id, &out_sc, &out_id, &desc, &ploc, &gq, &sums, &cnts, &d_list_count, &d_list_tile_lo, &plan, &scores, &sdesc, &stats}) b->release();
   }
 };
 
@@ -401,28 +401,37 @@ static int ivf_grow(IvfIndex* ix, int64_t need, hipStream_t stream) {
   return MRAG_OK;
 }
 
+// The dense launch (bf_launch) of nq prepared `queries` over n_rows prepared rows of `corpus`, in the index's layout and with its
+// workspace.  The caller adds k and the outputs, and what only it needs: id_base, an allow-set, events, the descriptor mode's fields.
+static BfLaunch ivf_launch(IvfIndex* ix, const uint16_t* corpus, int64_t n_rows, const void* queries, int64_t nq, hipStream_t stream) {
+  BfLaunch a;
+  a.corpus = corpus; a.n_rows = n_rows; a.queries = (const uint16_t*)queries; a.nq = nq;
+  a.ld = ix->ld; a.dtype = ix->dtype;
+  a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
+  return a;
+}
+
 // nearest centroid (k = 1) of prepared rows x [n][ld] (n need not be a multiple of 256: the
 // buffer behind it must be readable up to the next multiple) -> out_ids int64 [n]
 static int ivf_assign_rows(IvfIndex* ix, const uint16_t* x, int64_t n, int64_t* out_ids, float* out_sc, hipStream_t stream) {
-  BfLaunch a;
-  a.corpus = ix->cen; a.queries = x; a.ld = ix->ld; a.dtype = ix->dtype; a.k = 1;
-  a.nq = n; a.n_rows = ix->nlist; a.id_base = 0;
-  a.out_scores = out_sc; a.out_ids = out_ids;
-  a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
+  BfLaunch a = ivf_launch(ix, ix->cen, ix->nlist, x, n, stream);
+  a.k = 1; a.out_scores = out_sc; a.out_ids = out_ids;
   return bf_launch(a);
 }
 
-// rows (any dtype, host or device) -> prepared storage rows at dst (device), padded buffer rows zeroed by caller
-static int ivf_prepare(IvfIndex* ix, const void* rows, int64_t n, int src_dtype, int normalize, int is_device, uint16_t* dst,
-                       hipStream_t stream) {
-  const void* src = rows;
-  if (!is_device) {
-    const size_t bytes = (size_t)n * ix->dim * esize(src_dtype);
+// a caller's rows: n rows of ix->dim elements of any supported dtype, in host or device memory
+struct IvfRows { const void* p; int64_t n; int dtype, normalize, is_device; };
+
+// rows -> prepared storage rows at dst (device), padded buffer rows zeroed by caller
+static int ivf_prepare(IvfIndex* ix, const IvfRows& r, uint16_t* dst, hipStream_t stream) {
+  const void* src = r.p;
+  if (!r.is_device) {
+    const size_t bytes = (size_t)r.n * ix->dim * esize(r.dtype);
     MRAG_TRY(ix->stage_in.ensure(bytes));
-    MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, rows, bytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(ix->stage_in.p, r.p, bytes, hipMemcpyHostToDevice, stream));
     src = ix->stage_in.p;
   }
-  return launch_prep_rows(src, src_dtype, n, ix->dim, dst, ix->ld, ix->dtype, normalize && ix->metric == MRAG_METRIC_COSINE, stream);
+  return launch_prep_rows(src, r.dtype, r.n, ix->dim, dst, ix->ld, ix->dtype, r.normalize && ix->metric == MRAG_METRIC_COSINE, stream);
 }
 
 static uint64_t splitmix64(uint64_t& s) {
@@ -523,7 +532,7 @@ int mrag_ivf_set_centroids(mrag_handle h, const void* centroids, int src_dtype, 
   if (ix->n) return fail(MRAG_ERR_INVALID, "centroids cannot change after rows were added");
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
-  MRAG_TRY(ivf_prepare(ix, centroids, ix->nlist, src_dtype, normalize, is_device, ix->cen, stream));
+  MRAG_TRY(ivf_prepare(ix, {centroids, ix->nlist, src_dtype, normalize, is_device}, ix->cen, stream));
   MRAG_HIP(hipStreamSynchronize(stream));
   ix->has_centroids = true;
   return MRAG_OK;
@@ -566,7 +575,7 @@ int mrag_ivf_train(mrag_handle h, const void* rows, int64_t n, int src_dtype, in
   DevBuf x;
   MRAG_TRY(x.ensure((size_t)npad * ix->ld * 2));
   MRAG_HIP(hipMemsetAsync(x.p, 0, (size_t)npad * ix->ld * 2, stream));
-  int st = ivf_prepare(ix, rows, n, src_dtype, normalize, rows_is_device, (uint16_t*)x.p, stream);
+  int st = ivf_prepare(ix, {rows, n, src_dtype, normalize, rows_is_device}, (uint16_t*)x.p, stream);
   if (st != MRAG_OK) { x.release(); return st; }
   // init: nlist distinct rows (Floyd's sampling from splitmix64(seed)), in ascending row order
   std::vector<int64_t> pick;
@@ -639,7 +648,7 @@ int mrag_ivf_add(mrag_handle h, const void* rows, int64_t n, int src_dtype, int 
   // wherever the stored rows end (not on a tile boundary after an add of any other size), so the capacity covers that read
   MRAG_TRY(ivf_grow(ix, ix->n + bf_query_rows(n), stream));
   uint16_t* dst = ix->raw + (size_t)ix->n * ix->ld;
-  MRAG_TRY(ivf_prepare(ix, rows, n, src_dtype, normalize, rows_is_device, dst, stream));
+  MRAG_TRY(ivf_prepare(ix, {rows, n, src_dtype, normalize, rows_is_device}, dst, stream));
   MRAG_TRY(ix->tmp_id.ensure((size_t)n * 8));
   MRAG_TRY(ix->tmp_sc.ensure((size_t)n * 4));
   // (the raw buffer is zero beyond the stored rows and holds bf_query_rows(n) rows from dst on: safe to read as padded queries)
@@ -679,6 +688,10 @@ int mrag_ivf_get_assignments(mrag_handle h, int32_t* out, int out_is_device, voi
   return MRAG_OK;
 }
 
+}  // extern "C"
+
+namespace mrag {
+
 // The score buffer of the "score segments + select" regime: MRAG_IVF_SCORES_MB, default 16 GiB, 0 = always the fused kernel.
 static int64_t ivf_scores_cap() {
   static const int64_t cap = [] { const char* e = getenv("MRAG_IVF_SCORES_MB"); return (int64_t)(e ? atoll(e) : 16384) << 20; }();
@@ -699,222 +712,8 @@ static int64_t ivf_chunk_queries(const IvfIndex* ix, int64_t nq, int nprobe) {
   return chunk;
 }
 
-// where a search writes its nq x k results: the caller's buffers, or out_sc / out_id for host outputs, copied back by
-// ivf_copy_back (the search synchronises at its end)
-static int ivf_stage_outputs(IvfIndex* ix, int64_t nq, int k, float* out_scores, int64_t* out_ids, int out_is_device, float** d_sc, int64_t** d_id) {
-  if (out_is_device) { *d_sc = out_scores; *d_id = out_ids; return MRAG_OK; }
-  MRAG_TRY(ix->out_sc.ensure((size_t)nq * k * 4));
-  MRAG_TRY(ix->out_id.ensure((size_t)nq * k * 8));
-  *d_sc = (float*)ix->out_sc.p; *d_id = (int64_t*)ix->out_id.p;
-  return MRAG_OK;
-}
-
-static int ivf_copy_back(int64_t nq, int k, float* out_scores, int64_t* out_ids, int out_is_device, const float* d_sc, const int64_t* d_id, hipStream_t stream) {
-  if (out_is_device) return MRAG_OK;
-  MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, stream));
-  MRAG_HIP(hipMemcpyAsync(out_ids, d_id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, stream));
-  return MRAG_OK;
-}
-
-// queries -> storage dtype in ix->qbuf, zero padded to bf_query_rows(nq) rows
-static int ivf_prep_queries(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, hipStream_t stream) {
-  const int64_t nq_pad = bf_query_rows(nq);
-  MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
-  MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));   // (rows < nq: written whole by the prepare kernel)
-  return ivf_prepare(ix, queries, nq, q_dtype, normalize, queries_is_device, (uint16_t*)ix->qbuf.p, stream);
-}
-
-// What a range search adds to a search: the floor, per query the stored position of its excluded row (device, or NULL) and
-// the counts (in the memory space of the other outputs).  stored_rows: `queries` are rows of ix->raw (storage dtype, ld
-// apart: the self-join), copied as they are.  The range select has no fused form: a chunk that would take the fused regime
-// is refused.
-struct IvfRangeArgs {
-  float floor = 0.f;
-  const int64_t* excl_pos = nullptr;
-  int64_t* out_counts = nullptr;
-  bool stored_rows = false;
-};
-
-static int ivf_segments_only(const char* what, const char* why) {
-  return fail(MRAG_ERR_UNSUPPORTED, "IVF %s search runs in the score-segment regime only: %s", what, why);
-}
-static int ivf_range_unsupported(const char* why) { return ivf_segments_only("range", why); }
-
-// one chunk of a search (<= 2^20 queries whose score segments fit the buffer): probe selection, plan, list scan, selection
-// live_bits / stored_bits (filtered search, path P): probe only live lists, select only allowed stored positions
-// rg (range search): the selection lists and counts the rows >= rg->floor (pointers already moved to this chunk's queries)
-// fp8_refine > 0 (fp8 search): the scan runs over the fp8 copies of rows and queries, the selection keeps the top
-// fp8_refine local rows per query, and those are re-scored against the 16-bit rows in arrival order for the k best
-static int ivf_search_chunk(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
-                            int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream, int chunk_idx,
-                            const uint32_t* live_bits, const uint32_t* stored_bits, const IvfRangeArgs* rg = nullptr, int fp8_refine = 0) {
-  const bool f8 = fp8_refine > 0;
-  const char* seg_what = f8 ? "fp8" : "range";
-  hipEvent_t ev_scan0 = ix->cev[2 * chunk_idx], ev_scan1 = ix->cev[2 * chunk_idx + 1];
-  unsigned long long* d_stats = (unsigned long long*)ix->stats.p;
-
-  float* d_sc; int64_t* d_id;
-  MRAG_TRY(ivf_stage_outputs(ix, nq, k, out_scores, out_ids, out_is_device, &d_sc, &d_id));
-  int64_t* d_cnt = nullptr;
-  if (rg) {
-    d_cnt = rg->out_counts;
-    if (!out_is_device) { MRAG_TRY(ix->out_cnt.ensure((size_t)nq * 8)); d_cnt = (int64_t*)ix->out_cnt.p; }
-  }
-  // 1) queries -> storage dtype; probe lists
-  if (rg && rg->stored_rows) {
-    const int64_t nq_pad = bf_query_rows(nq);
-    MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * ix->ld * 2));
-    MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * ix->ld * 2, 0, (size_t)(nq_pad - nq) * ix->ld * 2, stream));
-    MRAG_HIP(hipMemcpyAsync(ix->qbuf.p, queries, (size_t)nq * ix->ld * 2, hipMemcpyDeviceToDevice, stream));
-  } else {
-    MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
-  }
-  if (f8) {   // (qbuf rows [nq, nq_pad) are zero, the scan's pad row nq among them: so are their fp8 rows)
-    const int64_t nq_pad = bf_query_rows(nq);
-    MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
-    MRAG_TRY(launch_quant_queries_fp8((const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, nq_pad, (uint8_t*)ix->qbuf8.p,
-                                      ix->ld8, stream));
-    MRAG_TRY(ix->cand.ensure((size_t)nq * fp8_refine * 8));
-  }
-  MRAG_TRY(ix->tmp_id.ensure((size_t)nq * nprobe * 8));
-  MRAG_TRY(ix->tmp_sc.ensure((size_t)nq * nprobe * 4));
-  // The list scan (and the probe selection before it) runs as "score segments + select" (ivf_scan.hip) whenever the
-  // fp32 segments of this search fit the score buffer; otherwise (exhaustive probing of a big index) as the fused
-  // GEMM + top-k kernel in descriptor mode.  MRAG_IVF_SCORES_MB = 0 forces the fused path (tests).
-  const int64_t scores_cap = ivf_scores_cap();
-  const int nl = ix->nlist;
-  MRAG_TRY(ix->plan.ensure((size_t)(4 * nl + 4) * 4 + (size_t)nl * 8));
-  int* d_lcount = (int*)ix->plan.p;      // queries per list | first group of the list | cursor | first descriptor | descriptor count, score floats | float offset of the list's score blocks
-  int* d_wg_first = d_lcount + nl;
-  int* d_cursor = d_wg_first + nl;
-  int* d_dfirst = d_cursor + nl;
-  int* d_nwg = d_dfirst + nl;
-  long long* d_foff = (long long*)(d_nwg + 4);
-  MRAG_HIP(hipMemsetAsync(d_lcount, 0, (size_t)nl * 4, stream));
-  bool counted = false;                  // the probe selection below can fill d_lcount itself
-  if (nprobe == ix->nlist) {
-    const int64_t np_ = nq * nprobe;
-    hipLaunchKernelGGL(ivf_all_lists_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, stream, (int64_t*)ix->tmp_id.p, np_, ix->nlist);
-    MRAG_HIP(hipGetLastError());
-  } else if (round_up(nq, IVFS_QUERIES) * ivfs_pitch(ix->nlist) * 4 <= scores_cap) {
-    MRAG_TRY(ix->sdesc.ensure((size_t)ivfs_dense_n_desc(nq, ix->nlist) * IVFS_DESC_WORDS * 4));
-    MRAG_TRY(ix->scores.ensure((size_t)(round_up(nq, IVFS_QUERIES) * ivfs_pitch(ix->nlist) * 4)));
-    MRAG_TRY(ivfs_dense_topk(ix->cen, ix->nlist, (const uint16_t*)ix->qbuf.p, nq, ix->ld, ix->dtype, nprobe, (int*)ix->sdesc.p,
-                             (float*)ix->scores.p, (float*)ix->tmp_sc.p, (int64_t*)ix->tmp_id.p, stream, d_lcount,
-                             (const int*)ix->d_list_count.p, live_bits));
-    counted = true;
-  } else {
-    BfLaunch a;
-    a.corpus = ix->cen; a.queries = (const uint16_t*)ix->qbuf.p; a.ld = ix->ld; a.dtype = ix->dtype; a.k = nprobe;
-    a.nq = nq; a.n_rows = ix->nlist;
-    a.out_scores = (float*)ix->tmp_sc.p; a.out_ids = (int64_t*)ix->tmp_id.p;
-    a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
-    a.allow = live_bits;                 // (filtered: dead lists are never probed; a pair without a list gets probe id -1)
-    MRAG_TRY(bf_launch(a));
-  }
-  // 2) device: list -> the queries that probe it, cut into workgroups of <= 128 (score segments) or <= 256 (fused
-  //    kernel) queries.  Only the workgroup count and the size of the segments come back to the host (12 bytes).
-  const size_t npairs = (size_t)nq * nprobe;
-  const int64_t wg_bound = (int64_t)std::min<size_t>((size_t)nl, npairs) + (int64_t)(npairs / IVFS_QUERIES) + 1;   // (covers the 256-query plan too)
-  // score-segment regime: every group is cut into ceil(list rows / IVFS_CHUNK_ROWS) scan descriptors
-  const int64_t desc_bound = wg_bound * std::max<int64_t>(1, (ix->max_list_rows + IVFS_CHUNK_ROWS - 1) / IVFS_CHUNK_ROWS);
-  MRAG_TRY(ix->desc.ensure((size_t)desc_bound * 8 * 4));
-  MRAG_TRY(ix->gq.ensure((size_t)wg_bound * 256 * 8));
-  MRAG_TRY(ix->ploc.ensure(npairs * 16));   // int2 (fused regime) or int4 (score segments) per pair
-  const unsigned pgrid = (unsigned)((npairs + 255) / 256);
-  if (!counted)
-    hipLaunchKernelGGL(ivf_count_kernel, dim3(pgrid), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs,
-                       (const int*)ix->d_list_count.p, d_lcount);
-  bool use_scores = scores_cap > 0 && nprobe <= 256;   // (the select kernel holds <= 256 segments per query; exhaustive probing takes the fused path)
-  if ((rg || f8) && !use_scores) return ivf_segments_only(seg_what, scores_cap > 0 ? "more than 256 probed lists per query" : "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
-  // Score floats of this search: known exactly only on the device (sum over the probed lists of queries x rows).  When
-  // even the bound "every pair probes the longest list" fits the buffer, nothing comes back to the host at all: the
-  // scan is launched over the BOUND of the workgroup count and reads the real one from device memory.
-  const int64_t max_pitch = ivfs_pitch(ix->max_list_rows);
-  const bool no_sync = use_scores && (int64_t)npairs * max_pitch * 4 <= scores_cap;
-  // (a filtered search only comes here when it fits: mrag_ivf_search_filtered runs path E otherwise)
-  if (stored_bits && !no_sync) return fail(MRAG_ERR_INVALID, "filtered IVF chunk does not fit the score buffer");
-  int plan_out[3] = {0, 0, 0};
-  const bool planned_scores = use_scores;
-  if (use_scores) {
-    hipLaunchKernelGGL(ivf_plan_scores_kernel, dim3(1), dim3(1024), 0, stream, (const int*)d_lcount, (const int*)ix->d_list_count.p,
-                       nl, d_wg_first, d_cursor, d_dfirst, d_foff, d_nwg, d_stats);
-    MRAG_HIP(hipGetLastError());
-    if (no_sync) {
-      MRAG_TRY(ix->scores.ensure((size_t)std::max<int64_t>((int64_t)npairs * max_pitch, 4) * 4));
-    } else {
-      MRAG_HIP(hipMemcpyAsync(plan_out, d_nwg, 12, hipMemcpyDeviceToHost, stream));
-      MRAG_HIP(hipStreamSynchronize(stream));
-      const int64_t floats = (int64_t)(uint32_t)plan_out[1] | ((int64_t)plan_out[2] << 32);
-      if (plan_out[0] < 0 || plan_out[0] > desc_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", plan_out[0], (long long)desc_bound);
-      if (floats * 4 > scores_cap && (rg || f8)) return ivf_segments_only(seg_what, "the score segments of one chunk exceed the score buffer (MRAG_IVF_SCORES_MB)");
-      if (floats * 4 > scores_cap) use_scores = false;
-      else MRAG_TRY(ix->scores.ensure((size_t)std::max<int64_t>(floats, 4) * 4));
-    }
-  }
-  int n_wg = -1;   // -1: still on the device (read back by mrag_ivf_last_timing if asked)
-  if (use_scores) {
-    hipLaunchKernelGGL(ivf_scatter_kernel, dim3(pgrid), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs, nprobe,
-                       (const int*)ix->d_list_count.p, (const int*)d_wg_first, d_cursor, (int64_t*)ix->gq.p, nullptr, 7,
-                       (const long long*)d_foff, (const int*)ix->d_list_tile_lo.p, (int4*)ix->ploc.p, (const int*)d_lcount,
-                       (const int*)d_dfirst, (int*)ix->desc.p, (int)desc_bound);
-    MRAG_HIP(hipGetLastError());
-    // 3) scores of every (query, probed list) pair, then the k best per query
-    MRAG_HIP(hipEventRecord(ev_scan0, stream));
-    // (no_sync: the workgroup count stays on the device, the grid is its bound)
-    if (!no_sync) n_wg = plan_out[0];
-    MRAG_TRY(ivfs_scan(f8 ? (const uint16_t*)ix->sorted8 : ix->sorted, (const uint16_t*)(f8 ? ix->qbuf8.p : ix->qbuf.p),
-                       f8 ? ix->ld8 / 2 : ix->ld, f8 ? MRAG_DT_FP8 : ix->dtype, nq, (const int*)ix->desc.p,
-                       no_sync ? (int)desc_bound : n_wg, no_sync ? d_nwg : nullptr, (const int64_t*)ix->gq.p, (float*)ix->scores.p,
-                       stream));
-    IvfsRange sel_range{0.f, nullptr, nullptr};
-    if (rg) sel_range = IvfsRange{rg->floor, rg->excl_pos, d_cnt};
-    if (f8)   // candidates: local rows in (fp8 score desc, row asc) order, -1 past the rows of the probed lists
-      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, fp8_refine, ix->row_ids, 0, nullptr, (int64_t*)ix->cand.p, stream));
-    else
-      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, nprobe, nq, k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
-                                 stored_bits, rg ? &sel_range : nullptr));
-    MRAG_HIP(hipEventRecord(ev_scan1, stream));
-    if (f8)
-      MRAG_TRY(launch_fp8_rerank(ix->raw, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)ix->cand.p, nq,
-                                 fp8_refine, k, ix->id_base, d_sc, d_id, stream));
-  } else {
-    MRAG_HIP(hipMemsetAsync(ix->gq.p, 0xFF, (size_t)wg_bound * 256 * 8, stream));   // (the gather below reads whole 256-slot slabs)
-    hipLaunchKernelGGL(ivf_plan_kernel, dim3(1), dim3(1024), 0, stream, (const int*)d_lcount, (const int*)ix->d_list_count.p,
-                       (const int*)ix->d_list_tile_lo.p, nl, d_wg_first, d_cursor, (int*)ix->desc.p, (int)wg_bound, d_nwg,
-                       planned_scores ? nullptr : d_stats);   // (a scores plan that turned out too big has already counted this chunk)
-    hipLaunchKernelGGL(ivf_scatter_kernel, dim3(pgrid), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs, nprobe,
-                       (const int*)ix->d_list_count.p, (const int*)d_wg_first, d_cursor, (int64_t*)ix->gq.p, (int2*)ix->ploc.p, 8,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-    MRAG_HIP(hipGetLastError());
-    MRAG_HIP(hipMemcpyAsync(&n_wg, d_nwg, 4, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-    if (n_wg < 0 || n_wg > wg_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", n_wg, (long long)wg_bound);
-    // 3) gather queries per workgroup, scan the lists, merge
-    if (n_wg) {
-      MRAG_TRY(ix->qg.ensure((size_t)n_wg * 256 * ix->ld * 2));
-      const int64_t ng = (int64_t)n_wg * 256;
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ng + 3) / 4)), dim3(256), 0, stream, (const uint16_t*)ix->qbuf.p,
-                         (const int64_t*)ix->gq.p, ng, ix->ld, (uint16_t*)ix->qg.p, 0);
-      MRAG_HIP(hipGetLastError());
-    }
-    BfLaunch a;
-    a.corpus = ix->sorted; a.queries = (const uint16_t*)ix->qg.p; a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
-    a.nq = nq;
-    static const int dummy_desc = 0;
-    a.wg_desc = n_wg ? (const int*)ix->desc.p : &dummy_desc; a.n_wg = n_wg;
-    a.pair_loc = ix->ploc.p; a.nprobe = nprobe; a.row_ids = ix->row_ids;
-    a.id_base = ix->id_base;
-    a.out_scores = d_sc; a.out_ids = d_id;
-    a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
-    a.ev_k2_begin = ev_scan0; a.ev_k2_end = ev_scan1;
-    MRAG_TRY(bf_launch(a));
-  }
-  ix->last_scores_path = use_scores;
-  (void)n_wg;
-  if (rg && !out_is_device) MRAG_HIP(hipMemcpyAsync(rg->out_counts, d_cnt, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
-  return ivf_copy_back(nq, k, out_scores, out_ids, out_is_device, d_sc, d_id, stream);
-}
+// range and fp8 searches have no fused form: what ("range" / "fp8") is refused, and why
+static int ivf_segments_only(const char* what, const char* why) { return fail(MRAG_ERR_UNSUPPORTED, "IVF %s search runs in the score-segment regime only: %s", what, why); }
 
 // the per-chunk events of a search in n_chunks chunks: list scan begin, list scan end
 static int ivf_grow_cev(IvfIndex* ix, int n_chunks) {
@@ -926,83 +725,18 @@ static int ivf_grow_cev(IvfIndex* ix, int n_chunks) {
   return MRAG_OK;
 }
 
-// the chunks of a search of nq queries, chunk queries each, one after another (live_bits / stored_bits: as ivf_search_chunk)
-static int ivf_run_chunks(IvfIndex* ix, const void* queries, int64_t nq, int64_t chunk, int q_dtype, int normalize, int queries_is_device,
-                          int nprobe, int k, float* out_scores, int64_t* out_ids, int out_is_device, hipStream_t stream,
-                          const uint32_t* live_bits = nullptr, const uint32_t* stored_bits = nullptr, const IvfRangeArgs* rg = nullptr,
-                          int fp8_refine = 0) {
-  const int n_chunks = (int)((nq + chunk - 1) / chunk);
-  MRAG_TRY(ivf_grow_cev(ix, n_chunks));
-  const size_t qrow = rg && rg->stored_rows ? (size_t)ix->ld * 2 : (size_t)ix->dim * esize(q_dtype);
-  for (int c = 0; c < n_chunks; ++c) {
-    const int64_t off = (int64_t)c * chunk, m = std::min(chunk, nq - off);
-    IvfRangeArgs crg;
-    if (rg) { crg = *rg; if (crg.excl_pos) crg.excl_pos += off; crg.out_counts += off; }
-    MRAG_TRY(ivf_search_chunk(ix, (const char*)queries + (size_t)off * qrow, m, q_dtype, normalize, queries_is_device, nprobe, k,
-                              out_scores + (size_t)off * k, out_ids + (size_t)off * k, out_is_device, stream, c, live_bits, stored_bits,
-                              rg ? &crg : nullptr, fp8_refine));
-  }
-  ix->n_chunks = n_chunks;
-  return MRAG_OK;
-}
-
-// nq, k and nprobe of both IVF searches
-static int ivf_check_nq_k(int64_t nq, int k, int nprobe) {
-  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
-  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
-  return MRAG_OK;
-}
-
-// After an IVF search's own argument checks: *nprobe clamped and checked (nq == 0 stops there: the caller returns), the
-// buffers, the index finalized, the batch cut into chunks of *chunk queries, `stream` ordered behind the previous search.
-static int ivf_search_begin(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, const float* out_scores, const int64_t* out_ids,
-                            hipStream_t stream, int* nprobe, int64_t* chunk) {
-  *nprobe = std::min(*nprobe, ix->nlist);
-  // probe selection = top-nprobe over the centroids: the fused kernel up to 64, the streaming kernel up to 256
-  // (8 queries per launch); nprobe == nlist needs no selection at all
-  if (*nprobe > bf_max_k_wide() && *nprobe < ix->nlist)
-    return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", *nprobe, bf_max_k_wide(), ix->nlist);
-  if (nq == 0) return MRAG_OK;
-  if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
-  if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
-  MRAG_TRY(use_device(ix->device));
-  MRAG_TRY(ivf_finalize(ix, stream));
-  *chunk = ivf_chunk_queries(ix, nq, *nprobe);
-  if (*chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
-  ix->timed = false;
-  // an asynchronous search (device queries + device results) returns with the handle's scratch buffers still in use on ITS
-  // stream; a following search on another stream first waits for that one's end event (a no-op on the same stream or after a
-  // synchronous search), so callers may switch streams between searches on one handle
+// An asynchronous call (device inputs + results) returns with the handle's scratch buffers still in use on ITS stream; a call
+// on another stream first waits for that one's end event (a no-op on the same stream or after a synchronous call).
+static int ivf_wait_previous(IvfIndex* ix, hipStream_t stream) {
   if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
   return MRAG_OK;
 }
-
-
-int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
-                    int k, float* out_scores, int64_t* out_ids, int out_is_device, void* stream_) {
-  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
-  if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
-  hipStream_t stream = (hipStream_t)stream_;
-  int64_t chunk = 0;
-  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
-  if (nq == 0) return MRAG_OK;
-  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
-  MRAG_TRY(ix->stats.ensure(16));
-  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
-  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device, stream));
+// ... and the end event of this call: the handle's buffers are in use on `stream` until here
+static int ivf_record_end(IvfIndex* ix, hipStream_t stream) {
   MRAG_HIP(hipEventRecord(ix->ev[3], stream));
   ix->end_recorded = true;
-  ix->timed = true;
-  // host buffers (pageable query / result memory) must not be touched by the caller before the copies are done; with
-  // queries and results in device memory the search is fully asynchronous on `stream`
-  if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
 }
-
-}  // extern "C"
-
-namespace mrag {
 
 // inv_pos = original row -> stored position of the current regroup (built once after every regroup)
 static int ivf_ensure_inv_pos(IvfIndex* ix, hipStream_t stream) {
@@ -1015,95 +749,321 @@ static int ivf_ensure_inv_pos(IvfIndex* ix, hipStream_t stream) {
   return MRAG_OK;
 }
 
-// ---- range search ---------------------------------------------------------------------------------------------------------
-// What mrag_ivf_search_range and mrag_ivf_self_join share once their arguments are checked and ivf_search_begin has run:
-// the refusals known before any chunk runs, the excluded rows as stored positions (rows: device int64 [nq], or NULL with
-// self_row0 >= 0 for "query i excludes row self_row0 + i", or neither: no exclusion), the chunks, the timing record.
-static int ivf_range_run(IvfIndex* ix, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
-                         int k, float floor, const int64_t* d_excl_rows, int64_t self_row0, int64_t chunk, float* out_scores,
-                         int64_t* out_ids, int64_t* out_counts, int out_is_device, hipStream_t stream) {
-  if (ivf_scores_cap() <= 0) return ivf_range_unsupported("the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
-  if (nprobe > 256) return ivf_range_unsupported("more than 256 probed lists per query (exhaustive probing with nlist > 256)");
-  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
-  MRAG_TRY(ix->stats.ensure(16));
-  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
-  IvfRangeArgs rg;
-  rg.floor = floor; rg.out_counts = out_counts; rg.stored_rows = self_row0 >= 0;
-  if (d_excl_rows || self_row0 >= 0) {
-    MRAG_TRY(ivf_ensure_inv_pos(ix, stream));
-    int64_t* d_pos = (int64_t*)ix->excl.p + nq;
-    hipLaunchKernelGGL(ivf_excl_pos_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_excl_rows, self_row0, nq, ix->n,
-                       (const int64_t*)ix->inv_pos.p, d_pos);
-    MRAG_HIP(hipGetLastError());
-    rg.excl_pos = d_pos;
-  }
-  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device,
-                          stream, nullptr, nullptr, &rg));
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->end_recorded = true;
-  ix->timed = true;
+// nq, k and nprobe of the plain, filtered and fp8 searches' kind
+static int ivf_check_nq_k(int64_t nq, int k, int nprobe) {
+  if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
+  if (k > bf_max_k()) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds the fused top-k limit %d", k, bf_max_k());
   return MRAG_OK;
 }
-
 static int ivf_check_range_args(int64_t nq, int k, int nprobe, float min_score, const void* out_counts) {
   if (nq < 0 || k <= 0 || nprobe <= 0) return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe");
   if (k > 256) return fail(MRAG_ERR_INVALID, "range search: k = %d, supported are 1..256 (the per-query selection's limit)", k);
-  if (!(min_score == min_score) || min_score - min_score != 0.f) return fail(MRAG_ERR_INVALID, "min_score must be finite");
+  if (!std::isfinite(min_score)) return fail(MRAG_ERR_INVALID, "min_score must be finite");
   if (nq > 0 && !out_counts) return fail(MRAG_ERR_INVALID, "out_counts is NULL");
   return MRAG_OK;
 }
 
-}  // namespace mrag
+// What a search does beyond "the k best rows of the probed lists".  A mode's fields of IvfSearch are read under that mode
+// alone, so these four are all the combinations there are: no filter with a floor, no fp8 scan with either.
+enum IvfMode {
+  IVF_PLAIN,      // the only mode with a fused form: exhaustive probing of > 256 lists, MRAG_IVF_SCORES_MB = 0, oversized segments
+  IVF_FILTERED,   // path P of the filtered search: probes live lists, selects allowed stored positions; score segments without a host round trip only
+  IVF_RANGE,      // lists and counts the rows scoring >= floor; score segments only
+  IVF_FP8,        // scans the fp8 copies, re-scores the `refine` best local rows per query against the 16-bit rows; score segments only
+};
 
-extern "C" {
+// One call of an IVF search entry point: the plumbing mrag_ivf_search, _search_range, _self_join, _search_filtered and
+// _search_fp8 share around their own argument checks and their mode's own work.
+struct IvfSearch {
+  IvfIndex* ix; hipStream_t stream;
+  int64_t nq; int k, nprobe;                        // (nprobe: clamped to nlist by begin)
+  const void* queries; int q_dtype, normalize, queries_is_device;
+  float* out_scores; int64_t* out_ids; int out_is_device;
+  IvfMode mode = IVF_PLAIN;
+  const uint32_t *live_bits = nullptr, *stored_bits = nullptr;   // IVF_FILTERED: bitsets over the lists / the stored positions
+  float floor = 0.f;                       // IVF_RANGE
+  const int64_t* excl_pos = nullptr;       //   per query the stored position of its excluded row (device, or NULL: none)
+  int64_t* out_counts = nullptr;           //   [nq], in the memory space of the other outputs
+  bool stored_rows = false;                //   `queries` are rows of ix->raw (storage dtype, ld apart: the self-join), copied as they are
+  int refine = 0;                          // IVF_FP8
+  int64_t chunk = 0;                       // queries per chunk (begin)
+  const char* what() const { return mode == IVF_FP8 ? "fp8" : "range"; }   // (the modes without a fused form, as the refusals name them)
 
-int mrag_ivf_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
-                          int nprobe, int k, float min_score, const int64_t* exclude_rows, int exclude_is_device,
-                          float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device, void* stream_) {
-  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
-  if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(ivf_check_range_args(nq, k, nprobe, min_score, out_counts));
-  hipStream_t stream = (hipStream_t)stream_;
-  int64_t chunk = 0;
-  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
-  if (nq == 0) return MRAG_OK;
-  const int64_t* d_excl = nullptr;
-  if (exclude_rows) {
-    MRAG_TRY(ix->excl.ensure((size_t)nq * 16));
-    if (exclude_is_device) {
-      d_excl = exclude_rows;
-    } else {
-      for (int64_t i = 0; i < nq; ++i)
-        if (exclude_rows[i] < -1 || exclude_rows[i] >= ix->n)
-          return fail(MRAG_ERR_INVALID, "exclude_rows[%lld] = %lld: a local row 0..%lld or -1", (long long)i, (long long)exclude_rows[i], (long long)ix->n - 1);
-      MRAG_HIP(hipMemcpyAsync(ix->excl.p, exclude_rows, (size_t)nq * 8, hipMemcpyHostToDevice, stream));
-      d_excl = (const int64_t*)ix->excl.p;
-    }
+  // After the entry point's own argument checks: nprobe clamped and checked (nq == 0 stops there: the caller returns),
+  // the buffers, the device, the index finalized, the batch cut into chunks of `chunk` queries, no search timed, `stream`
+  // ordered behind the previous call on this handle.
+  int begin() {
+    nprobe = std::min(nprobe, ix->nlist);
+    // probe selection = top-nprobe over the centroids: the fused kernel up to 64, the streaming kernel up to 256
+    // (8 queries per launch); nprobe == nlist needs no selection at all
+    if (nprobe > bf_max_k_wide() && nprobe < ix->nlist)
+      return fail(MRAG_ERR_UNSUPPORTED, "nprobe = %d: supported are 1..%d and nlist (= %d, exhaustive)", nprobe, bf_max_k_wide(), ix->nlist);
+    if (nq == 0) return MRAG_OK;
+    if (!queries || !out_scores || !out_ids || !esize(q_dtype)) return fail(MRAG_ERR_INVALID, "bad buffer / dtype");
+    if (!ix->has_centroids) return fail(MRAG_ERR_INVALID, "index has no centroids");
+    MRAG_TRY(use_device(ix->device));
+    MRAG_TRY(ivf_finalize(ix, stream));
+    chunk = ivf_chunk_queries(ix, nq, nprobe);
+    if (chunk > (1 << 20)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one IVF batch (2^20); cut the query batch");
+    ix->timed = false;
+    return ivf_wait_previous(ix, stream);
   }
-  MRAG_TRY(ivf_range_run(ix, queries, nq, q_dtype, normalize, queries_is_device, nprobe, k, min_score, d_excl, -1, chunk, out_scores,
-                         out_ids, out_counts, out_is_device, stream));
-  if (!out_is_device || !queries_is_device || (exclude_rows && !exclude_is_device)) MRAG_HIP(hipStreamSynchronize(stream));
+
+  // (range, fp8) the refusals known before any chunk runs; a refused call has recorded nothing
+  int refuse_fused() const {
+    if (ivf_scores_cap() <= 0) return ivf_segments_only(what(), "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
+    if (nprobe > 256) return ivf_segments_only(what(), "more than 256 probed lists per query (exhaustive probing with nlist > 256)");
+    return MRAG_OK;
+  }
+
+  // The search's device work starts here: ev[0], and its device accumulators (rows streamed, workgroups) start at zero.
+  // record_ev0 = false: the filtered search, whose ev[0] filter_upload records behind the host-side packing of a host allow-set.
+  int start(bool record_ev0 = true) {
+    if (record_ev0) MRAG_HIP(hipEventRecord(ix->ev[0], stream));
+    MRAG_TRY(ix->stats.ensure(16));
+    MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
+    return MRAG_OK;
+  }
+
+  // the chunks, one after another; ix->n_chunks is theirs once all have run
+  int run_chunks();
+
+  // (range) start, then the excluded rows as stored positions in ix->excl's second half (sized by the caller) -- rows: device
+  // int64 [nq], or NULL with self_row0 >= 0 for "query i excludes row self_row0 + i", or neither: no exclusion --, then the chunks
+  int run_range(const int64_t* d_excl_rows, int64_t self_row0) {
+    MRAG_TRY(refuse_fused());
+    MRAG_TRY(start());
+    if (d_excl_rows || self_row0 >= 0) {
+      MRAG_TRY(ivf_ensure_inv_pos(ix, stream));
+      int64_t* d_pos = (int64_t*)ix->excl.p + nq;
+      hipLaunchKernelGGL(ivf_excl_pos_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_excl_rows, self_row0, nq, ix->n,
+                         (const int64_t*)ix->inv_pos.p, d_pos);
+      MRAG_HIP(hipGetLastError());
+      excl_pos = d_pos;
+    }
+    return run_chunks();
+  }
+
+  // The search's device work is done: ev[3], the search is timed.  Host buffers (pageable memory) must not be touched by the
+  // caller before the copies are done: the call then returns when they have landed; otherwise it is asynchronous on `stream`.
+  int finish(bool host_buffer_involved) {
+    MRAG_TRY(ivf_record_end(ix, stream));
+    ix->timed = true;
+    if (host_buffer_involved) MRAG_HIP(hipStreamSynchronize(stream));
+    return MRAG_OK;
+  }
+};
+
+// One chunk of a search (<= 2^20 queries): seven stages, run in this order on the search's stream.  The list scan (and the
+// probe selection before it) runs as "score segments + select" (ivf_scan.hip) whenever the fp32 segments of the chunk fit
+// the score buffer; otherwise (exhaustive probing of a big index) as the fused GEMM + top-k kernel in descriptor mode.
+// DevBuf::ensure does not keep contents: every stage sizes a buffer before the chunk's first write into it.
+struct IvfChunk {
+  const IvfSearch& s; IvfIndex* const ix; const hipStream_t stream;
+  const int64_t off, nq;                  // the chunk's queries: [off, off + nq) of the search's
+  const hipEvent_t ev_scan0, ev_scan1;    // bracket the list scan (mrag_ivf_last_timing sums the chunks')
+  const bool rg, f8;                      // the search's mode is IVF_RANGE / IVF_FP8
+  float* d_sc = nullptr; int64_t* d_id = nullptr; int64_t* d_cnt = nullptr;   // stage_outputs: the chunk's results on the device
+  // select_probes: views of ix->plan -- queries per list | first group of the list | cursor | first descriptor |
+  // descriptor count, score floats (low, high) | float offset of the list's score blocks
+  int *d_lcount = nullptr, *d_wg_first = nullptr, *d_cursor = nullptr, *d_dfirst = nullptr, *d_nwg = nullptr;
+  long long* d_foff = nullptr;
+  bool lcount_filled = false;             // select_probes: the probe selection counted the queries per list itself
+  size_t npairs = 0; int64_t wg_bound = 0, desc_bound = 0;   // plan: (query, probe) pairs, bounds of the workgroup and descriptor counts
+  bool use_scores = false, no_sync = false;   // plan: score-segment regime (else fused) / ... without a host round trip: the descriptor count stays on the device
+  bool planned_scores = false; int n_desc = 0;   // plan: a score plan ran (and counted the chunk in ix->stats), whichever regime follows; scan descriptors of a synced one
+
+  IvfChunk(const IvfSearch& s_, int c)
+      : s(s_), ix(s_.ix), stream(s_.stream), off((int64_t)c * s_.chunk), nq(std::min(s_.chunk, s_.nq - off)),
+        ev_scan0(ix->cev[2 * c]), ev_scan1(ix->cev[2 * c + 1]), rg(s_.mode == IVF_RANGE), f8(s_.mode == IVF_FP8) {}
+  unsigned pgrid() const { return (unsigned)((npairs + 255) / 256); }
+  // Needs nothing.  Leaves d_sc / d_id (range: d_cnt) = where the chunk's nq x k results (nq counts) are written: the
+  // caller's buffers, or out_sc / out_id (out_cnt) for host outputs, which copy_back returns.
+  int stage_outputs() {
+    d_sc = s.out_scores + (size_t)off * s.k; d_id = s.out_ids + (size_t)off * s.k;
+    if (rg) d_cnt = s.out_counts + off;
+    if (s.out_is_device) return MRAG_OK;
+    MRAG_TRY(ix->out_sc.ensure((size_t)nq * s.k * 4));
+    MRAG_TRY(ix->out_id.ensure((size_t)nq * s.k * 8));
+    d_sc = (float*)ix->out_sc.p; d_id = (int64_t*)ix->out_id.p;
+    if (rg) { MRAG_TRY(ix->out_cnt.ensure((size_t)nq * 8)); d_cnt = (int64_t*)ix->out_cnt.p; }
+    return MRAG_OK;
+  }
+
+  // Needs nothing.  Leaves ix->qbuf = the chunk's queries in the storage dtype, zero padded to bf_query_rows(nq) rows; fp8:
+  // their quantised image in ix->qbuf8 (zero pad rows too, the scan's pad row nq among them), ix->cand sized for the candidates.
+  int prepare_queries() {
+    const int64_t nq_pad = bf_query_rows(nq);
+    const size_t row = (size_t)ix->ld * 2;
+    MRAG_TRY(ix->qbuf.ensure((size_t)nq_pad * row));
+    MRAG_HIP(hipMemsetAsync((char*)ix->qbuf.p + (size_t)nq * row, 0, (size_t)(nq_pad - nq) * row, stream));
+    if (rg && s.stored_rows)
+      MRAG_HIP(hipMemcpyAsync(ix->qbuf.p, (const char*)s.queries + (size_t)off * row, (size_t)nq * row, hipMemcpyDeviceToDevice, stream));
+    else
+      MRAG_TRY(ivf_prepare(ix, {(const char*)s.queries + (size_t)off * ix->dim * esize(s.q_dtype), nq, s.q_dtype, s.normalize, s.queries_is_device},
+                           (uint16_t*)ix->qbuf.p, stream));
+    if (!f8) return MRAG_OK;
+    MRAG_TRY(ix->qbuf8.ensure((size_t)nq_pad * ix->ld8));
+    MRAG_TRY(launch_quant_queries_fp8((const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, nq_pad, (uint8_t*)ix->qbuf8.p,
+                                      ix->ld8, stream));
+    return ix->cand.ensure((size_t)nq * s.refine * 8);
+  }
+
+  // Needs qbuf.  Leaves the probed lists of every query in ix->tmp_id ([nq][nprobe] list ids, -1: none; filtered: live lists
+  // only), the plan views over ix->plan, d_lcount zeroed -- or, with lcount_filled, already holding the queries per list.
+  int select_probes() {
+    MRAG_TRY(ix->tmp_id.ensure((size_t)nq * s.nprobe * 8));
+    MRAG_TRY(ix->tmp_sc.ensure((size_t)nq * s.nprobe * 4));
+    const int nl = ix->nlist;
+    MRAG_TRY(ix->plan.ensure((size_t)(4 * nl + 4) * 4 + (size_t)nl * 8));
+    d_lcount = (int*)ix->plan.p; d_wg_first = d_lcount + nl; d_cursor = d_wg_first + nl; d_dfirst = d_cursor + nl;
+    d_nwg = d_dfirst + nl; d_foff = (long long*)(d_nwg + 4);
+    MRAG_HIP(hipMemsetAsync(d_lcount, 0, (size_t)nl * 4, stream));
+    if (s.nprobe == nl) {                  // exhaustive: no selection
+      const int64_t np_ = nq * s.nprobe;
+      hipLaunchKernelGGL(ivf_all_lists_kernel, dim3((unsigned)((np_ + 255) / 256)), dim3(256), 0, stream, (int64_t*)ix->tmp_id.p, np_, nl);
+      MRAG_HIP(hipGetLastError());
+    } else if (round_up(nq, IVFS_QUERIES) * ivfs_pitch(nl) * 4 <= ivf_scores_cap()) {   // dense score segments + top-k
+      MRAG_TRY(ix->sdesc.ensure((size_t)ivfs_dense_n_desc(nq, nl) * IVFS_DESC_WORDS * 4));
+      MRAG_TRY(ix->scores.ensure((size_t)(round_up(nq, IVFS_QUERIES) * ivfs_pitch(nl) * 4)));
+      MRAG_TRY(ivfs_dense_topk(ix->cen, nl, (const uint16_t*)ix->qbuf.p, nq, ix->ld, ix->dtype, s.nprobe, (int*)ix->sdesc.p,
+                               (float*)ix->scores.p, (float*)ix->tmp_sc.p, (int64_t*)ix->tmp_id.p, stream, d_lcount,
+                               (const int*)ix->d_list_count.p, s.live_bits));
+      lcount_filled = true;
+    } else {                               // the centroid scores do not fit the score buffer: the fused kernel
+      BfLaunch a = ivf_launch(ix, ix->cen, nl, ix->qbuf.p, nq, stream);
+      a.k = s.nprobe; a.out_scores = (float*)ix->tmp_sc.p; a.out_ids = (int64_t*)ix->tmp_id.p;
+      a.allow = s.live_bits;               // (filtered: dead lists are never probed; a pair without a list gets probe id -1)
+      MRAG_TRY(bf_launch(a));
+    }
+    return MRAG_OK;
+  }
+
+  // Needs the probes and d_lcount (counted here unless lcount_filled).  The one place that decides the regime: leaves
+  // use_scores / no_sync, or the mode's refusal.  With use_scores the score plan has run and ix->scores is sized for the
+  // segments; only a plan whose bound does not fit comes back to the host (12 bytes: n_desc and the size of the segments).
+  int plan() {
+    const int64_t scores_cap = ivf_scores_cap();
+    npairs = (size_t)nq * s.nprobe;
+    wg_bound = (int64_t)std::min<size_t>((size_t)ix->nlist, npairs) + (int64_t)(npairs / IVFS_QUERIES) + 1;   // (covers the 256-query plan too)
+    // score-segment regime: every group is cut into ceil(list rows / IVFS_CHUNK_ROWS) scan descriptors
+    desc_bound = wg_bound * std::max<int64_t>(1, (ix->max_list_rows + IVFS_CHUNK_ROWS - 1) / IVFS_CHUNK_ROWS);
+    MRAG_TRY(ix->desc.ensure((size_t)desc_bound * 8 * 4));
+    MRAG_TRY(ix->gq.ensure((size_t)wg_bound * 256 * 8));
+    MRAG_TRY(ix->ploc.ensure(npairs * 16));   // int2 (fused regime) or int4 (score segments) per pair
+    if (!lcount_filled)
+      hipLaunchKernelGGL(ivf_count_kernel, dim3(pgrid()), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs,
+                         (const int*)ix->d_list_count.p, d_lcount);
+    use_scores = scores_cap > 0 && s.nprobe <= 256;   // (the select kernel holds <= 256 segments per query; exhaustive probing takes the fused path)
+    if ((rg || f8) && !use_scores) return ivf_segments_only(s.what(), scores_cap > 0 ? "more than 256 probed lists per query" : "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
+    // Score floats of this chunk: known exactly only on the device (sum over the probed lists of queries x rows).  When
+    // even the bound "every pair probes the longest list" fits the buffer, nothing comes back to the host at all: the
+    // scan is launched over the BOUND of the descriptor count and reads the real one from device memory.
+    const int64_t max_pitch = ivfs_pitch(ix->max_list_rows);
+    no_sync = use_scores && (int64_t)npairs * max_pitch * 4 <= scores_cap;
+    // (a filtered search only comes here when it fits: mrag_ivf_search_filtered runs path E otherwise)
+    if (s.stored_bits && !no_sync) return fail(MRAG_ERR_INVALID, "filtered IVF chunk does not fit the score buffer");
+    planned_scores = use_scores;
+    if (!use_scores) return MRAG_OK;
+    hipLaunchKernelGGL(ivf_plan_scores_kernel, dim3(1), dim3(1024), 0, stream, (const int*)d_lcount, (const int*)ix->d_list_count.p,
+                       ix->nlist, d_wg_first, d_cursor, d_dfirst, d_foff, d_nwg, (unsigned long long*)ix->stats.p);
+    MRAG_HIP(hipGetLastError());
+    if (no_sync) return ix->scores.ensure((size_t)std::max<int64_t>((int64_t)npairs * max_pitch, 4) * 4);
+    int plan_out[3] = {0, 0, 0};
+    MRAG_HIP(hipMemcpyAsync(plan_out, d_nwg, 12, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+    n_desc = plan_out[0];
+    const int64_t floats = (int64_t)(uint32_t)plan_out[1] | ((int64_t)plan_out[2] << 32);
+    if (n_desc < 0 || n_desc > desc_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", n_desc, (long long)desc_bound);
+    if (floats * 4 > scores_cap && (rg || f8)) return ivf_segments_only(s.what(), "the score segments of one chunk exceed the score buffer (MRAG_IVF_SCORES_MB)");
+    if (floats * 4 > scores_cap) { use_scores = false; return MRAG_OK; }   // (plain search: the fused regime takes the chunk)
+    return ix->scores.ensure((size_t)std::max<int64_t>(floats, 4) * 4);
+  }
+
+  // Needs plan() with use_scores.  Scatters the pairs into their groups, scores every (query, probed list) pair into
+  // ix->scores, selects per query; leaves the results at d_sc / d_id (/ d_cnt) -- fp8: via the candidates' exact re-rank.
+  int scan_scores() {
+    hipLaunchKernelGGL(ivf_scatter_kernel, dim3(pgrid()), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs, s.nprobe,
+                       (const int*)ix->d_list_count.p, (const int*)d_wg_first, d_cursor, (int64_t*)ix->gq.p, nullptr, 7,
+                       (const long long*)d_foff, (const int*)ix->d_list_tile_lo.p, (int4*)ix->ploc.p, (const int*)d_lcount,
+                       (const int*)d_dfirst, (int*)ix->desc.p, (int)desc_bound);
+    MRAG_HIP(hipGetLastError());
+    MRAG_HIP(hipEventRecord(ev_scan0, stream));
+    // (no_sync: the descriptor count stays on the device, the grid is its bound)
+    MRAG_TRY(ivfs_scan(f8 ? (const uint16_t*)ix->sorted8 : ix->sorted, (const uint16_t*)(f8 ? ix->qbuf8.p : ix->qbuf.p),
+                       f8 ? ix->ld8 / 2 : ix->ld, f8 ? MRAG_DT_FP8 : ix->dtype, nq, (const int*)ix->desc.p,
+                       no_sync ? (int)desc_bound : n_desc, no_sync ? d_nwg : nullptr, (const int64_t*)ix->gq.p, (float*)ix->scores.p,
+                       stream));
+    IvfsRange sel_range{s.floor, s.excl_pos ? s.excl_pos + off : nullptr, d_cnt};
+    if (f8)   // candidates: local rows in (fp8 score desc, row asc) order, -1 past the rows of the probed lists
+      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, s.nprobe, nq, s.refine, ix->row_ids, 0, nullptr, (int64_t*)ix->cand.p, stream));
+    else
+      MRAG_TRY(ivfs_select_lists((const float*)ix->scores.p, ix->ploc.p, s.nprobe, nq, s.k, ix->row_ids, ix->id_base, d_sc, d_id, stream,
+                                 s.stored_bits, rg ? &sel_range : nullptr));
+    MRAG_HIP(hipEventRecord(ev_scan1, stream));
+    if (f8)
+      MRAG_TRY(launch_fp8_rerank(ix->raw, (const uint16_t*)ix->qbuf.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)ix->cand.p, nq,
+                                 s.refine, s.k, ix->id_base, d_sc, d_id, stream));
+    return MRAG_OK;
+  }
+
+  // Needs plan() without use_scores (plain search only).  Plans 256-query workgroups, scatters, reads the workgroup count
+  // back (4 bytes), gathers the queries per workgroup and runs the fused kernel in descriptor mode; results at d_sc / d_id.
+  int scan_fused() {
+    MRAG_HIP(hipMemsetAsync(ix->gq.p, 0xFF, (size_t)wg_bound * 256 * 8, stream));   // (the gather below reads whole 256-slot slabs)
+    hipLaunchKernelGGL(ivf_plan_kernel, dim3(1), dim3(1024), 0, stream, (const int*)d_lcount, (const int*)ix->d_list_count.p,
+                       (const int*)ix->d_list_tile_lo.p, ix->nlist, d_wg_first, d_cursor, (int*)ix->desc.p, (int)wg_bound, d_nwg,
+                       planned_scores ? nullptr : (unsigned long long*)ix->stats.p);   // (a scores plan that turned out too big has already counted this chunk)
+    hipLaunchKernelGGL(ivf_scatter_kernel, dim3(pgrid()), dim3(256), 0, stream, (const int64_t*)ix->tmp_id.p, (int64_t)npairs, s.nprobe,
+                       (const int*)ix->d_list_count.p, (const int*)d_wg_first, d_cursor, (int64_t*)ix->gq.p, (int2*)ix->ploc.p, 8,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    MRAG_HIP(hipGetLastError());
+    int n_wg = -1;
+    MRAG_HIP(hipMemcpyAsync(&n_wg, d_nwg, 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+    if (n_wg < 0 || n_wg > wg_bound) return fail(MRAG_ERR_HIP, "IVF plan produced %d workgroups (bound %lld)", n_wg, (long long)wg_bound);
+    if (n_wg) {
+      MRAG_TRY(ix->qg.ensure((size_t)n_wg * 256 * ix->ld * 2));
+      const int64_t ng = (int64_t)n_wg * 256;
+      hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ng + 3) / 4)), dim3(256), 0, stream, (const uint16_t*)ix->qbuf.p,
+                         (const int64_t*)ix->gq.p, ng, ix->ld, (uint16_t*)ix->qg.p, 0);
+      MRAG_HIP(hipGetLastError());
+    }
+    BfLaunch a = ivf_launch(ix, ix->sorted, 0, ix->qg.p, nq, stream);
+    a.k = s.k; a.out_scores = d_sc; a.out_ids = d_id; a.id_base = ix->id_base;
+    static const int dummy_desc = 0;
+    a.wg_desc = n_wg ? (const int*)ix->desc.p : &dummy_desc; a.n_wg = n_wg;
+    a.pair_loc = ix->ploc.p; a.nprobe = s.nprobe; a.row_ids = ix->row_ids;
+    a.ev_k2_begin = ev_scan0; a.ev_k2_end = ev_scan1;
+    return bf_launch(a);
+  }
+
+  // Needs the results at d_sc / d_id (/ d_cnt).  Host outputs: their copies are queued (the search synchronises at its end).
+  int copy_back() const {
+    if (s.out_is_device) return MRAG_OK;
+    if (rg) MRAG_HIP(hipMemcpyAsync(s.out_counts + off, d_cnt, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(s.out_scores + (size_t)off * s.k, d_sc, (size_t)nq * s.k * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(s.out_ids + (size_t)off * s.k, d_id, (size_t)nq * s.k * 8, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  }
+
+  int run() {
+    MRAG_TRY(stage_outputs());
+    MRAG_TRY(prepare_queries());
+    MRAG_TRY(select_probes());
+    MRAG_TRY(plan());
+    MRAG_TRY(use_scores ? scan_scores() : scan_fused());
+    return copy_back();
+  }
+};
+
+int IvfSearch::run_chunks() {
+  const int n_chunks = (int)((nq + chunk - 1) / chunk);
+  MRAG_TRY(ivf_grow_cev(ix, n_chunks));
+  for (int c = 0; c < n_chunks; ++c) MRAG_TRY(IvfChunk(*this, c).run());
+  ix->n_chunks = n_chunks;
   return MRAG_OK;
 }
-
-int mrag_ivf_self_join(mrag_handle h, int64_t row0, int64_t n, int nprobe, int k, float min_score, float* out_scores, int64_t* out_ids,
-                       int64_t* out_counts, void* stream_) {
-  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
-  if (!ix) return MRAG_ERR_INVALID;
-  MRAG_TRY(ivf_check_range_args(n, k, nprobe, min_score, out_counts));
-  if (row0 < 0 || row0 + n > ix->n) return fail(MRAG_ERR_INVALID, "self-join rows [%lld, %lld) outside the %lld stored rows", (long long)row0, (long long)(row0 + n), (long long)ix->n);
-  hipStream_t stream = (hipStream_t)stream_;
-  int64_t chunk = 0;
-  const void* rows = n ? (const void*)(ix->raw + (size_t)row0 * ix->ld) : nullptr;
-  MRAG_TRY(ivf_search_begin(ix, rows, n, ix->dtype, out_scores, out_ids, stream, &nprobe, &chunk));
-  if (n == 0) return MRAG_OK;
-  MRAG_TRY(ix->excl.ensure((size_t)n * 16));
-  return ivf_range_run(ix, rows, n, ix->dtype, 0, 1, nprobe, k, min_score, nullptr, row0, chunk, out_scores, out_ids, out_counts, 1, stream);
-}
-
-}  // extern "C"
-
-namespace mrag {
 
 // ---- filtered search: AUTO's choice between path P (probe the live lists) and path E (filtered brute force) ------------
 // P scans ~ nprobe * n / nlist rows per query whatever the allow-set; E scans the m allowed rows (the dense filtered search
@@ -1112,8 +1072,8 @@ namespace mrag {
 constexpr double IVF_FILTER_C_BATCH = 8.0;     // 10 000 queries: E and P cross at 5-10 % of the rows (c ~ 9)
 constexpr double IVF_FILTER_C_STREAM = 24.0;   // 1 and 16 queries: they cross at ~20-25 % (c ~ 25)
 constexpr int64_t IVF_FILTER_STREAM_NQ = 16;   // batches up to this many queries count as the streaming regime
-static int ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t n, int64_t m, int dim) {
-  (void)k; (void)dim;            // (both paths pay them alike: the dot products per row, the top-k per query)
+// (k and dim do not enter: both paths pay them alike, the dot products per row and the top-k per query)
+static int ivf_choose_filter_path(int64_t nq, int nprobe, int nlist, int64_t n, int64_t m) {
   if (nprobe >= nlist) return MRAG_IVF_FILTER_EXACT;
   const double probed = (double)nprobe * (double)n / (double)nlist;
   return (double)m <= (nq <= IVF_FILTER_STREAM_NQ ? IVF_FILTER_C_STREAM : IVF_FILTER_C_BATCH) * probed ? MRAG_IVF_FILTER_EXACT : MRAG_IVF_FILTER_PROBE;
@@ -1146,11 +1106,67 @@ static int check_ivf_allow_args(IvfIndex* ix, const void* allow, int64_t allow_r
 
 extern "C" {
 
+int mrag_ivf_search(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
+                    int k, float* out_scores, int64_t* out_ids, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
+  IvfSearch s{ix, (hipStream_t)stream_, nq, k, nprobe, queries, q_dtype, normalize, queries_is_device, out_scores, out_ids, out_is_device};
+  MRAG_TRY(s.begin());
+  if (nq == 0) return MRAG_OK;
+  MRAG_TRY(s.start());
+  MRAG_TRY(s.run_chunks());
+  return s.finish(!out_is_device || !queries_is_device);
+}
+
+int mrag_ivf_search_range(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                          int nprobe, int k, float min_score, const int64_t* exclude_rows, int exclude_is_device,
+                          float* out_scores, int64_t* out_ids, int64_t* out_counts, int out_is_device, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(ivf_check_range_args(nq, k, nprobe, min_score, out_counts));
+  IvfSearch s{ix, (hipStream_t)stream_, nq, k, nprobe, queries, q_dtype, normalize, queries_is_device, out_scores, out_ids, out_is_device};
+  s.mode = IVF_RANGE; s.floor = min_score; s.out_counts = out_counts;
+  MRAG_TRY(s.begin());
+  if (nq == 0) return MRAG_OK;
+  const int64_t* d_excl = nullptr;
+  if (exclude_rows) {
+    MRAG_TRY(ix->excl.ensure((size_t)nq * 16));
+    if (exclude_is_device) {
+      d_excl = exclude_rows;
+    } else {
+      for (int64_t i = 0; i < nq; ++i)
+        if (exclude_rows[i] < -1 || exclude_rows[i] >= ix->n)
+          return fail(MRAG_ERR_INVALID, "exclude_rows[%lld] = %lld: a local row 0..%lld or -1", (long long)i, (long long)exclude_rows[i], (long long)ix->n - 1);
+      MRAG_HIP(hipMemcpyAsync(ix->excl.p, exclude_rows, (size_t)nq * 8, hipMemcpyHostToDevice, s.stream));
+      d_excl = (const int64_t*)ix->excl.p;
+    }
+  }
+  MRAG_TRY(s.run_range(d_excl, -1));
+  return s.finish(!out_is_device || !queries_is_device || (exclude_rows && !exclude_is_device));
+}
+
+int mrag_ivf_self_join(mrag_handle h, int64_t row0, int64_t n, int nprobe, int k, float min_score, float* out_scores, int64_t* out_ids,
+                       int64_t* out_counts, void* stream_) {
+  IvfIndex* ix = (IvfIndex*)lookup(h, KIND_IVF);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(ivf_check_range_args(n, k, nprobe, min_score, out_counts));
+  if (row0 < 0 || row0 + n > ix->n) return fail(MRAG_ERR_INVALID, "self-join rows [%lld, %lld) outside the %lld stored rows", (long long)row0, (long long)(row0 + n), (long long)ix->n);
+  const void* rows = n ? (const void*)(ix->raw + (size_t)row0 * ix->ld) : nullptr;
+  IvfSearch s{ix, (hipStream_t)stream_, n, k, nprobe, rows, ix->dtype, 0, 1, out_scores, out_ids, 1};
+  s.mode = IVF_RANGE; s.floor = min_score; s.out_counts = out_counts; s.stored_rows = true;
+  MRAG_TRY(s.begin());
+  if (n == 0) return MRAG_OK;
+  MRAG_TRY(ix->excl.ensure((size_t)n * 16));
+  MRAG_TRY(s.run_range(nullptr, row0));
+  return s.finish(false);   // (everything on the device: never synchronises)
+}
+
 int mrag_ivf_choose_filter_path(int64_t nq, int k, int nprobe, int nlist, int64_t total_rows, int64_t allowed_rows, int dim, int* out_path) {
   if (!out_path) return fail(MRAG_ERR_INVALID, "out_path is NULL");
   if (nq < 0 || k <= 0 || nprobe <= 0 || nlist <= 0 || total_rows < 0 || allowed_rows < 0 || allowed_rows > total_rows || dim <= 0)
     return fail(MRAG_ERR_INVALID, "bad nq / k / nprobe / nlist / rows / dim");
-  *out_path = ivf_choose_filter_path(nq, k, nprobe, nlist, total_rows, allowed_rows, dim);
+  *out_path = ivf_choose_filter_path(nq, nprobe, nlist, total_rows, allowed_rows);
   return MRAG_OK;
 }
 
@@ -1163,15 +1179,13 @@ int mrag_ivf_allowed_per_list(mrag_handle h, const void* allow, int64_t allow_ro
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
   MRAG_TRY(ivf_finalize(ix, stream));
-  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  MRAG_TRY(ivf_wait_previous(ix, stream));
   int64_t m = -1;
   MRAG_TRY(filter_upload(ix->fw, allow, ix->n, allow_format, allow_is_device, false, &m, ix->ev[1], stream));
   MRAG_TRY(ivf_filter_stored(ix, stream));
   MRAG_HIP(hipMemcpyAsync(out_counts, flist_counts(ix), (size_t)ix->nlist * 4, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-  // (the handle's buffers are in use on `stream` until here: a later search on another stream waits for it)
   ix->timed = false;
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->end_recorded = true;
+  MRAG_TRY(ivf_record_end(ix, stream));
   if (!out_is_device || !allow_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
 }
@@ -1184,19 +1198,20 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
   if (!ix) return MRAG_ERR_INVALID;
   MRAG_TRY(ivf_check_nq_k(nq, k, nprobe));
   MRAG_TRY(check_ivf_allow_args(ix, allow, allow_rows, allow_format, path));
-  hipStream_t stream = (hipStream_t)stream_;
-  int64_t chunk = 0;
-  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  IvfSearch s{ix, (hipStream_t)stream_, nq, k, nprobe, queries, q_dtype, normalize, queries_is_device, out_scores, out_ids, out_is_device};
+  MRAG_TRY(s.begin());
   if (nq == 0) return MRAG_OK;
+  hipStream_t stream = s.stream;
   ix->last_fpath = -1;
-  // path P runs the score-segment regime only, every chunk without a host round trip (ivf_search_chunk's no_sync case);
+  // path P runs the score-segment regime only, every chunk without a host round trip (IvfChunk::plan's no_sync case);
   // where that does not hold (nprobe == nlist, MRAG_IVF_SCORES_MB = 0, segments too big) the search runs path E
   const int64_t cap = ivf_scores_cap();
-  const bool probe_fits = cap > 0 && nprobe < ix->nlist && chunk * nprobe * ivfs_pitch(ix->max_list_rows) * 4 <= cap;
+  const bool probe_fits = cap > 0 && s.nprobe < ix->nlist && s.chunk * s.nprobe * ivfs_pitch(ix->max_list_rows) * 4 <= cap;
   const int64_t n = ix->n;
   int64_t m = -1;
+  // (ev[0], the search's start, is recorded in there: behind the host-side packing of a host allow-set)
   MRAG_TRY(filter_upload(ix->fw, allow, n, allow_format, allow_is_device, path != MRAG_IVF_FILTER_PROBE, &m, ix->ev[0], stream));
-  int chosen = path != MRAG_IVF_FILTER_AUTO ? path : ivf_choose_filter_path(nq, k, nprobe, ix->nlist, n, m, ix->dim);
+  int chosen = path != MRAG_IVF_FILTER_AUTO ? path : ivf_choose_filter_path(nq, s.nprobe, ix->nlist, n, m);
   if (!probe_fits) chosen = MRAG_IVF_FILTER_EXACT;
   if (chosen == MRAG_IVF_FILTER_EXACT && m < 0) {   // (forced P that cannot run as P, device allow-set: E needs the count)
     int hm = 0;
@@ -1204,30 +1219,27 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
     MRAG_HIP(hipStreamSynchronize(stream));
     m = hm;
   }
-  MRAG_TRY(ix->stats.ensure(16));
-  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
+  MRAG_TRY(s.start(false));
   MRAG_TRY(ivf_grow_cev(ix, 1));
   int live = -2;
   if (chosen == MRAG_IVF_FILTER_EXACT || m == 0) {
-    float* d_sc; int64_t* d_id;
-    MRAG_TRY(ivf_stage_outputs(ix, nq, k, out_scores, out_ids, out_is_device, &d_sc, &d_id));
+    s.chunk = nq;                        // one chunk, whatever nq: its outputs, its queries, its scan events cev[0..1]
+    IvfChunk e(s, 0);
+    MRAG_TRY(e.stage_outputs());
     if (m == 0) {                      // nothing allowed: no search kernel
-      MRAG_HIP(hipEventRecord(ix->cev[0], stream));
-      MRAG_TRY(launch_fill_empty(d_sc, d_id, nq * k, stream));
-      MRAG_HIP(hipEventRecord(ix->cev[1], stream));
+      MRAG_HIP(hipEventRecord(e.ev_scan0, stream));
+      MRAG_TRY(launch_fill_empty(e.d_sc, e.d_id, nq * k, stream));
+      MRAG_HIP(hipEventRecord(e.ev_scan1, stream));
     } else {
       // path E: the dense filtered search over the rows in arrival order (ix->raw: whole zeroed 256-row tiles), ids = row + id_base
-      MRAG_TRY(ivf_prep_queries(ix, queries, nq, q_dtype, normalize, queries_is_device, stream));
-      BfLaunch a;
-      a.corpus = ix->raw; a.queries = (const uint16_t*)ix->qbuf.p; a.ld = ix->ld; a.dtype = ix->dtype; a.k = k;
-      a.nq = nq; a.n_rows = n; a.id_base = ix->id_base;
-      a.out_scores = d_sc; a.out_ids = d_id;
-      a.lists = &ix->lists; a.counts = &ix->counts; a.stream = stream;
-      a.ev_k2_begin = ix->cev[0]; a.ev_k2_end = ix->cev[1];
+      MRAG_TRY(e.prepare_queries());
+      BfLaunch a = ivf_launch(ix, ix->raw, n, ix->qbuf.p, nq, stream);
+      a.k = k; a.out_scores = e.d_sc; a.out_ids = e.d_id; a.id_base = ix->id_base;
+      a.ev_k2_begin = e.ev_scan0; a.ev_k2_end = e.ev_scan1;
       MRAG_TRY(filter_search(ix->fw, a, filter_choose_path(nq, k, n, m, ix->ld), m, stream));
     }
     ix->n_chunks = 1;
-    MRAG_TRY(ivf_copy_back(nq, k, out_scores, out_ids, out_is_device, d_sc, d_id, stream));
+    MRAG_TRY(e.copy_back());
     if (m == 0) live = 0;
   } else {
     // path P: allow-set -> stored positions + per-list counts; liveness from those counts or the caller's (sharded: global)
@@ -1251,21 +1263,18 @@ int mrag_ivf_search_filtered(mrag_handle h, const void* queries, int64_t nq, int
     hipLaunchKernelGGL(ivf_live_bits_kernel, dim3((unsigned)(bf_round_rows(ix->nlist) / 256)), dim3(256), 0, stream, cnt, ix->nlist,
                        flist_live(ix), flist_nlive(ix));
     MRAG_HIP(hipGetLastError());
-    MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device,
-                            stream, (const uint32_t*)flist_live(ix), (const uint32_t*)ix->fstored.p));
+    s.mode = IVF_FILTERED; s.live_bits = flist_live(ix); s.stored_bits = (const uint32_t*)ix->fstored.p;
+    MRAG_TRY(s.run_chunks());
     // the figures last_filter reports, kept apart from the words the next call overwrites (no sync here)
     MRAG_TRY(ix->flast.ensure(8));
     MRAG_HIP(hipMemcpyAsync(ix->flast.p, ix->fw.fwork.p, 4, hipMemcpyDeviceToDevice, stream));
     MRAG_HIP(hipMemcpyAsync((int*)ix->flast.p + 1, flist_nlive(ix), 4, hipMemcpyDeviceToDevice, stream));
     live = -1;
   }
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->end_recorded = true;
-  ix->timed = true;
+  MRAG_TRY(s.finish(!out_is_device || !queries_is_device));
   ix->last_fpath = chosen;
   ix->last_fallowed = m;
   ix->last_flive = live;
-  if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
 }
 
@@ -1316,7 +1325,7 @@ int mrag_ivf_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, 
   MRAG_TRY(use_device(ix->device));
   hipStream_t stream = (hipStream_t)stream_;
   MRAG_TRY(ivf_finalize(ix, stream));
-  if (ix->end_recorded) MRAG_HIP(hipStreamWaitEvent(stream, ix->ev[3], 0));
+  MRAG_TRY(ivf_wait_previous(ix, stream));
   MRAG_TRY(ivf_ensure_inv_pos(ix, stream));
   const int64_t tot = n * ix->dim;
   uint8_t* d_out = out;
@@ -1329,11 +1338,8 @@ int mrag_ivf_get_rows_fp8(mrag_handle h, int64_t row0, int64_t n, uint8_t* out, 
   if (e == hipSuccess && !out_is_device) e = hipStreamSynchronize(stream);
   tmp.release();
   if (e != hipSuccess) return fail(MRAG_ERR_HIP, "reading the fp8 rows failed: %s", hipGetErrorString(e));
-  // (inv_pos is in use on `stream` until here: a later search on another stream waits for it)
   ix->timed = false;
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->end_recorded = true;
-  return MRAG_OK;
+  return ivf_record_end(ix, stream);   // (inv_pos is in use on `stream` until here)
 }
 
 int mrag_ivf_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device, int nprobe,
@@ -1345,23 +1351,15 @@ int mrag_ivf_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_dt
   if (k < 1 || k > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "fp8 search serves 1 <= k <= %d, got %d", FP8_MAX_REFINE, k);
   if (refine == 0) MRAG_TRY(mrag_index_fp8_default_refine(k, &refine));
   if (refine < k || refine > FP8_MAX_REFINE) return fail(MRAG_ERR_INVALID, "refine = %d outside k..%d (k = %d)", refine, FP8_MAX_REFINE, k);
-  hipStream_t stream = (hipStream_t)stream_;
-  int64_t chunk = 0;
-  MRAG_TRY(ivf_search_begin(ix, queries, nq, q_dtype, out_scores, out_ids, stream, &nprobe, &chunk));
+  IvfSearch s{ix, (hipStream_t)stream_, nq, k, nprobe, queries, q_dtype, normalize, queries_is_device, out_scores, out_ids, out_is_device};
+  s.mode = IVF_FP8; s.refine = refine;
+  MRAG_TRY(s.begin());
   if (nq == 0) return MRAG_OK;
-  // the refusals known before any chunk runs
-  if (ivf_scores_cap() <= 0) return ivf_segments_only("fp8", "the score buffer is disabled (MRAG_IVF_SCORES_MB = 0)");
-  if (nprobe > 256) return ivf_segments_only("fp8", "more than 256 probed lists per query (exhaustive probing with nlist > 256)");
-  MRAG_HIP(hipEventRecord(ix->ev[0], stream));
-  MRAG_TRY(ix->stats.ensure(16));
-  MRAG_HIP(hipMemsetAsync(ix->stats.p, 0, 16, stream));
-  MRAG_TRY(ivf_run_chunks(ix, queries, nq, chunk, q_dtype, normalize, queries_is_device, nprobe, k, out_scores, out_ids, out_is_device, stream,
-                          nullptr, nullptr, nullptr, refine));
-  MRAG_HIP(hipEventRecord(ix->ev[3], stream));
-  ix->end_recorded = true;
-  ix->timed = true;
+  MRAG_TRY(s.refuse_fused());
+  MRAG_TRY(s.start());
+  MRAG_TRY(s.run_chunks());
+  MRAG_TRY(s.finish(!out_is_device || !queries_is_device));
   ix->last_refine = refine;
-  if (!out_is_device || !queries_is_device) MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
 }
 

@@ -181,6 +181,105 @@ def test_fused_regime_gives_the_same_answer():
                 assert np.array_equal(res["scores"][key], res[other][key]), (key, other)
 
 
+_PLAN_CHILD = '''
+import sys, numpy as np
+sys.path.insert(0, ".")
+from oracle import dense_search as ds
+from mrag_amd.index import IVFFlatIndex
+from mrag_amd._native import MragError
+d, nlist, nprobe, k = 64, 32, 4, 10
+rng = np.random.default_rng(62)
+base = ds.normalize_round(ds.make_clustered(6000, 1, d, 61, n_centroids=32)[0])
+cen = ds.kmeans_spherical(base, nlist, 3, seed=2)          # (over the clustered rows alone: the copies all join one list)
+v = base[0].astype(np.float32)
+copies = ds.normalize_round(v + np.float32(0.005) * rng.standard_normal((8600, d), dtype=np.float32))
+c16 = np.concatenate([base, copies], axis=0)[rng.permutation(6000 + 8600)]
+ix = IVFFlatIndex(d, nlist); ix.set_centroids(cen, normalize=False); ix.add(c16, normalize=False)
+ix8 = IVFFlatIndex(d, nlist, fp8_scan=True); ix8.set_centroids(cen, normalize=False); ix8.add(c16, normalize=False)
+counts = np.bincount(ix.assignments(), minlength=nlist)
+L = int(np.argmax(counts))
+def probes(q):
+    return np.argsort(-(q.astype(np.float64) @ cen.astype(np.float64).T), axis=1, kind="stable")[:, :nprobe]
+cand = ds.normalize_round(base[rng.integers(0, 6000, size=4000)].astype(np.float32) + np.float32(0.01) * rng.standard_normal((4000, d), dtype=np.float32))
+qa = cand[~(probes(cand) == L).any(axis=1)][:1200]
+qb = ds.normalize_round(cen[L].astype(np.float32) + np.float32(0.01) * rng.standard_normal((1200, d), dtype=np.float32))
+out = {"counts": counts, "L": L, "probes_a": probes(qa), "probes_b": probes(qb)}
+def run(name, fn):
+    try:
+        res = fn()
+        out[name + "_code"] = 0
+        for j, r in enumerate(res):
+            out["%s_%d" % (name, j)] = r
+    except MragError as e:
+        out[name + "_code"] = e.code; out[name + "_msg"] = str(e)
+for s, q in (("a", qa), ("b", qb)):
+    run("plain_" + s, lambda: ix.search(q, k, nprobe, normalize=False))
+    run("range_" + s, lambda: ix.range_search(q, 0.6, k, nprobe, normalize=False))
+    run("fp8_" + s, lambda: ix8.search(q, k, nprobe, normalize=False, precision="fp8"))
+np.savez(sys.argv[1], **out)
+'''
+
+
+def test_synced_plan_fits_falls_back_or_refuses():
+    """The host-synced score plan of a chunk (the bound "every pair probes the longest list" exceeds the score buffer, so
+    the plan's 12 bytes come back): segments that fit stay in the score-segment regime, segments that do not send the plain
+    search to the fused regime -- same answer bit for bit -- and are refused by the range and fp8 searches, which have no
+    fused form.  One list L holds 8 600 near-copies of one direction next to ~190-row lists; under MRAG_IVF_SCORES_MB=16
+    the 1 200 queries of either set run as chunks of 640 and 560 queries.  Set A never probes L (about 2 MB of segments per
+    chunk), every query of set B does (about 21 MB; 8 600 copies rather than 8 000 so that the 560-query chunk clears the
+    buffer by 20 % as well).  The preconditions are asserted from the index's own assignments and a host top-nprobe over
+    the centroids, each with 20 % to spare: an fp near-tie may move a probe."""
+    import os, subprocess, sys, tempfile
+    cap, nq, nprobe, nlist = 16 << 20, 1200, 4, 32
+    with tempfile.TemporaryDirectory() as td:
+        res = {}
+        for mode, env in (("default", {}), ("small", {"MRAG_IVF_SCORES_MB": "16"})):
+            path = os.path.join(td, mode + ".npz")
+            subprocess.run([sys.executable, "-c", _PLAN_CHILD, path], check=True, env={**os.environ, **env},
+                           cwd=os.path.dirname(os.path.dirname(__file__)), timeout=600)
+            res[mode] = dict(np.load(path))
+    dflt, small = res["default"], res["small"]
+    # the preconditions, by the arithmetic of the chunking rule and of the score plan (csrc/ivf.hip)
+    counts = small["counts"]
+    pitch = (counts + 31) // 32 * 32
+    assert counts[int(small["L"])] >= 8000 and counts.max() == counts[int(small["L"])]
+    per_query = max(min(nprobe, 256) * int(pitch.max()), (nlist + 31) // 32 * 32) * 4
+    chunk = max(1024, cap // per_query // 128 * 128)
+    assert nq > chunk
+    n_chunks = (nq + chunk - 1) // chunk
+    chunk = ((nq + n_chunks - 1) // n_chunks + 127) // 128 * 128
+    assert (n_chunks, chunk) == (2, 640)
+    for lo in range(0, nq, chunk):
+        m = min(chunk, nq - lo)
+        assert m * nprobe * int(pitch.max()) * 4 > 1.2 * cap                      # the plan is host-synced
+        seg_a = int(pitch[small["probes_a"][lo:lo + m]].sum()) * 4
+        seg_b = int(pitch[small["probes_b"][lo:lo + m]].sum()) * 4
+        print("chunk at %d: %d queries, bound %d B, set A %d B, set B %d B, buffer %d B" % (lo, m, m * nprobe * int(pitch.max()) * 4, seg_a, seg_b, cap))
+        assert seg_a * 1.2 <= cap                                                 # A fits: score-segment regime
+        assert seg_b > 1.2 * cap                                                  # B does not: fused regime / refusal
+    assert small["probes_a"].shape == (nq, nprobe) and small["probes_b"].shape == (nq, nprobe)
+    # with the default buffer everything runs
+    for key in ("plain_a", "plain_b", "range_a", "range_b", "fp8_a", "fp8_b"):
+        assert int(dflt[key + "_code"]) == 0, (key, dflt.get(key + "_msg"))
+    # the plain search: same scores and ids whichever way the plan went
+    for s in ("a", "b"):
+        assert int(small["plain_%s_code" % s]) == 0
+        for j in (0, 1):
+            assert np.array_equal(small["plain_%s_%d" % (s, j)], dflt["plain_%s_%d" % (s, j)]), (s, j)
+        assert (dflt["plain_%s_1" % s][:, 0] >= 0).all()
+    # set A: range and fp8 run and equal their default-buffer results exactly
+    for j in (0, 1, 2):
+        assert np.array_equal(small["range_a_%d" % j], dflt["range_a_%d" % j]), j
+    for j in (0, 1):
+        assert np.array_equal(small["fp8_a_%d" % j], dflt["fp8_a_%d" % j]), j
+    assert int(small["range_a_code"]) == 0 and int(small["fp8_a_code"]) == 0
+    # set B: both are refused, and say which knob to turn
+    for key in ("range_b", "fp8_b"):
+        msg = str(small[key + "_msg"])
+        assert int(small[key + "_code"]) == -5 and "MRAG_ERR_UNSUPPORTED" in msg and "MRAG_IVF_SCORES_MB" in msg, (key, msg)
+        assert "the score segments of one chunk exceed the score buffer" in msg, (key, msg)
+
+
 def test_bf16_storage_and_exact_integer_ties():
     """bf16 storage through the score-segment scan, and small-integer rows (inner product): every partial sum is exact
     in fp32, so scores and ids must equal the oracle's exactly -- ties, which are many, included."""
