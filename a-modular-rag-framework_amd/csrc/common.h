@@ -70,7 +70,7 @@ constexpr int MRAG_DT_FP8 = 16;
 
 #if defined(__HIPCC__)
 // The block-scaled 16x16x128 MFMA (2x the fp16 MFMA rate; the unscaled _fp8_fp8 forms run at the fp16 rate) with e4m3 A
-// and B (format 0) and neutral E8M0 scales (127 = 2^0), shared by the fp8 instances of the dense kernels (bf_index.hip) and
+// and B (format 0) and neutral E8M0 scales (127 = 2^0), shared by the fp8 instances of the dense kernels (bf_batch.hip, bf_stream.hip) and
 // of the IVF list scan (ivf_scan.hip).  A 128-element K step is the 128 bytes per row a 16-bit K step stages, so the stage
 // layout and the two 16-byte fragment reads (k halves ph0 / ph1) stay; the two reads form one 32-byte operand.  Which k a
 // register byte stands for does not matter as long as A and B read alike.
@@ -87,7 +87,7 @@ struct MfmaFp8 {
 };
 #endif
 
-// The fp8 quantisers and the exact re-rank (bf_index.hip), shared by mrag_index_search_fp8 and mrag_ivf_search_fp8; all
+// The fp8 quantisers and the exact re-rank (bf_fp8.hip), shared by mrag_index_search_fp8 and mrag_ivf_search_fp8; all
 // pointers are device pointers.
 constexpr int FP8_K = 128;            // elements per fp8 K step (the 128 bytes per row a 16-bit K step stages)
 constexpr int FP8_MAX_REFINE = 64;    // candidates per query: the batch kernel's list limit
@@ -101,7 +101,7 @@ int launch_fp8_rerank(const uint16_t* rows, const uint16_t* queries, int ld, int
                       int k, int64_t id_base, float* out_sc, int64_t* out_id, hipStream_t stream);
 
 // One fused similarity + top-k pass (K2) and the candidate merge (K4) over PREPARED operands
-// (storage dtype, padded to `ld`, query buffer padded to a multiple of 256 rows).
+// (storage dtype, padded to `ld`, query buffer padded to a multiple of 256 rows); bf_launch is in bf_index.hip.
 struct BfLaunch {
   const uint16_t* corpus = nullptr;   // [rows padded to 256][ld]
   const uint16_t* queries = nullptr;  // dense: [ceil(nq/256)*256][ld]; descriptor mode: gathered [n_wg*256][ld]
@@ -133,7 +133,7 @@ struct BfLaunch {
 };
 int bf_launch(const BfLaunch& a);
 
-// Filtered dense search over prepared operands (bf_index.hip), shared by mrag_index_search_filtered and the exact path
+// Filtered dense search over prepared operands (bf_filter.hip), shared by mrag_index_search_filtered and the exact path
 // of mrag_ivf_search_filtered.
 struct FilterWork {
   DevBuf fbits;                       // allow-set bitset over the corpus rows, padded with zero words to whole 256-row tiles

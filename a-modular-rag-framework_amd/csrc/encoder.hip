@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void enc_gemm_skinny_kernel(const uint16_t* __
 
 // ------------------------------------------------------------------ 256 x 256 persistent GEMM (the K2 main loop)
 // Used when N_pad % 256 == 0 and M_pad % 256 == 0.  Same structure as the similarity kernel of
-// bf_index.hip: 8 waves (2 x 4), 256 x 256 x 64 stages through LDS-DMA issued from inline asm (scalar
+// bf_batch.hip: 8 waves (2 x 4), 256 x 256 x 64 stages through LDS-DMA issued from inline asm (scalar
 // base + 32-bit voffset, XOR swizzle on the source address), two fragment register sets so that the
 // MFMA pipe never waits on a read it has just issued, zero C operand on the first K step of a tile,
 // one barrier per K step.  Workgroups are persistent: each walks tiles lin = first, first + stride, ...

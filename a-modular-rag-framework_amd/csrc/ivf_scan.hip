@@ -1,7 +1,7 @@
 // IVF-flat, "score segments + select" regime (BASELINE.json config 5; the reference has no IVF index).
 //
 // The list scan of an IVF search is many SMALL similarity problems: ~150 rows x ~80 queries per list at
-// nlist 4096 / nprobe 32 / 10 000 queries.  The fused GEMM + top-k kernel (bf_index.hip, descriptor mode)
+// nlist 4096 / nprobe 32 / 10 000 queries.  The fused GEMM + top-k kernel (bf_batch.hip, descriptor mode)
 // spends them one 256 x 256 workgroup per CU at a time: its K loop waits out an HBM round trip per K step
 // and its top-k bootstrap / end-of-split compaction costs as much as the scores (IVF section).
 // Here the two halves are separate kernels:

@@ -47,7 +47,7 @@ def test_k_above_64_matches_oracle(nq, n, d, k):
 def test_wide_batch_k_above_64(k):
     """Batch evaluation with the reference's pool (retrieval_backend.py:218: 200 candidates) -- more than 32 queries with
     64 < k <= 256: the batch kernel at k' = 64 per corpus split + merge + the exactness check, flagged queries redone by the
-    streaming kernel (csrc/bf_index.hip bf_wide_verify_kernel).  i.i.d. rows: (almost) nothing is flagged; then rows stored
+    streaming kernel (csrc/bf_merge.hip bf_wide_verify_kernel).  i.i.d. rows: (almost) nothing is flagged; then rows stored
     cluster by cluster with k neighbours inside ONE cluster -- one split holds a query's whole top k, everything it touches is
     flagged and redone -- and exact integer ties.  Always the oracle's answer."""
     from mrag_amd.index import DenseIndex
@@ -253,6 +253,21 @@ for k in (10, 64, 200):
     sc, ids = ix.search(q16, k, normalize=False)
     rv, ri = ds.brute_force_topk(q16, c16, k)
     assert np.allclose(sc, rv, rtol=0, atol=1e-5) and ds.gap_aware_id_match(ids, sc, ri, rv, tol=1e-5)[1] == 0, k
+# k beyond the corpus (one region, total <= k: no select, the tail pads): the oracle's 150 entries, then exactly (-inf, -1)
+cs = ds.normalize_round(ds.make_gaussian(150, 32, 3)); qs = ds.normalize_round(ds.make_gaussian(3, 32, 4))
+ixs = DenseIndex(32); ixs.add(cs, normalize=False)
+sc, ids = ixs.search(qs, 200, normalize=False)
+rv, ri = ds.brute_force_topk(qs, cs, 150)
+assert np.allclose(sc[:, :150], rv, rtol=0, atol=1e-5) and ds.gap_aware_id_match(ids[:, :150], sc[:, :150], ri, rv, tol=1e-5)[1] == 0
+assert np.isneginf(sc[:, 150:]).all() and (ids[:, 150:] == -1).all()
+# real ties on the k-th score (integer-valued rows, inner product: exact sums; 24 regions): the select stops inside a
+# bucket of equal scores and the row-ascending order survives -> the oracle's ids and scores exactly
+rng = np.random.default_rng(9)
+ci = rng.integers(-2, 3, size=(6000, 64)).astype(np.float16); qi = rng.integers(-2, 3, size=(5, 64)).astype(np.float16)
+ixi = DenseIndex(64, metric="ip"); ixi.add(ci, normalize=False)
+sc, ids = ixi.search(qi, 130, normalize=False)
+rv, ri = ds.brute_force_topk(qi, ci, 130)
+assert (ids == ri).all() and (sc == rv).all()
 print("ok")
 ''' % str(root)
     for cap in ("0", "64", None):

@@ -72,7 +72,7 @@ def test_many_query_tiles_xcd_map(nq, n):
 @pytest.mark.parametrize("k", [10, 64, 100])
 def test_batch_launch_loop_is_exact(k):
     """16 641 queries = 64 query tiles + one tile + one query: the batch regimes cut them into launches of at most
-    MAX_QTILES_PER_LAUNCH tiles (csrc/bf_index.hip; fewer per launch in the wide-batch loop at k = 100).  Every query
+    MAX_QTILES_PER_LAUNCH tiles (csrc/bf_index.hip launch_batch; fewer per launch in the wide-batch loop at k = 100).  Every query
     against the oracle, and the first and last 300 result rows bit for bit against a search of those queries alone: a
     wrong query or output offset of a later launch shows there."""
     nq, n, d = 64 * 256 + 256 + 1, 777, 64
