@@ -144,7 +144,8 @@ ATTENTION_S = (16, 64, 65, 128, 129, 256, 257, 300, 511, 512)
 
 
 def attention_instance(dh: int, S: int) -> str:
-    """Kernel that ``forward_impl`` launches for this head dim and sequence length (read off its dispatch in csrc/encoder.hip)."""
+    """Kernel that ``launch_attention`` launches for this head dim and sequence length (read off its dispatch in
+    csrc/enc_attention.hip)."""
     if S > 256:
         return f"enc_attention_kernel<DT, {dh}, 8>"
     sp = 64 if S <= 64 else 128 if S <= 128 else 256

@@ -66,7 +66,7 @@ def test_case_discriminates(case):
 
 
 def test_attention_cases_cover_every_dispatch_cell():
-    """Every (head dim, key padding or general kernel) pair of ``forward_impl`` has a case on each side of its boundaries,
+    """Every (head dim, key padding or general kernel) pair of ``launch_attention`` has a case on each side of its boundaries,
     and each runs in both dtypes."""
     cells = {(c.geometry, c.note) for c in ec.ATTENTION_CASES}
     assert len(cells) == 8 and all(c.dtypes == ("f16", "bf16") for c in ec.ATTENTION_CASES)

@@ -84,7 +84,7 @@ def test_bge_base_shape_matches_oracle_cls():
                                             ("bge-base", 1, 24, "cls"), ("bge-base", 4, 16, "cls")])
 def test_single_question_batches_match_oracle(arch, B, S, pool):
     """<= 64 tokens per call -- the reference embeds one question at a time (retrieval_backend.py:227): the skinny,
-    K-split GEMM path (csrc/encoder.hip enc_gemm_skinny_kernel), real layer widths."""
+    K-split GEMM path (csrc/enc_gemm.hip enc_gemm_skinny_kernel), real layer widths."""
     from mrag_amd.encoder import HipSentenceEncoder, EncoderSpec
     spec = dict(oe.SPECS[arch], vocab_size=3000, max_position=64, layers=3)
     w = oe.seeded_weights(spec, 12)
@@ -102,7 +102,7 @@ def test_single_question_batches_match_oracle(arch, B, S, pool):
 
 @pytest.mark.parametrize("arch,B,S,pool,layers", [("minilm-l6", 512, 32, "mean", 6), ("bge-base", 128, 96, "cls", 3)])
 def test_fused_layernorm_flow_matches_oracle(arch, B, S, pool, layers):
-    """Batches large enough for the 256 x 256 GEMMs take the fused-LayerNorm flow (csrc/encoder.hip LnArgs: gamma folded into the
+    """Batches large enough for the 256 x 256 GEMMs take the fused-LayerNorm flow (csrc/enc_kernels.h LnArgs: gamma folded into the
     consuming weights, per-token statistics from the producing GEMM's epilogue, residuals normalised on the fly): against the
     oracle on a subsample of the rows, padded / ragged masks included."""
     from mrag_amd.encoder import HipSentenceEncoder, EncoderSpec

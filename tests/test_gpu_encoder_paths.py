@@ -1,12 +1,13 @@
-"""GPU parity of the HIP sentence encoder over its whole dispatch (csrc/encoder.hip ``forward_impl``): every attention instance
-in both dtypes, the mask families, the three GEMM kernels and both LayerNorm flows, against the fp64 oracle.
+"""GPU parity of the HIP sentence encoder over its whole dispatch (csrc/encoder.hip ``forward`` and the launchers of
+csrc/enc_*.hip): every attention instance in both dtypes, the mask families, the three GEMM kernels and both LayerNorm
+flows, against the fp64 oracle.
 
 Inputs, tolerances and the reasons for both come from ``oracle/encoder_cases.py``: query / key weights scaled until attention
 is neither uniform nor saturated, and a tolerance of 4 x the rounding noise of a 16-bit pipeline, computed from the oracle
 for each case and dtype.  ``tests/test_encoder_sensitivity.py`` shows on the CPU that at these tolerances a dropped key, an
 attended padding key, a wrong pooling divisor, shifted positions or swapped heads fail a case with a factor 2 to spare.
 
-Case -> attention kernel (``Case.note``), read off the dispatch in ``forward_impl``:
+Case -> attention kernel (``Case.note``), read off the dispatch in ``launch_attention`` (csrc/enc_attention.hip):
   S <= 64          enc_attention_s128_kernel<DT, dh, 64, 4>         S = 16, 64
   65 .. 128        enc_attention_s128_kernel<DT, dh, 128, 4>        S = 65, 128
   129 .. 256       enc_attention_s128_kernel<DT, dh, 256, 8>        S = 129, 256
@@ -184,3 +185,136 @@ def test_ids_outside_the_vocabulary_are_rejected():
     edge = ids.copy()
     edge[0, 0], edge[0, 1] = 0, vocab - 1
     assert np.isfinite(enc.forward(edge, mask)).all()
+
+
+# ---------------------------------------------------------------------------------------------- the C entry points directly
+def _create(spec, dtype="f16"):
+    """``mrag_encoder_create`` -> (library, handle): no parameter set yet."""
+    import ctypes as C
+    from mrag_amd import _native as N
+    lib = N.load()
+    cfg = N.EncoderConfig(spec["vocab_size"], spec["hidden"], spec["layers"], spec["heads"], spec["intermediate"],
+                          spec["max_position"], spec["type_vocab_size"], spec["layer_norm_eps"],
+                          N.MRAG_F16 if dtype == "f16" else N.MRAG_BF16)
+    h = C.c_uint64(0)
+    N.check(lib.mrag_encoder_create(C.byref(cfg), 0, C.byref(h)))
+    return lib, h
+
+
+def _set_param(lib, h, name, arr, numel=None):
+    """``mrag_encoder_set_param`` from a host array -> status (0 = accepted)."""
+    a = np.ascontiguousarray(arr, dtype=np.float32)
+    return lib.mrag_encoder_set_param(h, name.encode(), a.ctypes.data, a.size if numel is None else numel, 0, None)
+
+
+def _missing(lib, h):
+    import ctypes as C
+    from mrag_amd import _native as N
+    miss = C.c_int(-1)
+    N.check(lib.mrag_encoder_missing_params(h, C.byref(miss)))
+    return miss.value
+
+
+def _forward(lib, h, ids, mask, hidden, pool, normalize):
+    """``mrag_encoder_forward`` on host buffers -> (status, output)."""
+    from mrag_amd import _native as N
+    ids, mask = np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(mask, dtype=np.int32)
+    out = np.zeros((len(ids), hidden), dtype=np.float32)
+    st = lib.mrag_encoder_forward(h, ids.ctypes.data, mask.ctypes.data, ids.shape[0], ids.shape[1], out.ctypes.data,
+                                  N.POOL_CLS if pool == "cls" else N.POOL_MEAN, int(normalize), 0, None)
+    return st, out
+
+
+def test_parameter_table():
+    """``mrag_encoder_set_param`` / ``mrag_encoder_missing_params`` on the ``tiny`` architecture (geometry dh32): the count of
+    missing parameters starts at 5 + 16 x layers and drops by one per distinct accepted name; a wrong element count (a matrix, a
+    bias, one of the q / k / v blocks), an unknown suffix, a layer past the last and a layer prefix without its second dot are
+    rejected and set nothing; a forward with one parameter missing is refused.  With all of them set the case meets the oracle;
+    with the key and value weights of layer 0 swapped at upload it misses it by more than the case's tolerance (the swap moves
+    the fp64 oracle by 15 x tol or more in every quantity): the order of the three row blocks of the fused QKV Linear."""
+    case = ec.CASE_BY_NAME["dh32-S16"]
+    spec, w = case.spec, case.weights()
+    H, I, layers = spec["hidden"], spec["intermediate"], spec["layers"]
+    ids, mask = case.batch()
+    lib, h = _create(spec, "f16")
+    try:
+        left = 5 + 16 * layers
+        assert len(w) == left and _missing(lib, h) == left
+        wrong = (("encoder.layer.0.intermediate.dense.weight", I * H - 1), ("encoder.layer.1.output.dense.bias", H + 1),
+                 ("encoder.layer.1.attention.self.key.weight", H * H + H), ("encoder.layer.0.attention.self.value.bias", H - 1))
+        for name, numel in wrong:                                     # wrong size: an error, and the name stays missing
+            assert _set_param(lib, h, name, np.zeros(numel), numel) != 0, name
+            assert _missing(lib, h) == left, name
+        some = w["encoder.layer.0.output.dense.bias"]
+        for name in ("encoder.layer.0.output.dense.gain", "encoder.layer.0.output.dense.bias.", "output.dense.bias",
+                     f"encoder.layer.{layers}.output.dense.bias", "encoder.layer.-1.output.dense.bias",
+                     "encoder.layer.", "encoder.layer.0", "encoder.layer.0output.dense.bias", "embeddings.LayerNorm", ""):
+            assert _set_param(lib, h, name, some) != 0, name
+            assert _missing(lib, h) == left, name
+        names = list(w)
+        last = "encoder.layer.1.attention.self.value.weight"
+        names.remove(last)
+        for name in names:
+            assert _set_param(lib, h, name, w[name]) == 0, name
+            left -= 1
+            assert _missing(lib, h) == left, name
+            if name.endswith("query.bias") or name.endswith("LayerNorm.weight"):
+                assert _set_param(lib, h, name, w[name]) == 0, name     # the same name again: accepted, counted once
+                assert _missing(lib, h) == left, name
+        assert left == 1
+        st, _ = _forward(lib, h, ids, mask, H, "mean", True)
+        assert st != 0                                                  # one parameter missing: refused
+        assert _set_param(lib, h, last, w[last]) == 0 and _missing(lib, h) == 0
+        ex = ec.case_expected(case.name, "f16")
+        print(f"\nparameter table, {case.name} f16")
+        for q in ec.QUANTITIES:
+            st, got = _forward(lib, h, ids, mask, H, *q)
+            assert st == 0
+            _check(got, ex.want[q], ex.tol[q], f"{q[0]}{'' if q[1] else '-raw'}")
+        k, v = "encoder.layer.0.attention.self.key.weight", "encoder.layer.0.attention.self.value.weight"
+        assert _set_param(lib, h, k, w[v]) == 0 and _set_param(lib, h, v, w[k]) == 0 and _missing(lib, h) == 0
+        for q in ec.QUANTITIES:
+            st, got = _forward(lib, h, ids, mask, H, *q)
+            assert st == 0 and np.isfinite(got).all()
+            err = float(np.abs(got - ex.want[q]).max())
+            print(f"  key / value swapped, {q[0]}{'' if q[1] else '-raw'}: max |gpu - oracle| {err:.2e} = {err / ex.tol[q]:.1f} tol")
+            assert err > ex.tol[q], (q, err, ex.tol[q])
+    finally:
+        lib.mrag_encoder_destroy(h)
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_refold_after_parameter_change(dtype, monkeypatch):
+    """The folded copies of the fused-LayerNorm flow follow a parameter change.  MiniLM widths, 2 layers, 512 x 32 tokens
+    (M_pad = 16384: the smallest batch whose fused flow engages on 256 CUs).  Handle A runs a forward (which folds), then gets
+    another ``encoder.layer.0.output.LayerNorm.bias`` -- a parameter the fused flow reads only through the folded QKV bias and
+    the beta-augmented attention-output bias of layer 1 -- and runs again; handle B is created with the changed weights.  A's
+    second output equals B's bit for bit (the same kernels on the same inputs, partial sums added in slot order) and differs
+    from A's first."""
+    from mrag_amd.encoder import HipSentenceEncoder, EncoderSpec
+    case = ec.CASE_BY_NAME["large-minilm-512x32"]
+    monkeypatch.delenv("MRAG_ENC_NO_FUSED_LN", raising=False)
+    ids, mask = case.batch()
+    w = dict(case.weights())
+    name = "encoder.layer.0.output.LayerNorm.bias"
+    a = HipSentenceEncoder(EncoderSpec(**case.spec), w, dtype=dtype)
+    b = None
+    try:
+        first = a.forward(ids, mask, pool="mean")
+        w[name] = (w[name] + np.linspace(-0.5, 0.5, w[name].size)).astype(np.float32)
+        assert _set_param(a._lib, a._h, name, w[name]) == 0
+        second = a.forward(ids, mask, pool="mean")
+        b = HipSentenceEncoder(EncoderSpec(**case.spec), w, dtype=dtype)
+        fresh = b.forward(ids, mask, pool="mean")
+        again = b.forward(ids, mask, pool="mean")
+    finally:
+        a.close()
+        if b is not None:
+            b.close()
+    assert np.isfinite(second).all() and np.isfinite(fresh).all()
+    print(f"\nre-fold {dtype}: max |second - first| {float(np.abs(second - first).max()):.2e}, "
+          f"max |second - fresh handle| {float(np.abs(second - fresh).max()):.2e}, "
+          f"fresh handle twice {float(np.abs(again - fresh).max()):.2e}")
+    assert np.array_equal(fresh.view(np.uint32), again.view(np.uint32))        # (a handle reproduces itself)
+    assert np.array_equal(second.view(np.uint32), fresh.view(np.uint32))
+    assert not np.array_equal(second, first)
