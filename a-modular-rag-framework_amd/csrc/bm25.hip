@@ -13,6 +13,9 @@
 //   keep s > 0, sort desc, [:top_k] (:92-96)    MSB-first radix select over (score bits, ~doc) + rank by counting:
 //                                               (score desc, doc asc) -- the reference's tie order is the iteration
 //                                               order of a set of ints; doc-ascending is this library's declared order
+// The selection kernels (bm25_hist_kernel, bm25_gather_kernel) launch at most 1024 workgroups of 256 threads: one sweep
+// covers 1024 * 256 = 262 144 documents and a larger corpus is covered by their grid-stride loops, so a corpus above
+// 262 144 documents is the first at which those loops take a second iteration (tests/test_gpu_text_channel.py, "stride").
 // HBM-bound integer/byte work: bytes = 8 per posting read + 16 per score read-modify-write, + 8 N per selection pass.
 #include "common.h"
 

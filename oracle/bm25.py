@@ -13,7 +13,9 @@ from __future__ import annotations
 
 import math
 import re
-from typing import Any, Dict, List, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 
 def tokenize(text: str) -> List[str]:
@@ -82,3 +84,90 @@ class Bm25Oracle:
                         "meta": {"kind": "sentence", "text": meta.get("text"), "doc": meta.get("title"),
                                  "sent_id": meta.get("sent_id"), "source": "bm25"}})
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The same search from CSR postings, vectorised: what makes corpora of several hundred thousand rows testable.
+# ---------------------------------------------------------------------------------------------------------
+SELECT_GRID = 1024 * 256        # documents one sweep of the device's 1024 x 256 selection grid covers
+
+POSTINGS_MUTANTS = ("ties_doc_desc", "first_stride_only", "score_top5_bytes", "drop_repeats", "tokens_reversed",
+                    "sum_is_max", "skip_255", "cut_before_filter")
+
+
+def query_term_ids(postings: Dict[str, Any], queries: Sequence[str]) -> List[Tuple[List[int], List[float]]]:
+    """Every query as (term ids, idfs), token by token in order, repeats included; an unknown term has id -1.
+    ``postings`` is what ``build_postings`` returns; the idf is text_index.py:54-56 with its own expression."""
+    n_docs, out = postings["N"], []
+    for q in queries:
+        ids, idfs = [], []
+        for t in tokenize(q):
+            n = postings["df"].get(t, 0)
+            ids.append(postings["term_id"].get(t, -1))
+            idfs.append(math.log((n_docs - n + 0.5) / (n + 0.5) + 1.0) if n_docs > 0 else 0.0)
+        out.append((ids, idfs))
+    return out
+
+
+def merged_scores(postings: Dict[str, Any], queries, merge: str = "max", k1: float = 1.5,
+                  mutant: Optional[str] = None) -> np.ndarray:
+    """fp64 score of every document after the merge over the queries, before ``s > 0`` is asked.  Elementwise IEEE
+    operations in the order of ``Bm25Oracle.score_doc`` and ``search``: a document receives its tokens' terms left to
+    right, then the queries' scores are merged left to right."""
+    indptr, post_doc, post_tf = postings["indptr"], postings["post_doc"], postings["post_tf"]
+    doc_norm = np.asarray(postings["doc_norm"], dtype=np.float64)
+    if queries and isinstance(queries[0], str):
+        queries = query_term_ids(postings, queries)
+    if mutant == "sum_is_max" and merge == "sum":
+        merge = "max"
+    fin = None
+    for ids, idfs in queries:
+        toks = list(zip(ids, idfs))
+        if mutant == "drop_repeats":
+            toks = list(dict(toks).items())                         # every term once, at its first position
+        if mutant == "tokens_reversed":
+            toks = toks[::-1]
+        row = np.zeros(len(doc_norm), dtype=np.float64)
+        for t, idf in toks:
+            if t < 0:
+                continue
+            lo, hi = int(indptr[t]), int(indptr[t + 1])
+            docs, tf = post_doc[lo:hi], post_tf[lo:hi].astype(np.float64)
+            if mutant == "skip_255":
+                keep = np.arange(hi - lo) % 256 != 255
+                docs, tf = docs[keep], tf[keep]
+            row[docs] = row[docs] + (float(idf) * (tf * (k1 + 1))) / (tf + doc_norm[docs])
+        fin = row if fin is None else (fin + row if merge == "sum" else np.maximum(fin, row))
+    return fin if fin is not None else np.zeros(len(doc_norm), dtype=np.float64)
+
+
+def select_topk(fin: np.ndarray, k: int, mutant: Optional[str] = None) -> List[Tuple[int, float]]:
+    """Keep ``s > 0``, order by (score descending, document ascending), cut at ``k``."""
+    docs = np.arange(len(fin), dtype=np.int64)
+    if mutant == "cut_before_filter":
+        # the cut is made over the raw keys of every touched document (a negative double's bit pattern is above
+        # every positive one's), s <= 0 is dropped afterwards
+        bits = fin.view(np.uint64)
+        cand = docs[bits != 0]
+        cand = cand[np.lexsort((cand, ~bits[cand]))][:k]                              # negative scores first
+        cand = cand[fin[cand] > 0]
+        return [(int(d), float(fin[d])) for d in cand[np.lexsort((cand, -fin[cand]))]]
+    cand = docs[fin > 0]
+    if mutant == "first_stride_only":
+        cand = cand[cand < SELECT_GRID]
+    key = fin[cand]
+    if mutant == "score_top5_bytes":
+        key = (key.view(np.uint64) >> np.uint64(24)).astype(np.float64)                # 40 bits: exact in fp64
+    tie = -cand if mutant == "ties_doc_desc" else cand
+    order = np.lexsort((tie, -key))[:k]
+    return [(int(d), float(s)) for d, s in zip(cand[order], fin[cand[order]])]
+
+
+def search_postings(postings: Dict[str, Any], queries, k: int, merge: str = "max", k1: float = 1.5,
+                    mutant: Optional[str] = None) -> List[Tuple[int, float]]:
+    """``Bm25Oracle.search`` from the CSR arrays of ``build_postings`` (``indptr``, ``post_doc``, ``post_tf``,
+    ``doc_norm``), bit for bit.  ``queries``: strings (``postings`` then carries ``term_id`` / ``df`` / ``N``), or
+    one ``(term ids, idfs)`` pair per query for hand-made postings.  ``mutant`` makes one deliberate error
+    (``POSTINGS_MUTANTS``); only the sensitivity test passes it."""
+    assert mutant is None or mutant in POSTINGS_MUTANTS, mutant
+    return select_topk(merged_scores(postings, queries, merge, k1, mutant), k, mutant)
