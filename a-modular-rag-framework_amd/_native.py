@@ -1,4 +1,4 @@
-"""ctypes binding of libmrag_hip.so (include/mrag.h).  There is no CPU fallback: a missing
+"""ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -114,6 +114,12 @@ SIGNATURES = {
     "mrag_encoder_last_timing": [_h, _fp],
 }
 
+# the additions to the ABI that have a header of their own (include/mrag_bm25_batch.h), bound like the rest
+EXTENSION_SIGNATURES = {
+    "mrag_bm25_search_batch": [_h, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "mrag_bm25_set_scratch_limit": [_h, _i64],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -133,7 +139,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(str(p))
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

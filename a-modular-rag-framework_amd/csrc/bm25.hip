@@ -17,32 +17,12 @@
 // covers 1024 * 256 = 262 144 documents and a larger corpus is covered by their grid-stride loops, so a corpus above
 // 262 144 documents is the first at which those loops take a second iteration (tests/test_gpu_text_channel.py, "stride").
 // HBM-bound integer/byte work: bytes = 8 per posting read + 16 per score read-modify-write, + 8 N per selection pass.
-#include "common.h"
+#include "bm25_kernels.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace mrag {
-
-struct Bm25Index : Object {
-  int64_t n_docs = 0, n_terms = 0, nnz = 0;
-  double k1p1 = 2.5;
-  int64_t* indptr = nullptr;     // [n_terms + 1]
-  int32_t* post_doc = nullptr;   // [nnz]
-  int32_t* post_tf = nullptr;    // [nnz]
-  double* doc_norm = nullptr;    // [n_docs]  k1 * (1 - b + b * dl / avgdl)
-  std::vector<int64_t> h_indptr; // host copy: posting counts size the launches
-  DevBuf scores, fin, hist, sel, qbuf;
-  ~Bm25Index() override {
-    for (void* p : {(void*)indptr, (void*)post_doc, (void*)post_tf, (void*)doc_norm}) if (p) (void)hipFree(p);
-    for (DevBuf* b : {&scores, &fin, &hist, &sel, &qbuf}) b->release();
-  }
-};
-
-constexpr int BM25_MAX_K = 4096;
-constexpr int BM25_PASSES = 12;   // 8 bytes of score bits + 4 bytes of ~doc
-
-struct Bm25Job { int64_t lo, hi; double idf; int32_t query; int32_t pad; };   // one (query, token position) posting range
 
 // one token position of every query: jobs[y] = that query's posting range; x covers the longest range
 __global__ __launch_bounds__(256) void bm25_scatter_kernel(const Bm25Job* __restrict__ jobs, const int32_t* __restrict__ post_doc,
@@ -72,41 +52,6 @@ __global__ __launch_bounds__(256) void bm25_merge_kernel(const double* __restric
     s = merge_sum ? s + v : (v > s ? v : s);
   }
   fin[d] = s > 0.0 ? s : 0.0;
-}
-
-// digit p (0 = most significant) of the 96-bit key (score bits : ~doc); positive doubles order like their bit patterns
-__device__ __forceinline__ uint32_t bm25_digit(uint64_t sb, uint32_t nd, int p) {
-  return p < 8 ? (uint32_t)(sb >> (56 - 8 * p)) & 255u : (nd >> (24 - 8 * (p - 8))) & 255u;
-}
-
-// Selection state, derived by every workgroup from the histograms of the passes already run:
-// prefix bytes pre[0..np), keys needed inside the prefix bucket, done = bucket wholly selected.
-struct Bm25Pick { uint32_t pre[BM25_PASSES]; int np; int64_t need; bool done; };
-
-__device__ inline void bm25_replay(const unsigned* __restrict__ hist, int passes, int64_t k, Bm25Pick& st) {
-  st.np = 0; st.need = k; st.done = false;
-  for (int p = 0; p < passes && !st.done; ++p) {
-    const unsigned* h = hist + p * 256;
-    int64_t cum = 0;
-    int b = 255;
-    for (; b >= 0; --b) {
-      if (cum + h[b] >= st.need) break;
-      cum += h[b];
-    }
-    if (b < 0) { st.done = true; st.need = 0; break; }   // fewer than `need` keys exist: everything is selected
-    st.pre[st.np++] = (uint32_t)b;
-    st.need -= cum;
-    if ((int64_t)h[b] == st.need) st.done = true;
-  }
-}
-
-__device__ __forceinline__ int bm25_cmp_prefix(uint64_t sb, uint32_t nd, const Bm25Pick& st) {
-  // -1 below, 0 inside, +1 above the prefix bucket
-  for (int p = 0; p < st.np; ++p) {
-    const uint32_t dg = bm25_digit(sb, nd, p);
-    if (dg != st.pre[p]) return dg > st.pre[p] ? 1 : -1;
-  }
-  return 0;
 }
 
 // pass `pass`: histogram of digit `pass` over the keys inside the current prefix bucket

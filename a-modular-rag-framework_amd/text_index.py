@@ -8,6 +8,9 @@
 The index is built on the host like the reference builds it (same tokeniser, same counts) and uploaded once
 as CSR postings; every search then runs on the device (``mrag_bm25_search``): scores are the reference's
 fp64 sums bit for bit, order is (score desc, doc asc).  There is no CPU search path.
+
+``search_batch`` answers many questions in one call (``mrag_bm25_search_batch``), each exactly as ``search`` answers
+it alone, and both take ``allow=``: the row filter of ``DenseIndex.search(allow=...)`` over the same docs.jsonl rows.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
+from .index import allow_bits
 
 _SPLIT = re.compile(r"[^a-zA-Z0-9]+")
 
@@ -115,8 +119,11 @@ class HipBM25Index:
         n = self.df.get(term, 0)
         return math.log((self.N - n + 0.5) / (n + 0.5) + 1.0) if self.N > 0 else 0.0
 
-    def search(self, queries: List[str], top_k: int = 20, alpha_merge: str = "max") -> List[Tuple[int, float]]:
-        """text_index.py:71-97 on the device.  ``[(doc_idx, score)]``, best first."""
+    def search(self, queries: List[str], top_k: int = 20, alpha_merge: str = "max", allow=None) -> List[Tuple[int, float]]:
+        """text_index.py:71-97 on the device.  ``[(doc_idx, score)]``, best first.  ``allow`` (see :meth:`search_batch`)
+        restricts the candidates to some documents; with a set the search runs as a batch of one question."""
+        if allow is not None:
+            return self.search_batch([queries], top_k=top_k, alpha_merge=alpha_merge, allow=allow)[0]
         if not self.N or not queries or top_k <= 0:
             return []
         q_ptr, q_terms, q_idf = [0], [], []
@@ -137,6 +144,64 @@ class HipBM25Index:
                                            C.byref(n), None))
         return [(int(d), float(s)) for d, s in zip(docs[:n.value], scores[:n.value])]
 
+    def _allow_words(self, allow) -> np.ndarray:
+        """``allow`` -> the ABI's packed words (uint32 [ceil(N/32)], bit d%32 of word d/32).  A bool / uint8 mask over
+        the documents or integer document positions go through ``index.allow_bits``, like ``DenseIndex.search(allow=)``
+        on the host; an array of dtype uint32 is taken as the packed words themselves (what ``allow_bits`` returns), so
+        positions must come in another integer dtype.  Bits past the last document are ignored."""
+        words = (self.N + 31) // 32
+        a = allow if isinstance(allow, np.ndarray) else None
+        if a is not None and a.dtype == np.uint32:
+            if a.ndim != 1 or a.shape[0] != words:
+                raise ValueError(f"packed allow bits must be uint32 [{words}] for {self.N} documents, got shape {a.shape}")
+            return np.ascontiguousarray(a)
+        return np.ascontiguousarray(allow_bits(allow, self.N))
+
+    def search_batch(self, questions: Sequence[Sequence[str]], top_k: int = 20, alpha_merge: str = "max",
+                     allow=None) -> List[List[Tuple[int, float]]]:
+        """:meth:`search` for many questions in one call (``mrag_bm25_search_batch``).  ``questions[g]`` is the list of
+        expanded query strings of question g; the result holds one ``[(doc_idx, score)]`` list per question, each equal
+        to ``search(questions[g], top_k, alpha_merge)``: same documents, same score bits, same order.
+
+        ``allow`` restricts every question's candidates to a set of documents: a bool / uint8 mask over the documents,
+        integer document positions, or packed uint32 bits (:meth:`_allow_words`).  It changes no score -- idf and avgdl
+        stay the corpus's -- and ``None`` or an all-allowed set is the plain search."""
+        questions = [list(qs) for qs in questions]
+        if not self.N or not questions or top_k <= 0:
+            return [[] for _ in questions]
+        bits = self._allow_words(allow) if allow is not None else None
+        g_ptr, q_ptr, q_terms, q_idf = [0], [0], [], []
+        known: Dict[str, Tuple[int, float]] = {}
+        for qs in questions:
+            for q in qs:
+                for t in tokenize(q):
+                    e = known.get(t)
+                    if e is None:
+                        e = known[t] = (self._term_id.get(t, -1), self._idf(t))
+                    q_terms.append(e[0])
+                    q_idf.append(e[1])
+                q_ptr.append(len(q_terms))
+            g_ptr.append(len(q_ptr) - 1)
+        k, nq = int(min(top_k, self.N)), len(questions)
+        gp = np.asarray(g_ptr, dtype=np.int32)
+        qp = np.asarray(q_ptr, dtype=np.int32)
+        qt = np.asarray(q_terms if q_terms else [0], dtype=np.int32)
+        qi = np.asarray(q_idf if q_idf else [0.0], dtype=np.float64)
+        docs = np.empty((nq, k), dtype=np.int64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        n = np.zeros(nq, dtype=np.int32)
+        N.check(self._lib.mrag_bm25_search_batch(self._h, nq, gp.ctypes.data, qp.ctypes.data, qt.ctypes.data, qi.ctypes.data,
+                                                 1 if alpha_merge == "sum" else 0, k, bits.ctypes.data if bits is not None else None,
+                                                 docs.ctypes.data, scores.ctypes.data, n.ctypes.data, None))
+        dl, sl = docs.tolist(), scores.tolist()
+        return [list(zip(dl[g][:c], sl[g][:c])) for g, c in enumerate(n.tolist())]
+
+    def set_scratch_limit(self, nbytes: int) -> None:
+        """Bytes of fp64 score rows (8 * N per expanded query) one chunk of :meth:`search_batch` may use
+        (``mrag_bm25_set_scratch_limit``); ``<= 0`` restores the default.  Results do not depend on it."""
+        if self._h is not None:
+            N.check(self._lib.mrag_bm25_set_scratch_limit(self._h, int(nbytes)))
+
     def doc_meta(self, doc_idx: int) -> Dict[str, Any]:
         return dict(self.docs[doc_idx]) if 0 <= doc_idx < len(self.docs) else {}
 
@@ -148,16 +213,26 @@ class HipBM25TextSearcher:
     def __init__(self, index: HipBM25Index):
         self.index = index
 
-    def search(self, *, queries: List[str], top_k: int) -> List[Dict[str, Any]]:
-        if self.index.N <= 0:
-            return []
+    def _hits(self, ranked: List[Tuple[int, float]]) -> List[Dict[str, Any]]:
         out = []
-        for doc_idx, s in self.index.search(queries, top_k=top_k, alpha_merge="max"):
+        for doc_idx, s in ranked:
             meta = self.index.doc_meta(doc_idx)
             out.append({"id": "sent::%s::%s" % (meta.get("doc_id") or meta.get("title") or "doc", str(meta.get("sent_id") or "")),
                         "score": float(s),
                         "meta": {"kind": "sentence", "text": meta.get("text"), "doc": meta.get("title"),
                                  "sent_id": meta.get("sent_id"), "source": "bm25"}})
         return out
+
+    def search(self, *, queries: List[str], top_k: int) -> List[Dict[str, Any]]:
+        if self.index.N <= 0:
+            return []
+        return self._hits(self.index.search(queries, top_k=top_k, alpha_merge="max"))
+
+    def search_batch(self, *, queries: Sequence[Sequence[str]], top_k: int, allow=None) -> List[List[Dict[str, Any]]]:
+        """:meth:`search` for one list of expanded queries per question (``HipBM25Index.search_batch``); per question
+        the hit list :meth:`search` returns.  ``allow``: the document filter of ``HipBM25Index.search_batch``."""
+        if self.index.N <= 0:
+            return [[] for _ in queries]
+        return [self._hits(r) for r in self.index.search_batch(queries, top_k=top_k, alpha_merge="max", allow=allow)]
 
     __call__ = search

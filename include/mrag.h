@@ -375,6 +375,7 @@ int mrag_bm25_create(int device, int64_t n_docs, int64_t n_terms, const int64_t*
 int mrag_bm25_destroy(mrag_handle h);
 int mrag_bm25_search(mrag_handle h, int n_queries, const int32_t* q_ptr, const int32_t* q_terms, const double* q_idf,
                      int merge_sum, int k, int64_t* out_docs, double* out_scores, int* out_n, void* stream);
+/* The same search for a batch of questions, optionally over an allow-set of documents: mrag_bm25_batch.h, included below. */
 
 /* a7 on the device: the fusion arithmetic of HybridRetrievalBackend.run (retrieval_backend.py:336-372).
  * keys / scores hold the text, graph and dense channel entries back to back (n_text, n_graph, n_dense); a key is
@@ -391,4 +392,8 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 #ifdef __cplusplus
 }
 #endif
+
+/* Additions to the ABI since its 64 entry points: each in a header of its own, part of this one. */
+#include "mrag_bm25_batch.h"
+
 #endif /* MRAG_H_ */
