@@ -1,4 +1,4 @@
-"""ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h).  There is no CPU fallback: a missing
+"""ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -120,6 +120,12 @@ EXTENSION_SIGNATURES = {
     "mrag_bm25_set_scratch_limit": [_h, _i64],
 }
 
+# include/mrag_fuse_batch.h
+FUSE_BATCH_SIGNATURES = {
+    "mrag_fuse_topk_batch": [_i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -139,7 +145,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(str(p))
-    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

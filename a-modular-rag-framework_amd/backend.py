@@ -178,6 +178,7 @@ class DenseRetrievalBackend:
         if dense_row_filter is not None and not callable(dense_row_filter):
             raise TypeError(f"dense_row_filter must be callable or a 'pkg.mod:func' string, got {type(dense_row_filter)}")
         self.dense_row_filter = dense_row_filter
+        self._own_text_search = None                     # the searcher _bm25_searcher() made over index_path, if any
         if text_channel not in (None, "bm25"):
             raise ValueError(f"unknown text_channel {text_channel!r} (supported: 'bm25')")
         self._state = None
@@ -306,7 +307,8 @@ class DenseRetrievalBackend:
             sig = f"{self.index_path}|missing"
         key = f"bm25-index|{sig}|{self.device}|{self.bm25_k1}|{self.bm25_b}"
         ix = _corpus.shared(key, lambda: HipBM25Index(self.index_path, k1=self.bm25_k1, b=self.bm25_b, device=self.device))
-        return HipBM25TextSearcher(ix)
+        self._own_text_search = HipBM25TextSearcher(ix)    # run_batch reads its document positions as corpus rows
+        return self._own_text_search
 
     _FAIL_BACKOFF_S = 30.0
     _failed: Dict[str, Any] = {}        # key -> (monotonic deadline, error text): no re-embed storm after a failed build
@@ -420,3 +422,190 @@ class DenseRetrievalBackend:
         result = self.run(req)
         hits = [Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]]
         return RetrievalOut(hits=hits, diagnostics=result.get("diagnostics", {}))
+
+    # -- the same protocol for a list of requests: one dense search, one BM25 batch search, one fusion launch ------------
+    def _norm_keys(self, state):
+        """``fusion.corpus_norm_keys`` of the state's rows, built once per state and kept in it."""
+        if "norm_keys" not in state:
+            state["norm_keys"] = _fusion.corpus_norm_keys(state["rows"])
+        return state["norm_keys"]
+
+    def run_batch(self, reqs) -> List[Dict[str, Any]]:
+        """:meth:`run` for every request of ``reqs``, in order, with the device work of the whole list in three calls:
+        one ``DenseIndex.search`` over all query embeddings, one ``HipBM25Index.search_batch`` (``text_channel="bm25"``)
+        and one ``mrag_fuse_topk_batch``.  ``top_k``, ``trace_id`` and the pool are each request's own: the searches run
+        at the list's largest pool and every question uses the leading part of its lists that its own pool covers (both
+        searches are exact with a declared order, so a prefix is the smaller search's answer).  Requests for which
+        ``dense_row_filter`` returns a set are searched one by one with their ``allow``; an injected ``text_search`` and
+        ``graph_expand`` are called once per request.  Like :meth:`run` it degrades and never raises out of the dense
+        channel.  Diagnostics are :meth:`run`'s plus ``batch_size``."""
+        from .text_index import HipBM25TextSearcher
+        reqs = list(reqs)
+        B = len(reqs)
+        if not B:
+            return []
+        model_hint = resolve_embed_model(self.router)
+        trace = [getattr(r, "trace_id", None) or "trace-demo" for r in reqs]
+        top_k = [int(getattr(r, "top_k", None) or self.default_top_k) for r in reqs]
+        pool = [max(k, self.dense_pool_k) for k in top_k]
+        pool_max = max(pool)
+
+        # ---- text and graph channels
+        text_error = None
+        if self.text_search is None and self.text_channel == "bm25":
+            try:
+                self.text_search = self._bm25_searcher()
+            except Exception as e:
+                text_error = repr(e)
+                logger.error("[DenseRetrievalBackend] BM25 channel unavailable: %s", e)
+        bm25 = self.text_channel == "bm25" and isinstance(self.text_search, HipBM25TextSearcher)
+        # only the searcher made here over index_path numbers its documents as the dense state numbers its rows (both read
+        # the file's non-empty lines in order); an injected one, even of the same length, is fused by id strings
+        own = bm25 and self.text_search is self._own_text_search
+        t_arrays = None                                  # bm25: (docs [B][k], scores [B][k], n [B]) of the batch search
+        t_hits: List[List[Dict[str, Any]]] = [[] for _ in reqs]
+        g_hits: List[List[Dict[str, Any]]] = [[] for _ in reqs]
+        if bm25:
+            with span("Backend/TextSearch", self.sink, trace[0]):
+                if self.text_search.index.N > 0:
+                    t_arrays = self.text_search.index.search_batch_arrays([[r.query] for r in reqs], top_k=pool_max,
+                                                                          alpha_merge="max")
+        elif self.text_search is not None:
+            for g, r in enumerate(reqs):
+                with span("Backend/TextSearch", self.sink, trace[g]):
+                    t_hits[g] = list(self.text_search(queries=[r.query], top_k=pool[g]) or [])
+        if self.graph_expand is not None:
+            for g, r in enumerate(reqs):
+                with span("Backend/GraphExpand", self.sink, trace[g]):
+                    g_hits[g] = list(self.graph_expand(query=r.query, graph_id=getattr(r, "graph_id", "") or "",
+                                                       top_k=pool[g]) or [])
+
+        # ---- dense channel: d_ids / d_sc [B][kd], (-1, -inf) where a request has no row
+        dense_error: List[Optional[str]] = [None] * B
+        dense_filter: List[Any] = [None] * B
+        k_eff = [0] * B
+        state = None
+        d_ids = np.full((B, 0), -1, dtype=np.int64)
+        d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
+        with span("Backend/DenseRerank", self.sink, trace[0]):
+            try:
+                state = self._get_state(model_hint, trace[0])
+                if state["index"] is not None:
+                    ix, rows = state["index"], state["rows"]
+                    Q = self._embed_texts([r.query for r in reqs], model_hint, trace[0], dim=state["dim"])
+                    k_one, k_many = ix.max_k(1), ix.max_k(B)
+                    d_ids = np.full((B, max(min(pool_max, len(rows)), 0)), -1, dtype=np.int64)
+                    d_sc = np.full(d_ids.shape, -np.inf, dtype=np.float32)
+                    plain = []
+                    for g, r in enumerate(reqs):
+                        try:
+                            allow = self.dense_row_filter(r, rows) if self.dense_row_filter is not None else None
+                            if allow is None:
+                                plain.append(g)
+                                continue
+                            k_eff[g] = min(pool[g], len(rows), k_one)
+                            sc, ids = ix.search(Q[g:g + 1], k_eff[g], allow=allow)
+                            dense_filter[g] = ix.last_filter()
+                            d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
+                        except Exception as e:
+                            dense_error[g] = repr(e)
+                            d_ids[g] = -1
+                            logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
+                    if plain:
+                        try:
+                            k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
+                            sc, ids = ix.search(Q[plain] if len(plain) < B else Q, k_batch)
+                            for j, g in enumerate(plain):
+                                k_eff[g] = min(pool[g], k_batch)
+                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
+                        except Exception as e:
+                            for g in plain:
+                                dense_error[g] = repr(e)
+                                d_ids[g] = -1
+                            logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+            except Exception as e:     # reference policy: degrade, never raise out of run() (:229-231)
+                dense_error = [repr(e)] * B
+                d_ids = np.full((B, 0), -1, dtype=np.int64)
+                d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
+                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+
+        alphas = dict(alpha_text=self.alpha_text, alpha_graph=self.alpha_graph, alpha_dense=self.alpha_dense)
+        fast = (own and self.graph_expand is None and state is not None and state["index"] is not None
+                and (t_arrays is None or len(self.text_search.index.docs) == len(state["rows"])))
+        if fast:
+            norm_keys, sorted_ids = self._norm_keys(state)
+            if t_arrays is None:
+                t_arrays = (np.full((B, 0), -1, dtype=np.int64), np.zeros((B, 0), dtype=np.float64), np.zeros(B, dtype=np.int32))
+            chan_ptr, keys, scores, payload = _fusion.batch_entries(t_arrays[0], t_arrays[1], t_arrays[2], d_ids, d_sc, norm_keys,
+                                                                    pool=pool)
+            sizes = chan_ptr[3::3] - chan_ptr[0:-1:3]
+            fast = int(sizes.max()) <= _fusion.FUSE_MAX_ENTRIES
+        results = []
+        if fast:
+            rows = state["rows"]
+            ok, osc, nt, ng, nd, op, n_out = _fusion.fuse_entries_device_batch(chan_ptr, keys, scores, payload, top_k=top_k,
+                                                                              device=self.device, **alphas)
+            for g in range(B):
+                hits = []
+                for i in range(int(n_out[g])):
+                    rt, rd = int(op[g, i, 0]), int(op[g, i, 2])
+                    meta = _fusion.row_meta(rows[rt], "bm25") if rt >= 0 else {}
+                    if not meta.get("text") and rd >= 0:           # dense-only ids carry their own meta
+                        meta = _fusion.row_meta(rows[rd], "dense")
+                    meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[g, i]), float(ng[g, i]), float(nd[g, i])
+                    hits.append({"id": sorted_ids[int(ok[g, i])], "score": float(osc[g, i]), "meta": meta})
+                dk = keys[chan_ptr[3 * g + 2]:chan_ptr[3 * g + 3]]
+                results.append((hits, int(chan_ptr[3 * g + 1] - chan_ptr[3 * g]), int(np.unique(dk).shape[0])))
+        else:
+            if t_arrays is not None:
+                dl, sl, nl = t_arrays[0].tolist(), t_arrays[1].tolist(), t_arrays[2].tolist()
+                for g in range(B):
+                    c = min(nl[g], pool[g])
+                    t_hits[g] = self.text_search._hits(list(zip(dl[g][:c], sl[g][:c])))
+            dense_norm, questions = [], []
+            for g in range(B):
+                dense_hits = []
+                if state is not None:
+                    for s, i in zip(d_sc[g].tolist(), d_ids[g].tolist()):
+                        if i < 0:
+                            continue
+                        row = state["rows"][i]
+                        dense_hits.append({"id": _fusion.raw_hit_id(row), "score": float(s), "meta": _fusion.row_meta(row, "dense")})
+                dn = _fusion.dedupe_by_norm_id(dense_hits)
+                dense_norm.append(dn)
+                questions.append((t_hits[g], g_hits[g], {nid: h["score"] for nid, h in dn.items()}))
+            if self.fuse_on_device:
+                fused_all = _fusion.fuse_channels_device_batch(questions, top_k=10 ** 9, device=self.device, **alphas)
+            else:
+                fused_all = [_fusion.fuse_channels(*q, top_k=10 ** 9, **alphas) for q in questions]
+            for g, fused in enumerate(fused_all):
+                for h in fused:                               # dense-only ids carry their own meta
+                    if not h["meta"].get("text") and h["id"] in dense_norm[g]:
+                        meta = dict(dense_norm[g][h["id"]]["meta"])
+                        meta.update({k: v for k, v in h["meta"].items() if k.startswith("score_")})
+                        h["meta"] = meta
+                results.append((fused[:top_k[g]], len(t_hits[g]), len(dense_norm[g])))
+
+        out = []
+        for g, (hits, n_text, n_dense) in enumerate(results):
+            diagnostics = {
+                "queries": [reqs[g].query],
+                "bm25_candidates": n_text,
+                "graph_candidates": len(g_hits[g]),
+                "dense_scored": n_dense,
+                "weights": dict(alphas),
+                "pool": {"dense_pool_k": self.dense_pool_k, "final_top_k": top_k[g], "dense_pool_k_effective": k_eff[g]},
+                "resolved_embed_model": model_hint,
+                "dense_backend": "mrag_amd.DenseIndex",
+                "dense_error": dense_error[g],
+                "text_error": text_error,
+                "batch_size": B,
+            }
+            if dense_filter[g] is not None:
+                diagnostics["dense_filter"] = dense_filter[g]
+            out.append({"hits": hits, "diagnostics": diagnostics})
+        return out
+
+    def retrieve_batch(self, reqs) -> List[RetrievalOut]:
+        return [RetrievalOut(hits=[Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]],
+                             diagnostics=result.get("diagnostics", {})) for result in self.run_batch(reqs)]

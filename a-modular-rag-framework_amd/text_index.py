@@ -196,6 +196,41 @@ class HipBM25Index:
         dl, sl = docs.tolist(), scores.tolist()
         return [list(zip(dl[g][:c], sl[g][:c])) for g, c in enumerate(n.tolist())]
 
+    def search_batch_arrays(self, questions: Sequence[Sequence[str]], top_k: int = 20, alpha_merge: str = "max",
+                            allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search_batch` as the call's own arrays: ``(docs int64 [B][k], scores float64 [B][k], n int32 [B])`` with
+        ``k = min(top_k, N)`` (0 for an empty index or ``top_k <= 0``); question g's answer is its first ``n[g]`` slots,
+        the others hold (-1, 0.0).  What the batched fusion reads without building a tuple per hit."""
+        questions = [list(qs) for qs in questions]
+        nq = len(questions)
+        if not self.N or not questions or top_k <= 0:
+            return np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0), dtype=np.float64), np.zeros(nq, dtype=np.int32)
+        bits = self._allow_words(allow) if allow is not None else None
+        g_ptr, q_ptr, q_terms, q_idf = [0], [0], [], []
+        known: Dict[str, Tuple[int, float]] = {}
+        for qs in questions:
+            for q in qs:
+                for t in tokenize(q):
+                    e = known.get(t)
+                    if e is None:
+                        e = known[t] = (self._term_id.get(t, -1), self._idf(t))
+                    q_terms.append(e[0])
+                    q_idf.append(e[1])
+                q_ptr.append(len(q_terms))
+            g_ptr.append(len(q_ptr) - 1)
+        k = int(min(top_k, self.N))
+        gp = np.asarray(g_ptr, dtype=np.int32)
+        qp = np.asarray(q_ptr, dtype=np.int32)
+        qt = np.asarray(q_terms if q_terms else [0], dtype=np.int32)
+        qi = np.asarray(q_idf if q_idf else [0.0], dtype=np.float64)
+        docs = np.empty((nq, k), dtype=np.int64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        n = np.zeros(nq, dtype=np.int32)
+        N.check(self._lib.mrag_bm25_search_batch(self._h, nq, gp.ctypes.data, qp.ctypes.data, qt.ctypes.data, qi.ctypes.data,
+                                                 1 if alpha_merge == "sum" else 0, k, bits.ctypes.data if bits is not None else None,
+                                                 docs.ctypes.data, scores.ctypes.data, n.ctypes.data, None))
+        return docs, scores, n
+
     def set_scratch_limit(self, nbytes: int) -> None:
         """Bytes of fp64 score rows (8 * N per expanded query) one chunk of :meth:`search_batch` may use
         (``mrag_bm25_set_scratch_limit``); ``<= 0`` restores the default.  Results do not depend on it."""

@@ -388,6 +388,7 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
                    double alpha_text, double alpha_graph, double alpha_dense, int top_k, int32_t* out_keys,
                    double* out_scores, double* out_text_norm, double* out_graph_norm, double* out_dense_norm,
                    int* out_n, void* stream);
+/* The same fusion for a batch of questions in one launch: mrag_fuse_batch.h, included below. */
 
 #ifdef __cplusplus
 }
@@ -395,5 +396,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 
 /* Additions to the ABI since its 64 entry points: each in a header of its own, part of this one. */
 #include "mrag_bm25_batch.h"
+#include "mrag_fuse_batch.h"
 
 #endif /* MRAG_H_ */
