@@ -1,4 +1,5 @@
-"""ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h).  There is no CPU fallback: a missing
+"""ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h,
+include/mrag_rerank_batch.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -126,6 +127,11 @@ FUSE_BATCH_SIGNATURES = {
                              _vp, _vp],
 }
 
+# include/mrag_rerank_batch.h
+RERANK_BATCH_SIGNATURES = {
+    "mrag_index_score_rows_batch": [_h, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -145,7 +151,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(str(p))
-    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

@@ -13,7 +13,9 @@ injected when declared).
                           ``HybridRetrievalBackend`` (:303-390), hit ids / meta / fusion keys
                           unchanged.  Optional text / graph channels are injected callables
                           with the reference's hit shape and fused with the reference's
-                          min-max + alpha rule.
+                          min-max + alpha rule.  ``dense_mode="rerank"``: the dense channel
+                          scores the text channel's candidates (the reference's step 4, :332-334)
+                          instead of searching the corpus.
 """
 from __future__ import annotations
 
@@ -85,12 +87,7 @@ class HipDenseReranker:
     def score(self, *, query: str, candidates: List[Dict[str, Any]], trace_id: str) -> Dict[str, float]:
         if not candidates:
             return {}
-        ids, texts = [], []
-        for h in candidates[: self.max_pool]:
-            t = (h.get("meta") or {}).get("text") or ""
-            if t:
-                ids.append(h["id"])
-                texts.append(t)
+        ids, texts = self._select(candidates)
         if not texts:
             return {}
         model_hint = self._resolve_embed_model()
@@ -102,6 +99,11 @@ class HipDenseReranker:
         known: Dict[int, float] = {}                # candidate position -> score from the stored row
         if self.corpus is not None:
             known = self._lookup(ids, texts, qv, model_hint, trace_id)
+        return self._score_rest(ids, texts, qv, known, model_hint, trace_id)
+
+    def _score_rest(self, ids: List[str], texts: List[str], qv, known: Dict[int, float], model_hint: str,
+                    trace_id: str) -> Dict[str, float]:
+        """The candidates ``known`` does not cover, embedded in chunks and scored (:234-245), merged with ``known``."""
         todo = [i for i in range(len(texts)) if i not in known]
         vecs: List[Any] = []
         step = max(8, int(self.embed_batch))        # :234
@@ -117,6 +119,88 @@ class HipDenseReranker:
         scored = dict(zip(todo[:n], self._cosines(qv, vecs[:n])))
         scored.update(known)
         return {ids[i]: scored[i] for i in range(len(ids)) if i in scored}
+
+    def _select(self, candidates):
+        """The candidates ``score`` looks at (:218-224): the leading ``max_pool``, those without text skipped."""
+        ids, texts = [], []
+        for h in (candidates or [])[: self.max_pool]:
+            t = (h.get("meta") or {}).get("text") or ""
+            if t:
+                ids.append(h["id"])
+                texts.append(t)
+        return ids, texts
+
+    def score_batch(self, *, queries: List[str], candidates: List[List[Dict[str, Any]]],
+                    trace_ids: List[str]) -> List[Dict[str, float]]:
+        """:meth:`score` for every question of a list: one ``{id: score}`` dict per question, each equal to
+        ``score(query=, candidates=, trace_id=)`` of that question alone.  The queries are embedded in chunks of
+        ``embed_batch`` instead of one call each, and with ``corpus=`` the known candidates of ALL questions are scored
+        in one ``DenseIndex.score_rows_batch``; each question's unknown remainder is embedded and scored as in
+        :meth:`score`.  If a query chunk raises or comes back with the wrong count, a wrong dim or an all-zero vector (the
+        router's answer to a provider failure), the whole call is the loop of :meth:`score` -- the per-question error
+        policy (:229-231) is then the reference's."""
+        queries, candidates, trace_ids = list(queries), list(candidates), list(trace_ids)
+        B = len(queries)
+        if len(candidates) != B or len(trace_ids) != B:
+            raise ValueError(f"{B} queries, {len(candidates)} candidate lists, {len(trace_ids)} trace ids")
+        sel = [self._select(c) for c in candidates]
+        live = [g for g in range(B) if sel[g][1]]    # the questions for which score() reaches the query embed
+        out: List[Dict[str, float]] = [{} for _ in range(B)]
+        if not live:
+            return out
+        model_hint = self._resolve_embed_model()
+        qvs: Dict[int, Any] = {}
+        step = max(1, int(self.embed_batch))
+        try:
+            for lo in range(0, len(live), step):
+                chunk = live[lo:lo + step]
+                got = list(_vectors(self.router.embed(model_hint=model_hint, texts=[queries[g] for g in chunk],
+                                                      require={"trace_id": trace_ids[chunk[0]]})) or [])
+                if len(got) != len(chunk):
+                    raise ValueError(f"{len(got)} vectors for {len(chunk)} queries")
+                qvs.update(zip(chunk, got))
+            dim = len(qvs[live[0]])
+            if not dim or any(len(qvs[g]) != dim for g in live):
+                raise ValueError("query vectors of differing or zero dim")
+            if not all(any(qvs[g]) for g in live):     # the router's answer to a provider failure (llm_router.py:124-129)
+                raise ValueError("an all-zero query vector")
+        except Exception as e:
+            logger.error("[HipDenseReranker] batched query embed failed, scoring question by question: %s", e)
+            return [self.score(query=q, candidates=c, trace_id=t) for q, c, t in zip(queries, candidates, trace_ids)]
+        known: Dict[int, Dict[int, float]] = {}
+        if self.corpus is not None:
+            known = self._lookup_batch(live, sel, qvs, dim, model_hint, trace_ids[live[0]])
+        for g in live:
+            out[g] = self._score_rest(sel[g][0], sel[g][1], qvs[g], known.get(g, {}), model_hint, trace_ids[g])
+        return out
+
+    def _lookup_batch(self, live, sel, qvs, dim: int, model_hint: str, trace_id: str) -> Dict[int, Dict[int, float]]:
+        """:meth:`_lookup` for the questions ``live``: question -> {candidate position: score}, the known candidates of
+        all of them scored in one call.  Any failure degrades to "nothing known" for every question."""
+        try:
+            state = self.corpus._get_state(model_hint, trace_id)
+            ix, row_of, rows = state["index"], state["row_of"], state["rows"]
+            if ix is None or dim != state["dim"]:
+                return {}
+            who, pos, rid = [], [], []
+            for g in live:
+                p, r = [], []
+                for i, (hid, text) in enumerate(zip(*sel[g])):
+                    row = row_of.get(hid)
+                    if row is not None and (rows[row].get("text") or "") == text:
+                        p.append(i)
+                        r.append(row)
+                if p:
+                    who.append(g)
+                    pos.append(p)
+                    rid.append(np.asarray(r, dtype=np.int64))
+            if not who:
+                return {}
+            sc = ix.score_rows_batch(np.asarray([qvs[g] for g in who], dtype=np.float32), rid)
+            return {g: {i: float(v) for i, v in zip(p, s)} for g, p, s in zip(who, pos, sc)}
+        except Exception as e:
+            logger.error("[HipDenseReranker] row lookup failed, embedding every candidate: %s", e)
+            return {}
 
     def _lookup(self, ids: List[str], texts: List[str], qv, model_hint: str, trace_id: str) -> Dict[int, float]:
         """Scores of the candidates that are rows of ``self.corpus``'s index (same embedding model, same
@@ -153,7 +237,7 @@ class DenseRetrievalBackend:
                  graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None,
                  text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
                  fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
-                 dense_row_filter: Optional[Any] = None):
+                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search"):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -181,6 +265,13 @@ class DenseRetrievalBackend:
         self._own_text_search = None                     # the searcher _bm25_searcher() made over index_path, if any
         if text_channel not in (None, "bm25"):
             raise ValueError(f"unknown text_channel {text_channel!r} (supported: 'bm25')")
+        # dense_mode="search": the dense channel is a corpus-wide top-k (above).  "rerank": it scores the text channel's
+        # candidates instead -- the reference's step 4 (retrieval_backend.py:332-334) with max_pool = pool
+        if dense_mode not in ("search", "rerank"):
+            raise ValueError(f"unknown dense_mode {dense_mode!r} (supported: 'search', 'rerank')")
+        if dense_mode == "rerank" and dense_row_filter is not None:
+            raise ValueError("dense_row_filter restricts the corpus-wide search: it has no meaning with dense_mode='rerank'")
+        self.dense_mode = dense_mode
         self._state = None
 
     # -- corpus index: built once per (file signature, model), shared process-wide --------------
@@ -348,9 +439,18 @@ class DenseRetrievalBackend:
             except Exception as e:     # degrade like the dense channel: report, keep serving the other channels
                 text_error = repr(e)
                 logger.error("[DenseRetrievalBackend] BM25 channel unavailable: %s", e)
+        rerank = self.dense_mode == "rerank"
+        own = rerank and self._is_own_searcher()
+        t_docs: List[int] = []                           # rerank over the own searcher: the hits' document positions
         if self.text_search is not None:
             with span("Backend/TextSearch", self.sink, trace_id):
-                t_hits = list(self.text_search(queries=[req.query], top_k=pool) or [])
+                if own:
+                    ranked = (self.text_search.index.search([req.query], top_k=pool, alpha_merge="max")
+                              if self.text_search.index.N > 0 else [])
+                    t_docs = [int(d) for d, _ in ranked]
+                    t_hits = self.text_search._hits(ranked)
+                else:
+                    t_hits = list(self.text_search(queries=[req.query], top_k=pool) or [])
         if self.graph_expand is not None:
             with span("Backend/GraphExpand", self.sink, trace_id):
                 g_hits = list(self.graph_expand(query=req.query, graph_id=getattr(req, "graph_id", "") or "",
@@ -362,8 +462,11 @@ class DenseRetrievalBackend:
         k_eff = 0
         with span("Backend/DenseRerank", self.sink, trace_id):      # same span name as :332
             try:
-                state = self._get_state(model_hint, trace_id)
-                if state["index"] is not None:
+                state = None if rerank else self._get_state(model_hint, trace_id)
+                if rerank and t_hits:
+                    dense_hits = self._rerank_one(req, t_hits[:pool], t_docs[:pool] if own else None, pool, model_hint, trace_id)
+                    k_eff = len(dense_hits)
+                if state is not None and state["index"] is not None:
                     qv = np.asarray(_vectors(self.router.embed(model_hint=model_hint, texts=[req.query],
                                                                require={"trace_id": trace_id}))[0], dtype=np.float32)
                     if qv.shape[0] != state["dim"]:
@@ -414,9 +517,44 @@ class DenseRetrievalBackend:
             "dense_error": dense_error,
             "text_error": text_error,
         }
+        if rerank:
+            diagnostics["dense_mode"] = "rerank"
         if dense_filter is not None:
             diagnostics["dense_filter"] = dense_filter
         return {"hits": fused, "diagnostics": diagnostics}
+
+    # -- dense_mode="rerank": the dense channel scores the text channel's candidates ------------------------------------
+    def _is_own_searcher(self) -> bool:
+        """The text channel is the BM25 searcher this backend made over ``index_path``: its document positions are then
+        the dense state's rows (both read the file's non-empty lines in order)."""
+        return self.text_channel == "bm25" and self.text_search is not None and self.text_search is self._own_text_search
+
+    def _rows_are_docs(self, state) -> bool:
+        return state["index"] is not None and len(self.text_search.index.docs) == len(state["rows"])
+
+    @staticmethod
+    def _scored_hits(cands: List[Dict[str, Any]], scores: Dict[str, float]) -> List[Dict[str, Any]]:
+        """The re-ranker's ``{raw id: score}`` as dense hits that carry the candidates' meta, so that they are keyed by
+        normalised id like the text hits (the backend's fusion convention; the reference's raw-id keying, SURVEY a7,
+        stays consciously fixed)."""
+        return [{"id": h["id"], "score": float(scores[h["id"]]), "meta": dict(h.get("meta") or {})}
+                for h in cands if h.get("id") in scores]
+
+    def _rerank_one(self, req, cands, docs, pool: int, model_hint: str, trace_id: str) -> List[Dict[str, Any]]:
+        """The dense hits of one request in rerank mode.  ``docs`` (own searcher): the candidates' document positions --
+        they are scored as corpus rows by ``score_rows``, rows whose ``doc_id`` occurs twice in the file included, and
+        nothing is re-embedded.  Otherwise (injected searcher) the candidates go through :class:`HipDenseReranker` with
+        this backend as its corpus.  :meth:`run_batch` makes the same choice, so both score the same thing."""
+        if docs is not None:
+            state = self._get_state(model_hint, trace_id)
+            if self._rows_are_docs(state):
+                qv = self._embed_texts([req.query], model_hint, trace_id, dim=state["dim"])[0]      # validated as run_batch's
+                sc = state["index"].score_rows(qv, np.asarray(docs, dtype=np.int64))
+                rows = state["rows"]
+                return [{"id": _fusion.raw_hit_id(rows[d]), "score": float(s), "meta": _fusion.row_meta(rows[d], "dense")}
+                        for d, s in zip(docs, sc)]
+        rr = HipDenseReranker(self.router, max_pool=pool, embed_batch=self.embed_batch, device=self.device, corpus=self)
+        return self._scored_hits(cands, rr.score(query=req.query, candidates=cands, trace_id=trace_id))
 
     def retrieve(self, req) -> RetrievalOut:
         result = self.run(req)
@@ -438,7 +576,9 @@ class DenseRetrievalBackend:
         searches are exact with a declared order, so a prefix is the smaller search's answer).  Requests for which
         ``dense_row_filter`` returns a set are searched one by one with their ``allow``; an injected ``text_search`` and
         ``graph_expand`` are called once per request.  Like :meth:`run` it degrades and never raises out of the dense
-        channel.  Diagnostics are :meth:`run`'s plus ``batch_size``."""
+        channel.  Diagnostics are :meth:`run`'s plus ``batch_size``.  With ``dense_mode="rerank"`` the dense search is
+        replaced by one ``DenseIndex.score_rows_batch`` over every question's leading text candidates (own BM25 searcher)
+        or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`."""
         from .text_index import HipBM25TextSearcher
         reqs = list(reqs)
         B = len(reqs)
@@ -487,10 +627,16 @@ class DenseRetrievalBackend:
         state = None
         d_ids = np.full((B, 0), -1, dtype=np.int64)
         d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
+        rerank = self.dense_mode == "rerank"
+        rr_hits: Optional[List[List[Dict[str, Any]]]] = None      # rerank through HipDenseReranker: the dense hits per request
         with span("Backend/DenseRerank", self.sink, trace[0]):
             try:
-                state = self._get_state(model_hint, trace[0])
-                if state["index"] is not None:
+                if rerank:
+                    state, d_ids, d_sc, k_eff, dense_error, rr_hits = self._rerank_batch(reqs, pool, trace, model_hint,
+                                                                                         t_arrays, t_hits)
+                else:
+                    state = self._get_state(model_hint, trace[0])
+                if not rerank and state["index"] is not None:
                     ix, rows = state["index"], state["rows"]
                     Q = self._embed_texts([r.query for r in reqs], model_hint, trace[0], dim=state["dim"])
                     k_one, k_many = ix.max_k(1), ix.max_k(B)
@@ -565,7 +711,9 @@ class DenseRetrievalBackend:
             dense_norm, questions = [], []
             for g in range(B):
                 dense_hits = []
-                if state is not None:
+                if rr_hits is not None:
+                    dense_hits = rr_hits[g]
+                elif state is not None:
                     for s, i in zip(d_sc[g].tolist(), d_ids[g].tolist()):
                         if i < 0:
                             continue
@@ -601,10 +749,82 @@ class DenseRetrievalBackend:
                 "text_error": text_error,
                 "batch_size": B,
             }
+            if rerank:
+                diagnostics["dense_mode"] = "rerank"
             if dense_filter[g] is not None:
                 diagnostics["dense_filter"] = dense_filter[g]
             out.append({"hits": hits, "diagnostics": diagnostics})
         return out
+
+    def _rerank_batch(self, reqs, pool, trace, model_hint: str, t_arrays, t_hits):
+        """The dense channel of :meth:`run_batch` in rerank mode: ``(state, d_ids, d_sc, k_eff, dense_error, rr_hits)``.
+        Own searcher: every question's leading ``min(n, pool[g])`` documents of the batch search are scored as corpus rows
+        in ONE ``score_rows_batch`` after one ``_embed_texts`` of the queries (d_ids = those documents, d_sc = their
+        scores, for the ``batch_entries`` path).  Otherwise one ``HipDenseReranker.score_batch`` over the requests' text
+        hits (``rr_hits``: its scores as dense hits).  The choice is :meth:`_rerank_one`'s.  Requests without candidates
+        have an empty dense channel and no error; a failure is reported for the others and never raised."""
+        B = len(reqs)
+        state, rr_hits = None, None
+        d_ids, d_sc = np.full((B, 0), -1, dtype=np.int64), np.full((B, 0), -np.inf, dtype=np.float32)
+        k_eff: List[int] = [0] * B
+        dense_error: List[Optional[str]] = [None] * B
+        own = self._is_own_searcher()
+        if t_arrays is not None:                     # a batched BM25 search: the backend's own searcher or an injected one
+            n_c = [min(int(n), pool[g]) for g, n in enumerate(t_arrays[2].tolist())]
+        elif own:
+            n_c = [0] * B
+        else:
+            n_c = [len(t_hits[g][:pool[g]]) for g in range(B)]
+        live = [g for g in range(B) if n_c[g] > 0]
+        if not live:
+            return state, d_ids, d_sc, k_eff, dense_error, rr_hits
+        try:
+            by_row = False
+            if own:
+                state = self._get_state(model_hint, trace[0])
+                by_row = self._rows_are_docs(state)
+            if by_row:
+                try:
+                    Q = self._embed_texts([reqs[g].query for g in live], model_hint, trace[0], dim=state["dim"])
+                except Exception:                        # one bad vector fails its chunk: find out whose, as run() would
+                    good, vecs = [], []
+                    for g in live:
+                        try:
+                            vecs.append(self._embed_texts([reqs[g].query], model_hint, trace[g], dim=state["dim"])[0])
+                            good.append(g)
+                        except Exception as e:
+                            dense_error[g] = repr(e)
+                            logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
+                    live, Q = good, np.asarray(vecs, dtype=np.float32).reshape(len(good), state["dim"])
+                ptr = np.zeros(len(live) + 1, dtype=np.int64)
+                np.cumsum([n_c[g] for g in live], out=ptr[1:])
+                flat = np.concatenate([t_arrays[0][g, :n_c[g]] for g in live]) if live else np.zeros(0, dtype=np.int64)
+                _, sc = state["index"].score_rows_batch(Q, (ptr, flat))
+                ids_out = np.full(t_arrays[0].shape, -1, dtype=np.int64)
+                sc_out = np.full(t_arrays[0].shape, -np.inf, dtype=np.float32)
+                for j, g in enumerate(live):
+                    ids_out[g, :n_c[g]], sc_out[g, :n_c[g]] = flat[ptr[j]:ptr[j + 1]], sc[ptr[j]:ptr[j + 1]]
+                    k_eff[g] = n_c[g]
+                d_ids, d_sc = ids_out, sc_out
+            else:
+                if t_arrays is not None:                 # an injected BM25 searcher, or documents that are not the state's
+                    dl, sl = t_arrays[0].tolist(), t_arrays[1].tolist()      # rows: the hits, scored by id and text
+                    for g in range(B):
+                        t_hits[g] = self.text_search._hits(list(zip(dl[g][:n_c[g]], sl[g][:n_c[g]])))
+                cands = [t_hits[g][:pool[g]] for g in range(B)]
+                rr = HipDenseReranker(self.router, max_pool=max(pool), embed_batch=self.embed_batch, device=self.device,
+                                      corpus=self)
+                scores = rr.score_batch(queries=[r.query for r in reqs], candidates=cands, trace_ids=trace)
+                rr_hits = [self._scored_hits(c, s) for c, s in zip(cands, scores)]
+                k_eff = [len(h) for h in rr_hits]
+        except Exception as e:
+            state, rr_hits = None, None
+            d_ids, d_sc = np.full((B, 0), -1, dtype=np.int64), np.full((B, 0), -np.inf, dtype=np.float32)
+            k_eff = [0] * B
+            for g in live:
+                dense_error[g] = repr(e)
+            logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+        return state, d_ids, d_sc, k_eff, dense_error, rr_hits
 
     def retrieve_batch(self, reqs) -> List[RetrievalOut]:
         return [RetrievalOut(hits=[Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]],

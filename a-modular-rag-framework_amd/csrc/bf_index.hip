@@ -65,11 +65,13 @@ struct BfIndex : Object {
   int ld8 = 0;
   uint8_t* rows8 = nullptr;
   DevBuf qbuf8, cand;                       // quantised queries [nq padded][ld8]; candidates (fp8 scores | local rows)
+  DevBuf rr_q;                              // batched re-rank: its prepared queries [n_questions][ld] -- not qbuf, whose zero-padding
+                                            // bookkeeping (q_cleared_*, q_dirty_rows) a 10 000-question re-rank must not disturb
   int last_refine = -1, last_regime = -1;   // of the last mrag_index_search_fp8
   ~BfIndex() override {
     if (rows) (void)hipFree(rows);
     if (rows8) (void)hipFree(rows8);
-    qbuf8.release(); cand.release();
+    qbuf8.release(); cand.release(); rr_q.release();
     qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
     rslots.release(); out_cnt.release();
     fw.release();   // (the destroy path synchronised the device)
@@ -772,6 +774,60 @@ int mrag_index_score_rows(mrag_handle h, const void* query, int q_dtype, int nor
                      ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)(st + qb), n, ix->n, (float*)(st + qb + ib));
   MRAG_HIP(hipGetLastError());
   MRAG_HIP(hipMemcpyAsync(out_scores, st + qb + ib, ob, hipMemcpyDeviceToHost, stream));
+  MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
+
+int mrag_index_score_rows_batch(mrag_handle h, const void* queries, int q_dtype, int normalize, int64_t n_questions,
+                                const int64_t* row_ptr, const int64_t* row_ids, float* out_scores, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (n_questions < 0) return fail(MRAG_ERR_INVALID, "n_questions < 0");
+  if (n_questions == 0) return MRAG_OK;
+  if (!row_ptr) return fail(MRAG_ERR_INVALID, "row_ptr is NULL");
+  if (row_ptr[0] != 0) return fail(MRAG_ERR_INVALID, "row_ptr[0] = %lld, not 0 (question 0)", (long long)row_ptr[0]);
+  for (int64_t g = 0; g < n_questions; ++g)
+    if (row_ptr[g + 1] < row_ptr[g])
+      return fail(MRAG_ERR_INVALID, "row_ptr decreases at question %lld (%lld -> %lld)", (long long)g, (long long)row_ptr[g],
+                  (long long)row_ptr[g + 1]);
+  const int64_t n = row_ptr[n_questions];
+  if (n == 0) return MRAG_OK;                 // a batch of empty questions
+  if (!queries || !row_ids || !out_scores) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  std::vector<RerankDesc> desc;
+  MRAG_TRY(rerank_batch_plan(n_questions, row_ptr, desc));
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  // staging: [query src | descriptors | row ids | scores]; prepared queries in rr_q
+  const size_t qbytes = (size_t)n_questions * ix->dim * esz, dbytes = desc.size() * sizeof(RerankDesc);
+  const size_t qb = round_up((int64_t)qbytes, 256), db = round_up((int64_t)dbytes, 256), ib = round_up(n * 8, 256), ob = (size_t)n * 4;
+  MRAG_TRY(ix->stage_in.ensure(qb + db + ib + ob));
+  MRAG_TRY(ix->rr_q.ensure((size_t)n_questions * ix->ld * 2));
+  if ((n_questions + 3) / 4 > 2147483647ll)   // (out of reach: the two buffers above do not fit any device at this size)
+    return fail(MRAG_ERR_HIP, "row preparation grid for %lld questions outside HIP's limits", (long long)n_questions);
+  char* st = (char*)ix->stage_in.p;
+  // the uploads read `desc` and the caller's buffers asynchronously: whatever fails below, the stream is synchronised
+  // before they go out of scope
+  const auto enqueue = [&]() -> int {
+    MRAG_HIP(hipMemcpyAsync(st, queries, qbytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(st + qb, desc.data(), dbytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(st + qb + db, row_ids, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    // the single call's preparation of its one row, for every row (row g's source keeps the 16-byte alignment of row 0
+    // wherever launch_prep_rows asks for it: dim % 8 == 0 there)
+    MRAG_TRY(launch_prep_rows(st, q_dtype, n_questions, ix->dim, ix->rr_q.p, ix->ld, ix->dtype,
+                              normalize && ix->metric == MRAG_METRIC_COSINE, stream));
+    MRAG_TRY(launch_rerank_batch(ix->rows, (const uint16_t*)ix->rr_q.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0,
+                                 (const RerankDesc*)(st + qb), (int64_t)desc.size(), (const int64_t*)(st + qb + db), ix->n,
+                                 (float*)(st + qb + db + ib), stream));
+    MRAG_HIP(hipMemcpyAsync(out_scores, st + qb + db + ib, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  };
+  const int status = enqueue();
+  if (status != MRAG_OK) {
+    (void)hipStreamSynchronize(stream);
+    return status;
+  }
   MRAG_HIP(hipStreamSynchronize(stream));
   return MRAG_OK;
 }

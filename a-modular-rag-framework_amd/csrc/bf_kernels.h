@@ -97,6 +97,22 @@ int launch_merge(MergeParams mp, int* flags, int* need, hipStream_t stream);
 // range search (bf_merge.hip): the per-query sums of the count slots of one launch (T query tiles x S splits) -> out[0 .. nq)
 int launch_range_sum(const int* slots, int S, int64_t nq, int64_t* out, hipStream_t stream);
 
+// The batched candidate lookup (bf_rerank_batch.hip).  One workgroup scores one descriptor: entries [first, first + count)
+// of the flat id list, all of question `question`.  64 rows per descriptor: each of the 4 waves amortises the one read of
+// its question's query row over 16 stored rows (6 % extra traffic), the reference's 200-candidate pool still spreads
+// over 4 workgroups, and a 10 000 x 200 batch is 40 000 workgroups -- some 150 per CU, so a tail does not show.
+constexpr int RERANK_ROWS = 64;
+struct RerankDesc {
+  int64_t question, first;
+  int32_t count, pad;
+};
+// host: the descriptors of row_ptr [n_questions + 1] (validated by the caller), in question order; empty questions get none
+int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<RerankDesc>& desc);
+// out[e] = <queries[question of e], rows[ids[e]]> for every entry the n_desc descriptors cover (0.0 for an id outside
+// [0, n_rows)); prepared queries at pitch ld; one launch per 2^31 - 1 descriptors
+int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const RerankDesc* desc, int64_t n_desc,
+                        const int64_t* ids, int64_t n_rows, float* out, hipStream_t stream);
+
 #if defined(__HIPCC__)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -447,6 +447,42 @@ class DenseIndex:
                                                 ids.shape[0], out.ctypes.data, None))
         return out
 
+    def score_rows_batch(self, queries, row_ids, normalize: Optional[bool] = None):
+        """:meth:`score_rows` for a batch of questions in one call (``mrag_index_score_rows_batch``): ``queries`` is
+        ``[nq, dim]``, ``row_ids`` either a sequence of nq int arrays -- the result is then a list of nq float32 arrays --
+        or a pair ``(row_ptr int64 [nq + 1], flat_ids)`` -- the result is then ``(row_ptr, flat_scores)``.  Question g's
+        scores are bit for bit ``score_rows(queries[g], ids of g)``.  No library call for nq = 0 or no entries."""
+        if normalize is None:
+            normalize = self.metric == "cosine"
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1 and q.shape[0] == 0:
+            q = q.reshape(0, self.dim)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries have shape {q.shape}, index has dim {self.dim}")
+        nq = q.shape[0]
+        csr = isinstance(row_ids, tuple) and len(row_ids) == 2
+        if csr:
+            ptr = np.ascontiguousarray(row_ids[0], dtype=np.int64).reshape(-1)
+            ids = np.ascontiguousarray(row_ids[1], dtype=np.int64).reshape(-1)
+            if ptr.shape[0] != nq + 1:
+                raise ValueError(f"row_ptr has {ptr.shape[0]} entries for {nq} queries (expected {nq + 1})")
+            if ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != ids.shape[0]:
+                raise ValueError("row_ptr must start at 0, never decrease and end at the number of ids")
+        else:
+            lists = [np.asarray(r, dtype=np.int64).reshape(-1) for r in row_ids]
+            if len(lists) != nq:
+                raise ValueError(f"{len(lists)} id lists for {nq} queries")
+            ptr = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum([r.shape[0] for r in lists], out=ptr[1:])
+            ids = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros(0, dtype=np.int64)
+        out = np.empty(ids.shape[0], dtype=np.float32)
+        if nq and ids.shape[0]:
+            N.check(self._lib.mrag_index_score_rows_batch(self._h, q.ctypes.data, N.MRAG_F32, int(bool(normalize)), nq,
+                                                          ptr.ctypes.data, ids.ctypes.data, out.ctypes.data, None))
+        if csr:
+            return ptr, out
+        return [out[ptr[g]:ptr[g + 1]] for g in range(nq)]
+
     def stored_bits(self) -> np.ndarray:
         """The stored rows as their 16-bit patterns ([n, dim] uint16, fp16 or bf16 per ``dtype``):
         what the embedding cache keeps, so that a warm start re-adds the exact bits K1 produced."""

@@ -177,6 +177,7 @@ int mrag_index_last_fp8(mrag_handle h, int* out_refine, int* out_regime);
  * normalised); an id outside [0, size) scores 0.0 like an unusable vector (:193-197).  Host buffers. */
 int mrag_index_score_rows(mrag_handle h, const void* query, int q_dtype, int normalize, const int64_t* row_ids,
                           int64_t n, float* out_scores, void* stream);
+/* The same lookup for a batch of questions in one launch: mrag_rerank_batch.h, included below. */
 /* timing hooks for bench.py: device time in ms of the dominant kernel (fused similarity
  * GEMM + top-k) and of the whole search of the LAST mrag_index_search call, measured with
  * hipEvents on the stream the kernels were launched on.  Blocks until that call is done. */
@@ -397,5 +398,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 /* Additions to the ABI since its 64 entry points: each in a header of its own, part of this one. */
 #include "mrag_bm25_batch.h"
 #include "mrag_fuse_batch.h"
+#include "mrag_rerank_batch.h"
 
 #endif /* MRAG_H_ */
