@@ -247,7 +247,7 @@ class DenseRetrievalBackend:
         # text_channel="bm25": the reference's BM25 channel (text_index.py, retrieval_backend.py:102-128) over the same
         # docs.jsonl, on the device (mrag_amd.text_index), built once per file and shared process-wide
         self.text_channel, self.bm25_k1, self.bm25_b = text_channel, float(bm25_k1), float(bm25_b)
-        self.fuse_on_device = bool(fuse_on_device)     # a7's arithmetic in one launch (mrag_fuse_topk) instead of host Python
+        self.fuse_on_device = bool(fuse_on_device)     # a7's arithmetic in one launch (mrag_fuse_topk_batch) instead of host Python
         # corpus ingest: when the provider the router resolves can embed in bulk on the device (``embed_device``), the
         # index is built from docs.jsonl through it in ``bulk_batch``-passage batches (text_index.py:32-53: the reference
         # builds its index from the file in one go); the router path below stays as the fallback / error-policy reference

@@ -1,5 +1,7 @@
 // BM25 text channel on the device: the reference's BM25LiteIndex.search
-// (app/modules/retrieval/text_index.py:59-97) over CSR postings resident in HBM.
+// (app/modules/retrieval/text_index.py:59-97) over CSR postings resident in HBM, for MANY questions per call, each with
+// its own expanded queries, optionally restricted to an allow-set of documents.  There is one search path:
+// mrag_bm25_search_batch runs it for its questions, mrag_bm25_search is a batch of one question without an allow-set.
 //
 //   reference                                   here
 //   tf: term -> {doc: tf}        (:27,45-47)    CSR: indptr[term], post_doc[], post_tf[] (docs ascending)
@@ -9,27 +11,89 @@
 //     score += idf*(f*(k1+1))/(f+K(doc))        its postings into that query's dense fp64 score row -- a document
 //                                               receives its contributions in token order, exactly the reference's
 //                                               left-to-right fp64 sum (same IEEE operations, no contraction)
-//   merge over queries: max | sum (:90-91)      bm25_merge_kernel, queries in order
+//   merge over queries: max | sum (:90-91)      bm25_merge_kernel, a question's queries in order
 //   keep s > 0, sort desc, [:top_k] (:92-96)    MSB-first radix select over (score bits, ~doc) + rank by counting:
 //                                               (score desc, doc asc) -- the reference's tie order is the iteration
 //                                               order of a set of ints; doc-ascending is this library's declared order
-// The selection kernels (bm25_hist_kernel, bm25_gather_kernel) launch at most 1024 workgroups of 256 threads: one sweep
+//
+//   chunk      questions are taken in order while their expanded queries fit the score-row scratch (one fp64 row of n_docs
+//              per expanded query; mrag_bm25_set_scratch_limit), at most 65 535 rows (a job is a grid row in y) and at
+//              most BM25_CHUNK_QUESTIONS questions that have a query.  A question is never split: one with more rows than
+//              the limit allows gets a chunk of its own.  A question without queries needs no row and no launch.
+//   scatter    one launch per token position: y = the (row, position) jobs of the whole chunk, x covers the longest range
+//   merge      y = question: max / sum over its rows in query order, s > 0 ? s : 0, 0 for a document outside the allow-set;
+//              the merged row is written over the question's FIRST score row (a thread owns its document: in place is safe),
+//              so the scratch is exactly one row per expanded query
+//   select     y = question: MSB-first radix select over (score bits, ~doc) with per-question histograms and counters;
+//              every workgroup rebuilds the selection state from the earlier passes' histograms with a 256-thread suffix
+//              scan per pass (not a one-thread walk: with a grid of 1024 x questions workgroups the walk would cost more
+//              than the documents), a question whose bucket is settled reads no document again
+//   rank       y = question: rank by counting into the call's result buffer [n_questions][k]
+// The selection kernels (bm25_hist_kernel, bm25_gather_kernel) launch at most 1024 workgroups of 256 threads in x: one sweep
 // covers 1024 * 256 = 262 144 documents and a larger corpus is covered by their grid-stride loops, so a corpus above
 // 262 144 documents is the first at which those loops take a second iteration (tests/test_gpu_text_channel.py, "stride").
-// HBM-bound integer/byte work: bytes = 8 per posting read + 16 per score read-modify-write, + 8 N per selection pass.
-#include "bm25_kernels.h"
+// Launches per chunk: longest token list + 15 (merge, 12 histogram passes, gather, rank) and two memsets, whatever the
+// number of questions.  The plan of every chunk (jobs, question descriptors) is built on the host and uploaded ONCE per
+// call; the results of the whole call sit in one device buffer and come back after ONE stream synchronisation per call.
+// HBM-bound integer/byte work.  Bytes per question with q expanded queries over N documents: 8 N q (row memset) + 8 + 16
+// per posting (scatter) + 8 N q + 8 N (merge) + 8 N per histogram pass that still has a bucket to split + 8 N (gather).
+#include "common.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace mrag {
 
-// one token position of every query: jobs[y] = that query's posting range; x covers the longest range
+constexpr int64_t BM25_DEFAULT_SCRATCH = 1ll << 30;   // score rows of one chunk (mrag_bm25_batch.h: not a measured optimum)
+constexpr int BM25_MAX_K = 4096;
+constexpr int BM25_MAX_QUERIES = 1024;       // expanded queries of one question
+constexpr int BM25_PASSES = 12;              // 8 bytes of score bits + 4 bytes of ~doc
+constexpr int BM25_CHUNK_QUESTIONS = 1024;   // questions with a query per chunk: bounds the selection state (12 KiB + 16 k bytes each)
+constexpr unsigned BM25_GRID_YZ = 65535;     // HIP's limit of gridDim.y / gridDim.z
+
+struct Bm25Index : Object {
+  int64_t n_docs = 0, n_terms = 0, nnz = 0;
+  double k1p1 = 2.5;
+  int64_t* indptr = nullptr;     // [n_terms + 1]
+  int32_t* post_doc = nullptr;   // [nnz]
+  int32_t* post_tf = nullptr;    // [nnz]
+  double* doc_norm = nullptr;    // [n_docs]  k1 * (1 - b + b * dl / avgdl)
+  std::vector<int64_t> h_indptr; // host copy: posting counts size the launches
+  int64_t scratch_limit = BM25_DEFAULT_SCRATCH;
+  DevBuf scores, plan, hist, sel, out, allow;   // one call in flight per handle
+  ~Bm25Index() override {
+    for (void* p : {(void*)indptr, (void*)post_doc, (void*)post_tf, (void*)doc_norm}) if (p) (void)hipFree(p);
+    for (DevBuf* b : {&scores, &plan, &hist, &sel, &out, &allow}) b->release();
+  }
+};
+
+struct Bm25Job { int64_t lo, hi; double idf; int32_t query; int32_t pad; };   // one (score row, token position) posting range
+struct Bm25Group { int32_t row0, n_rows, question, pad; };   // one question of a chunk: its score rows, its index in the call
+
+// digit p (0 = most significant) of the 96-bit key (score bits : ~doc); positive doubles order like their bit patterns
+__device__ __forceinline__ uint32_t bm25_digit(uint64_t sb, uint32_t nd, int p) {
+  return p < 8 ? (uint32_t)(sb >> (56 - 8 * p)) & 255u : (nd >> (24 - 8 * (p - 8))) & 255u;
+}
+
+// Selection state, derived by every workgroup from the histograms of the passes already run:
+// prefix bytes pre[0..np), keys needed inside the prefix bucket, done = bucket wholly selected.
+struct Bm25Pick { uint32_t pre[BM25_PASSES]; int np; int64_t need; bool done; };
+
+__device__ __forceinline__ int bm25_cmp_prefix(uint64_t sb, uint32_t nd, const Bm25Pick& st) {
+  // -1 below, 0 inside, +1 above the prefix bucket
+  for (int p = 0; p < st.np; ++p) {
+    const uint32_t dg = bm25_digit(sb, nd, p);
+    if (dg != st.pre[p]) return dg > st.pre[p] ? 1 : -1;
+  }
+  return 0;
+}
+
+// one token position of a chunk: jobs[y] = a score row's posting range; x covers the longest range
 __global__ __launch_bounds__(256) void bm25_scatter_kernel(const Bm25Job* __restrict__ jobs, const int32_t* __restrict__ post_doc,
                                                            const int32_t* __restrict__ post_tf, const double* __restrict__ doc_norm,
                                                            double k1p1, int64_t n_docs, double* __restrict__ scores) {
 #pragma clang fp contract(off)
-  const Bm25Job j = jobs[blockIdx.y];
+  const Bm25Job j = jobs[blockIdx.y];           // .query = the job's score row inside the chunk
   const int64_t i = j.lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= j.hi) return;
   const int32_t d = post_doc[i];
@@ -37,32 +101,70 @@ __global__ __launch_bounds__(256) void bm25_scatter_kernel(const Bm25Job* __rest
   const double denom = f + doc_norm[d];
   const double num = j.idf * (f * k1p1);
   double* s = scores + (size_t)j.query * n_docs + d;
-  *s = *s + num / denom;      // docs are unique inside one posting list: no two lanes share a word
+  *s = *s + num / denom;      // one row per expanded query, docs unique inside a posting list: no two lanes share a word
 }
 
-// max / sum over the queries, in query order (text_index.py:90-91); s <= 0 or untouched -> 0 (not a candidate, :92)
-__global__ __launch_bounds__(256) void bm25_merge_kernel(const double* __restrict__ scores, int nq, int64_t n_docs, int merge_sum,
-                                                         double* __restrict__ fin) {
+// per question: max / sum over its rows in query order (text_index.py:90-91); s <= 0, untouched or not allowed -> 0
+// (not a candidate, :92).  The allow-set only removes candidates: every score is computed as without it (idf and avgdl
+// are the corpus's).
+__global__ __launch_bounds__(256) void bm25_merge_kernel(double* __restrict__ scores, const Bm25Group* __restrict__ groups,
+                                                         int64_t n_docs, int merge_sum, const uint32_t* __restrict__ allow) {
 #pragma clang fp contract(off)
   const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= n_docs) return;
-  double s = scores[d];
-  for (int q = 1; q < nq; ++q) {
-    const double v = scores[(size_t)q * n_docs + d];
+  const Bm25Group g = groups[blockIdx.y];
+  double* row = scores + (size_t)g.row0 * n_docs + d;
+  double s = row[0];
+  for (int q = 1; q < g.n_rows; ++q) {
+    const double v = row[(size_t)q * n_docs];
     s = merge_sum ? s + v : (v > s ? v : s);
   }
-  fin[d] = s > 0.0 ? s : 0.0;
+  s = s > 0.0 ? s : 0.0;
+  if (allow && !((allow[d >> 5] >> (d & 31)) & 1u)) s = 0.0;
+  row[0] = s;
 }
 
-// pass `pass`: histogram of digit `pass` over the keys inside the current prefix bucket
-__global__ __launch_bounds__(256) void bm25_hist_kernel(const double* __restrict__ fin, int64_t n_docs, int pass, int64_t k,
-                                                        unsigned* __restrict__ hist) {
-  __shared__ unsigned lh[256];
-  __shared__ Bm25Pick st;
-  if (threadIdx.x == 0) bm25_replay(hist, pass, k, st);
-  lh[threadIdx.x] = 0u;
+// The selection state after `passes` passes, by the whole workgroup (256 threads, one per bin): per pass a suffix sum over
+// the bins; the bucket is the highest bin whose suffix sum reaches `need`.  Ends on a barrier.
+__device__ inline void bm25_replay_block(const unsigned* __restrict__ hist, int passes, int64_t k, Bm25Pick& st, unsigned* suf) {
+  const int t = threadIdx.x;
+  if (t == 0) { st.np = 0; st.need = k; st.done = false; }
   __syncthreads();
+  for (int p = 0; p < passes; ++p) {
+    if (st.done) break;                       // uniform: st is only written between barriers
+    const unsigned h = hist[p * 256 + t];
+    suf[t] = h;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+      const unsigned v = t + off < 256 ? suf[t + off] : 0u;
+      __syncthreads();
+      suf[t] += v;
+      __syncthreads();
+    }
+    const int64_t need = st.need;
+    const int64_t at = suf[t], above = t < 255 ? suf[t + 1] : 0u, all = suf[0];    // keys in bins >= t, > t, in every bin
+    __syncthreads();
+    if (all < need) {
+      if (t == 0) { st.done = true; st.need = 0; }   // fewer than `need` keys exist: everything is selected
+    } else if (at >= need && above < need) {         // exactly one bin: the suffix sums fall with the bin
+      st.pre[st.np++] = (uint32_t)t;
+      st.need = need - above;
+      if ((int64_t)h == need - above) st.done = true;
+    }
+    __syncthreads();
+  }
+}
+
+// pass `pass` of every question of the chunk: histogram of digit `pass` over the keys inside the question's prefix bucket
+__global__ __launch_bounds__(256) void bm25_hist_kernel(const double* __restrict__ scores, const Bm25Group* __restrict__ groups,
+                                                        int64_t n_docs, int pass, int64_t k, unsigned* __restrict__ hist) {
+  __shared__ unsigned lh[256], suf[256];
+  __shared__ Bm25Pick st;
+  unsigned* gh = hist + (size_t)blockIdx.y * (BM25_PASSES * 256);
+  lh[threadIdx.x] = 0u;
+  bm25_replay_block(gh, pass, k, st, suf);    // ends on a barrier
   if (st.done) return;
+  const double* fin = scores + (size_t)groups[blockIdx.y].row0 * n_docs;
   for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t sb = (uint64_t)__double_as_longlong(fin[d]);
     if (sb == 0ull) continue;
@@ -70,45 +172,206 @@ __global__ __launch_bounds__(256) void bm25_hist_kernel(const double* __restrict
     if (bm25_cmp_prefix(sb, nd, st) == 0) atomicAdd(&lh[bm25_digit(sb, nd, pass)], 1u);
   }
   __syncthreads();
-  if (lh[threadIdx.x]) atomicAdd(&hist[pass * 256 + threadIdx.x], lh[threadIdx.x]);
+  if (lh[threadIdx.x]) atomicAdd(&gh[pass * 256 + threadIdx.x], lh[threadIdx.x]);
 }
 
-// gather the selected keys (above the bucket, or inside a wholly selected bucket), unordered
-__global__ __launch_bounds__(256) void bm25_gather_kernel(const double* __restrict__ fin, int64_t n_docs, int64_t k,
-                                                          const unsigned* __restrict__ hist, int* __restrict__ n_sel,
+// the selected keys of every question (above its bucket, or inside a wholly selected bucket), unordered, k slots per question
+__global__ __launch_bounds__(256) void bm25_gather_kernel(const double* __restrict__ scores, const Bm25Group* __restrict__ groups,
+                                                          int64_t n_docs, int k, const unsigned* __restrict__ hist,
+                                                          int* __restrict__ n_sel /*[question of the call]*/,
                                                           int64_t* __restrict__ sel_doc, double* __restrict__ sel_score) {
+  __shared__ unsigned suf[256];
   __shared__ Bm25Pick st;
-  if (threadIdx.x == 0) bm25_replay(hist, BM25_PASSES, k, st);
-  __syncthreads();
+  const Bm25Group g = groups[blockIdx.y];
+  bm25_replay_block(hist + (size_t)blockIdx.y * (BM25_PASSES * 256), BM25_PASSES, (int64_t)k, st, suf);
+  const double* fin = scores + (size_t)g.row0 * n_docs;
   for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += (int64_t)gridDim.x * blockDim.x) {
     const double s = fin[d];
     const uint64_t sb = (uint64_t)__double_as_longlong(s);
     if (sb == 0ull) continue;
-    const int c = bm25_cmp_prefix(sb, 0xFFFFFFFFu - (uint32_t)d, st);
-    if (c > 0 || c == 0) {     // after all 12 passes the bucket is one key; an early stop means the bucket is taken whole
-      const int slot = atomicAdd(n_sel, 1);
-      if (slot < BM25_MAX_K) { sel_doc[slot] = d; sel_score[slot] = s; }
+    if (bm25_cmp_prefix(sb, 0xFFFFFFFFu - (uint32_t)d, st) >= 0) {   // after all 12 passes the bucket is one key; an early stop takes it whole
+      const int slot = atomicAdd(&n_sel[g.question], 1);
+      if (slot < k) { sel_doc[(size_t)blockIdx.y * k + slot] = d; sel_score[(size_t)blockIdx.y * k + slot] = s; }
     }
   }
 }
 
-// one workgroup: order the <= k selected by (score desc, doc asc) with rank-by-counting
-__global__ __launch_bounds__(1024) void bm25_rank_kernel(const int* __restrict__ n_sel, const int64_t* __restrict__ sel_doc,
-                                                         const double* __restrict__ sel_score, int k, int64_t* __restrict__ out_doc,
-                                                         double* __restrict__ out_score) {
-  const int n = min(*n_sel, k);
+// one workgroup per question: order its <= k selected by (score desc, doc asc) into the call's result rows
+__global__ __launch_bounds__(1024) void bm25_rank_kernel(const Bm25Group* __restrict__ groups, const int* __restrict__ n_sel,
+                                                         const int64_t* __restrict__ sel_doc, const double* __restrict__ sel_score,
+                                                         int k, int64_t* __restrict__ out_doc, double* __restrict__ out_score) {
+  const int question = groups[blockIdx.x].question;
+  const int n = min(n_sel[question], k);
+  const int64_t* sd = sel_doc + (size_t)blockIdx.x * k;
+  const double* ss = sel_score + (size_t)blockIdx.x * k;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const double s = sel_score[i];
-    const int64_t d = sel_doc[i];
+    const double s = ss[i];
+    const int64_t d = sd[i];
     int rank = 0;
     for (int j = 0; j < n; ++j) {
-      const double sj = sel_score[j];
-      rank += (sj > s || (sj == s && sel_doc[j] < d)) ? 1 : 0;
+      const double sj = ss[j];
+      rank += (sj > s || (sj == s && sd[j] < d)) ? 1 : 0;
     }
-    out_doc[rank] = d;
-    out_score[rank] = s;
+    out_doc[(size_t)question * k + rank] = d;
+    out_score[(size_t)question * k + rank] = s;
   }
 }
+
+namespace {
+
+struct Bm25Chunk {
+  int rows = 0, n_groups = 0, max_len = 0;
+  size_t group0 = 0;      // first descriptor in the call's group list
+  size_t pos0 = 0;        // pos_first[pos0 .. pos0 + max_len] (job indexes in the call's job list), pos_longest[pos0 ..)
+};
+
+int grid_ok(const dim3& g) {
+  if (g.x == 0 || g.y == 0 || g.y > BM25_GRID_YZ || g.z > BM25_GRID_YZ)
+    return fail(MRAG_ERR_HIP, "BM25 launch grid (%u, %u, %u) outside HIP's limits", g.x, g.y, g.z);
+  return MRAG_OK;
+}
+
+// the token lists of queries [q_first, q_last): offsets from 0 upwards, term ids inside the vocabulary (< 0 = unknown term)
+int check_queries(const Bm25Index* ix, int q_first, int q_last, const int32_t* q_ptr, const int32_t* q_terms, const double* q_idf) {
+  if (q_first >= q_last) return MRAG_OK;
+  if (q_ptr[q_first] < 0) return fail(MRAG_ERR_INVALID, "q_ptr starts below 0");
+  for (int q = q_first; q < q_last; ++q)
+    if (q_ptr[q + 1] < q_ptr[q]) return fail(MRAG_ERR_INVALID, "q_ptr not monotone");
+  if (q_ptr[q_last] == q_ptr[q_first]) return MRAG_OK;
+  if (!q_terms || !q_idf) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  for (int at = q_ptr[q_first]; at < q_ptr[q_last]; ++at)
+    if (q_terms[at] >= ix->n_terms)
+      return fail(MRAG_ERR_INVALID, "term id %d outside the vocabulary (%lld)", q_terms[at], (long long)ix->n_terms);
+  return MRAG_OK;
+}
+
+// The search of n_questions >= 1 validated questions over a non-empty index, 1 <= k <= BM25_MAX_K: question g's answer in
+// slots [g * k, g * k + out_n[g]) of out_docs / out_scores, (-1, 0.0) in the rest of its k slots.  A question without
+// queries gets no launch and no output: its slots are the caller's to fill.
+int search_questions(Bm25Index* ix, int n_questions, const int32_t* g_ptr, const int32_t* q_ptr, const int32_t* q_terms,
+                     const double* q_idf, int merge_sum, int k, const uint32_t* allow_bits, int64_t* out_docs, double* out_scores,
+                     int32_t* out_n, hipStream_t stream) {
+  const int64_t N = ix->n_docs;
+  const size_t n_out = (size_t)n_questions * k;
+
+  // ---- the plan: chunks of whole questions, per chunk the jobs of every token position (unknown terms, id < 0, add nothing)
+  const int64_t rows_cap = std::min<int64_t>(std::max<int64_t>(ix->scratch_limit / (N * 8), 1), BM25_GRID_YZ);
+  std::vector<Bm25Chunk> chunks;
+  std::vector<Bm25Group> groups;
+  std::vector<Bm25Job> jobs;
+  std::vector<size_t> pos_first;
+  std::vector<int64_t> pos_longest;
+  int max_rows = 0, max_groups = 0;
+  for (int g = 0; g < n_questions;) {
+    Bm25Chunk c;
+    c.group0 = groups.size();
+    int q0 = -1;                                 // the chunk's first query: its rows are the queries q0 .. q0 + rows - 1
+    for (; g < n_questions; ++g) {
+      const int nq = g_ptr[g + 1] - g_ptr[g];
+      if (nq == 0) continue;
+      if (c.n_groups && (c.rows + nq > rows_cap || c.n_groups == BM25_CHUNK_QUESTIONS)) break;
+      if (q0 < 0) q0 = g_ptr[g];
+      groups.push_back(Bm25Group{c.rows, nq, g, 0});
+      c.rows += nq;
+      ++c.n_groups;
+    }
+    if (!c.n_groups) break;
+    for (int r = 0; r < c.rows; ++r) c.max_len = std::max(c.max_len, q_ptr[q0 + r + 1] - q_ptr[q0 + r]);
+    c.pos0 = pos_first.size();
+    for (int j = 0; j < c.max_len; ++j) {
+      pos_first.push_back(jobs.size());
+      int64_t longest = 0;
+      for (int r = 0; r < c.rows; ++r) {
+        const int at = q_ptr[q0 + r] + j;
+        if (at >= q_ptr[q0 + r + 1]) continue;
+        const int32_t t = q_terms[at];
+        if (t < 0) continue;
+        const int64_t lo = ix->h_indptr[t], hi = ix->h_indptr[t + 1];
+        if (hi == lo) continue;
+        jobs.push_back(Bm25Job{lo, hi, q_idf[at], r, 0});
+        longest = std::max(longest, hi - lo);
+      }
+      pos_longest.push_back(longest);
+    }
+    pos_first.push_back(jobs.size());
+    pos_longest.push_back(0);
+    max_rows = std::max(max_rows, c.rows);
+    max_groups = std::max(max_groups, c.n_groups);
+    chunks.push_back(c);
+  }
+  if (chunks.empty()) return MRAG_OK;            // no question has a query
+
+  MRAG_TRY(use_device(ix->device));
+  const size_t jobs_bytes = jobs.size() * sizeof(Bm25Job), groups_bytes = groups.size() * sizeof(Bm25Group);
+  const size_t hist_bytes = (size_t)BM25_PASSES * 256 * 4, words = (size_t)(N + 31) / 32;
+  // every buffer before the first launch: growing one frees it
+  MRAG_TRY(ix->scores.ensure((size_t)max_rows * N * 8));
+  MRAG_TRY(ix->plan.ensure(jobs_bytes + groups_bytes));
+  MRAG_TRY(ix->hist.ensure((size_t)max_groups * hist_bytes));
+  MRAG_TRY(ix->sel.ensure((size_t)max_groups * k * 16));
+  MRAG_TRY(ix->out.ensure(n_out * 16 + (size_t)n_questions * 4));
+  if (allow_bits) MRAG_TRY(ix->allow.ensure(words * 4));
+  const Bm25Job* d_jobs = (const Bm25Job*)ix->plan.p;
+  const Bm25Group* d_groups = (const Bm25Group*)((char*)ix->plan.p + jobs_bytes);
+  unsigned* d_hist = (unsigned*)ix->hist.p;
+  int64_t* d_sel_doc = (int64_t*)ix->sel.p;
+  double* d_sel_score = (double*)(d_sel_doc + (size_t)max_groups * k);
+  int64_t* d_out_doc = (int64_t*)ix->out.p;
+  double* d_out_score = (double*)(d_out_doc + n_out);
+  int* d_n_sel = (int*)(d_out_score + n_out);
+  double* d_scores = (double*)ix->scores.p;
+  const uint32_t* d_allow = allow_bits ? (const uint32_t*)ix->allow.p : nullptr;
+
+  auto enqueue = [&]() -> int {
+    if (jobs_bytes) MRAG_HIP(hipMemcpyAsync(ix->plan.p, jobs.data(), jobs_bytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync((char*)ix->plan.p + jobs_bytes, groups.data(), groups_bytes, hipMemcpyHostToDevice, stream));
+    if (allow_bits) MRAG_HIP(hipMemcpyAsync(ix->allow.p, allow_bits, words * 4, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemsetAsync(d_out_doc, 0xFF, n_out * 8, stream));                                   // (-1, 0.0) and out_n = 0
+    MRAG_HIP(hipMemsetAsync(d_out_score, 0, n_out * 8 + (size_t)n_questions * 4, stream));
+    const unsigned dgrid = (unsigned)((N + 255) / 256), sgrid = std::min<unsigned>(dgrid, 1024);
+    for (const Bm25Chunk& c : chunks) {
+      const Bm25Group* cg = d_groups + c.group0;
+      MRAG_HIP(hipMemsetAsync(d_scores, 0, (size_t)c.rows * N * 8, stream));
+      MRAG_HIP(hipMemsetAsync(d_hist, 0, (size_t)c.n_groups * hist_bytes, stream));
+      for (int j = 0; j < c.max_len; ++j) {
+        const size_t first = pos_first[c.pos0 + j], nj = pos_first[c.pos0 + j + 1] - first;
+        if (!nj) continue;
+        const dim3 grid((unsigned)((pos_longest[c.pos0 + j] + 255) / 256), (unsigned)nj);
+        MRAG_TRY(grid_ok(grid));
+        hipLaunchKernelGGL(bm25_scatter_kernel, grid, dim3(256), 0, stream, d_jobs + first, ix->post_doc, ix->post_tf,
+                           ix->doc_norm, ix->k1p1, N, d_scores);
+      }
+      const dim3 mgrid(dgrid, (unsigned)c.n_groups), hgrid(sgrid, (unsigned)c.n_groups), rgrid((unsigned)c.n_groups);
+      MRAG_TRY(grid_ok(mgrid));
+      MRAG_TRY(grid_ok(hgrid));
+      hipLaunchKernelGGL(bm25_merge_kernel, mgrid, dim3(256), 0, stream, d_scores, cg, N, merge_sum ? 1 : 0, d_allow);
+      for (int p = 0; p < BM25_PASSES; ++p)
+        hipLaunchKernelGGL(bm25_hist_kernel, hgrid, dim3(256), 0, stream, (const double*)d_scores, cg, N, p, (int64_t)k, d_hist);
+      hipLaunchKernelGGL(bm25_gather_kernel, hgrid, dim3(256), 0, stream, (const double*)d_scores, cg, N, k,
+                         (const unsigned*)d_hist, d_n_sel, d_sel_doc, d_sel_score);
+      hipLaunchKernelGGL(bm25_rank_kernel, rgrid, dim3(1024), 0, stream, cg, (const int*)d_n_sel, (const int64_t*)d_sel_doc,
+                         (const double*)d_sel_score, k, d_out_doc, d_out_score);
+      MRAG_HIP(hipGetLastError());
+    }
+    MRAG_HIP(hipMemcpyAsync(out_n, d_n_sel, (size_t)n_questions * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_docs, d_out_doc, n_out * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_out_score, n_out * 8, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  };
+  const int st = enqueue();
+  const hipError_t e = hipStreamSynchronize(stream);   // the plan and the caller's buffers are in use until here, also after a failure
+  if (st != MRAG_OK) { std::fill(out_n, out_n + n_questions, 0); return st; }
+  MRAG_HIP(e);
+  for (int g = 0; g < n_questions; ++g)
+    if (out_n[g] > k) {
+      const int n = out_n[g];
+      std::fill(out_n, out_n + n_questions, 0);
+      return fail(MRAG_ERR_HIP, "BM25 selection produced %d > k = %d entries for question %d", n, k, g);
+    }
+  return MRAG_OK;
+}
+
+}  // namespace
 
 }  // namespace mrag
 
@@ -155,8 +418,17 @@ int mrag_bm25_destroy(mrag_handle h) {
   return MRAG_OK;
 }
 
+int mrag_bm25_set_scratch_limit(mrag_handle h, int64_t bytes) {
+  Bm25Index* ix = (Bm25Index*)lookup(h, KIND_BM25);
+  if (!ix) return MRAG_ERR_INVALID;
+  ix->scratch_limit = bytes > 0 ? bytes : BM25_DEFAULT_SCRATCH;
+  return MRAG_OK;
+}
+
+// One question: its n_queries expanded queries are the question's score rows, so the scratch limit never splits it.
+// The k slots of out_docs / out_scores are the capacity mrag.h asks for; those past *out_n hold (-1, 0.0).
 int mrag_bm25_search(mrag_handle h, int n_queries, const int32_t* q_ptr, const int32_t* q_terms, const double* q_idf,
-                     int merge_sum, int k, int64_t* out_docs, double* out_scores, int* out_n, void* stream_) {
+                     int merge_sum, int k, int64_t* out_docs, double* out_scores, int* out_n, void* stream) {
   Bm25Index* ix = (Bm25Index*)lookup(h, KIND_BM25);
   if (!ix) return MRAG_ERR_INVALID;
   if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
@@ -165,228 +437,38 @@ int mrag_bm25_search(mrag_handle h, int n_queries, const int32_t* q_ptr, const i
   if (k > BM25_MAX_K) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds %d", k, BM25_MAX_K);
   if (n_queries == 0 || k == 0 || ix->n_docs == 0) return MRAG_OK;
   if (!q_ptr || !out_docs || !out_scores) return fail(MRAG_ERR_INVALID, "NULL buffer");
-  if (n_queries > 1024) return fail(MRAG_ERR_UNSUPPORTED, "more than 1024 queries per call");
-  MRAG_TRY(use_device(ix->device));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int64_t N = ix->n_docs;
-  // jobs per token position: the j-th token of every query that has one (unknown terms, id < 0, add nothing)
-  int max_len = 0;
-  for (int q = 0; q < n_queries; ++q) {
-    if (q_ptr[q + 1] < q_ptr[q]) return fail(MRAG_ERR_INVALID, "q_ptr not monotone");
-    max_len = std::max(max_len, q_ptr[q + 1] - q_ptr[q]);
+  if (n_queries > BM25_MAX_QUERIES) return fail(MRAG_ERR_UNSUPPORTED, "more than %d queries per call", BM25_MAX_QUERIES);
+  MRAG_TRY(check_queries(ix, 0, n_queries, q_ptr, q_terms, q_idf));
+  const int32_t g_ptr[2] = {0, n_queries};
+  return search_questions(ix, 1, g_ptr, q_ptr, q_terms, q_idf, merge_sum, k, nullptr, out_docs, out_scores, out_n, (hipStream_t)stream);
+}
+
+int mrag_bm25_search_batch(mrag_handle h, int n_questions, const int32_t* g_ptr, const int32_t* q_ptr, const int32_t* q_terms,
+                           const double* q_idf, int merge_sum, int k, const uint32_t* allow_bits, int64_t* out_docs,
+                           double* out_scores, int32_t* out_n, void* stream) {
+  Bm25Index* ix = (Bm25Index*)lookup(h, KIND_BM25);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (n_questions < 0 || k < 0) return fail(MRAG_ERR_INVALID, "bad n_questions / k");
+  if (n_questions == 0) return MRAG_OK;
+  if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
+  std::fill(out_n, out_n + n_questions, 0);
+  if (k > BM25_MAX_K) return fail(MRAG_ERR_UNSUPPORTED, "k = %d exceeds %d", k, BM25_MAX_K);
+  if (k == 0) return MRAG_OK;
+  if (!g_ptr || !q_ptr || !out_docs || !out_scores) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t n_out = (size_t)n_questions * k;
+  std::fill(out_docs, out_docs + n_out, (int64_t)-1);     // what a question without queries, or every question of an empty index, keeps
+  std::fill(out_scores, out_scores + n_out, 0.0);
+  if (ix->n_docs == 0) return MRAG_OK;
+  // the whole batch is validated before anything is launched
+  if (g_ptr[0] < 0) return fail(MRAG_ERR_INVALID, "g_ptr starts below 0");
+  for (int g = 0; g < n_questions; ++g) {
+    if (g_ptr[g + 1] < g_ptr[g]) return fail(MRAG_ERR_INVALID, "g_ptr not monotone at question %d", g);
+    if (g_ptr[g + 1] - g_ptr[g] > BM25_MAX_QUERIES)
+      return fail(MRAG_ERR_UNSUPPORTED, "question %d has more than %d queries", g, BM25_MAX_QUERIES);
   }
-  std::vector<Bm25Job> jobs;
-  std::vector<int> pos_first(max_len + 1, 0);
-  std::vector<int64_t> pos_longest(max_len, 0);
-  for (int j = 0; j < max_len; ++j) {
-    pos_first[j] = (int)jobs.size();
-    for (int q = 0; q < n_queries; ++q) {
-      const int at = q_ptr[q] + j;
-      if (at >= q_ptr[q + 1]) continue;
-      const int32_t t = q_terms[at];
-      if (t < 0) continue;
-      if (t >= ix->n_terms) return fail(MRAG_ERR_INVALID, "term id %d outside the vocabulary (%lld)", t, (long long)ix->n_terms);
-      const int64_t lo = ix->h_indptr[t], hi = ix->h_indptr[t + 1];
-      if (hi == lo) continue;
-      jobs.push_back(Bm25Job{lo, hi, q_idf[at], q, 0});
-      pos_longest[j] = std::max(pos_longest[j], hi - lo);
-    }
-  }
-  pos_first[max_len] = (int)jobs.size();
-  MRAG_TRY(ix->scores.ensure((size_t)n_queries * N * 8));
-  MRAG_TRY(ix->fin.ensure((size_t)N * 8));
-  MRAG_TRY(ix->hist.ensure(BM25_PASSES * 256 * 4 + 16));
-  MRAG_TRY(ix->sel.ensure((size_t)BM25_MAX_K * 16 * 2));
-  MRAG_TRY(ix->qbuf.ensure(std::max<size_t>(jobs.size(), 1) * sizeof(Bm25Job)));
-  MRAG_HIP(hipMemsetAsync(ix->scores.p, 0, (size_t)n_queries * N * 8, stream));
-  MRAG_HIP(hipMemsetAsync(ix->hist.p, 0, BM25_PASSES * 256 * 4 + 16, stream));
-  if (!jobs.empty()) MRAG_HIP(hipMemcpyAsync(ix->qbuf.p, jobs.data(), jobs.size() * sizeof(Bm25Job), hipMemcpyHostToDevice, stream));
-  for (int j = 0; j < max_len; ++j) {
-    const int nj = pos_first[j + 1] - pos_first[j];
-    if (!nj) continue;
-    const dim3 grid((unsigned)((pos_longest[j] + 255) / 256), (unsigned)nj);
-    hipLaunchKernelGGL(bm25_scatter_kernel, grid, dim3(256), 0, stream, (const Bm25Job*)ix->qbuf.p + pos_first[j], ix->post_doc,
-                       ix->post_tf, ix->doc_norm, ix->k1p1, N, (double*)ix->scores.p);
-  }
-  MRAG_HIP(hipGetLastError());
-  const unsigned dgrid = (unsigned)((N + 255) / 256);
-  hipLaunchKernelGGL(bm25_merge_kernel, dim3(dgrid), dim3(256), 0, stream, (const double*)ix->scores.p, n_queries, N, merge_sum ? 1 : 0,
-                     (double*)ix->fin.p);
-  unsigned* hist = (unsigned*)ix->hist.p;
-  int* n_sel = (int*)(hist + BM25_PASSES * 256);
-  const unsigned sgrid = std::min<unsigned>(dgrid, 1024);
-  for (int p = 0; p < BM25_PASSES; ++p)
-    hipLaunchKernelGGL(bm25_hist_kernel, dim3(sgrid), dim3(256), 0, stream, (const double*)ix->fin.p, N, p, (int64_t)k, hist);
-  int64_t* sel_doc = (int64_t*)ix->sel.p;
-  double* sel_score = (double*)(sel_doc + BM25_MAX_K);
-  int64_t* out_doc_d = (int64_t*)(sel_score + BM25_MAX_K);
-  double* out_score_d = (double*)(out_doc_d + BM25_MAX_K);
-  hipLaunchKernelGGL(bm25_gather_kernel, dim3(sgrid), dim3(256), 0, stream, (const double*)ix->fin.p, N, (int64_t)k, (const unsigned*)hist,
-                     n_sel, sel_doc, sel_score);
-  hipLaunchKernelGGL(bm25_rank_kernel, dim3(1), dim3(1024), 0, stream, (const int*)n_sel, (const int64_t*)sel_doc,
-                     (const double*)sel_score, k, out_doc_d, out_score_d);
-  MRAG_HIP(hipGetLastError());
-  int n = 0;
-  MRAG_HIP(hipMemcpyAsync(&n, n_sel, 4, hipMemcpyDeviceToHost, stream));
-  MRAG_HIP(hipStreamSynchronize(stream));
-  if (n > k) return fail(MRAG_ERR_HIP, "BM25 selection produced %d > k = %d entries", n, k);
-  if (n) {
-    MRAG_HIP(hipMemcpyAsync(out_docs, out_doc_d, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipMemcpyAsync(out_scores, out_score_d, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
-    MRAG_HIP(hipStreamSynchronize(stream));
-  }
-  *out_n = n;
-  return MRAG_OK;
+  MRAG_TRY(check_queries(ix, g_ptr[0], g_ptr[n_questions], q_ptr, q_terms, q_idf));
+  return search_questions(ix, n_questions, g_ptr, q_ptr, q_terms, q_idf, merge_sum, k, allow_bits, out_docs, out_scores, out_n,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// a7 on the device: the fusion arithmetic of HybridRetrievalBackend.run (retrieval_backend.py:336-372) over the
-// three channels' (key, score) lists -- key = the rank of the hit's NORMALISED id among all ids of the call
-// (assigned by the host binding, so ascending key == ascending id, the declared tie order):
-//   per channel  dedupe by key, strictly larger score wins (:336-348)
-//                min-max over the kept scores, all-equal / empty -> 0.0 (:296-301)
-//   union        score = a_t*ts + a_g*gs + a_d*ds, left to right, no contraction (:363)
-//   sort (score desc, key asc), keep top_k (:371-372)
-// One workgroup; the lists are a few hundred entries (pools of 200).  fp64, bit for bit the reference's values.
-// ------------------------------------------------------------------------------------------
-namespace mrag {
-
-constexpr int FUSE_MAX = 4096;   // entries over the three channels
-
-__global__ __launch_bounds__(1024) void fuse_topk_kernel(const int32_t* __restrict__ key, const double* __restrict__ score,
-                                                         const int* __restrict__ chan_ptr /*[4]*/, double a_t, double a_g, double a_d,
-                                                         int top_k, int32_t* __restrict__ out_key, double* __restrict__ out /*[4][top_k]*/,
-                                                         int* __restrict__ out_n, double* __restrict__ work /*[4][n]: norm | fused | kept flag | carrier flag*/) {
-#pragma clang fp contract(off)
-  __shared__ double s_lo[3], s_hi[3];
-  __shared__ int s_any[3], s_cnt;
-  const int tid = threadIdx.x, n = chan_ptr[3];
-  double* norm = work;
-  double* fused = work + n;
-  double* keep = work + 2 * n;     // 1.0 = this entry represents its key in its channel
-  double* carrier = work + 3 * n;  // 1.0 = first kept entry of its key over all channels: carries the fused score
-  if (tid < 3) { s_any[tid] = 0; }
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  // 1) dedupe inside each channel: an entry is kept unless another entry of the same channel and key has a
-  //    strictly larger score, or the same score and a smaller index (the first one met keeps the slot)
-  for (int i = tid; i < n; i += blockDim.x) {
-    const int c = i >= chan_ptr[2] ? 2 : (i >= chan_ptr[1] ? 1 : 0);
-    bool k = true;
-    for (int j = chan_ptr[c]; j < chan_ptr[c + 1]; ++j)
-      if (j != i && key[j] == key[i] && (score[j] > score[i] || (score[j] == score[i] && j < i))) { k = false; break; }
-    keep[i] = k ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  // 2) per-channel min / max over the kept entries (one thread per channel: the lists are short)
-  if (tid < 3) {
-    double lo = 0.0, hi = 0.0;
-    bool any = false;
-    for (int j = chan_ptr[tid]; j < chan_ptr[tid + 1]; ++j) {
-      if (keep[j] == 0.0) continue;
-      const double v = score[j];
-      if (!any) { lo = hi = v; any = true; }
-      else { lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
-    }
-    s_lo[tid] = lo; s_hi[tid] = hi; s_any[tid] = any ? 1 : 0;
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += blockDim.x) {
-    const int c = i >= chan_ptr[2] ? 2 : (i >= chan_ptr[1] ? 1 : 0);
-    const double lo = s_lo[c], hi = s_hi[c];
-    norm[i] = (keep[i] != 0.0 && hi > lo) ? (score[i] - lo) / (hi - lo) : 0.0;
-  }
-  __syncthreads();
-  // 3) union: the FIRST kept entry of a key (lowest index over all channels) carries the fused score
-  for (int i = tid; i < n; i += blockDim.x) {
-    fused[i] = 0.0;
-    carrier[i] = 0.0;
-    if (keep[i] == 0.0) continue;
-    double ch[3] = {0.0, 0.0, 0.0};
-    bool first = true;
-    for (int j = 0; j < n; ++j) {
-      if (keep[j] == 0.0 || key[j] != key[i]) continue;
-      if (j < i) { first = false; break; }
-      ch[j >= chan_ptr[2] ? 2 : (j >= chan_ptr[1] ? 1 : 0)] = norm[j];
-    }
-    if (!first) continue;
-    fused[i] = a_t * ch[0] + a_g * ch[1] + a_d * ch[2];
-    carrier[i] = 1.0;
-  }
-  __syncthreads();
-  // 4) rank the carriers by (fused desc, key asc) and write the top_k
-  for (int i = tid; i < n; i += blockDim.x) {
-    if (carrier[i] == 0.0) continue;
-    int rank = 0;
-    for (int j = 0; j < n; ++j)
-      if (carrier[j] != 0.0 && (fused[j] > fused[i] || (fused[j] == fused[i] && key[j] < key[i]))) ++rank;
-    atomicAdd(&s_cnt, 1);
-    if (rank < top_k) {
-      double ch[3] = {0.0, 0.0, 0.0};
-      for (int j = i; j < n; ++j)
-        if (keep[j] != 0.0 && key[j] == key[i]) ch[j >= chan_ptr[2] ? 2 : (j >= chan_ptr[1] ? 1 : 0)] = norm[j];
-      out_key[rank] = key[i];
-      out[rank] = fused[i];
-      out[top_k + rank] = ch[0];
-      out[2 * top_k + rank] = ch[1];
-      out[3 * top_k + rank] = ch[2];
-    }
-  }
-  __syncthreads();
-  if (tid == 0) *out_n = min(s_cnt, top_k);
-}
-
-}  // namespace mrag
-
-extern "C" int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_text, int n_graph, int n_dense,
-                              double alpha_text, double alpha_graph, double alpha_dense, int top_k, int32_t* out_keys,
-                              double* out_scores, double* out_text_norm, double* out_graph_norm, double* out_dense_norm,
-                              int* out_n, void* stream_) {
-  using namespace mrag;
-  if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
-  *out_n = 0;
-  if (n_text < 0 || n_graph < 0 || n_dense < 0 || top_k < 0) return fail(MRAG_ERR_INVALID, "negative size");
-  const int n = n_text + n_graph + n_dense;
-  if (n > FUSE_MAX) return fail(MRAG_ERR_UNSUPPORTED, "%d fusion entries exceed %d", n, FUSE_MAX);
-  if (n == 0 || top_k == 0) return MRAG_OK;
-  if (!keys || !scores || !out_keys || !out_scores || !out_text_norm || !out_graph_norm || !out_dense_norm)
-    return fail(MRAG_ERR_INVALID, "NULL buffer");
-  for (int i = 0; i < n; ++i)
-    if (!(scores[i] == scores[i])) return fail(MRAG_ERR_INVALID, "NaN score at fusion entry %d", i);
-  MRAG_TRY(use_device(device));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int kk = std::min(top_k, n);
-  // one scratch block: keys | scores | chan_ptr | work[4n] | out_key[kk] | out[4kk] | out_n
-  const size_t o_scores = round_up((int64_t)n * 4, 16), o_ptr = o_scores + (size_t)n * 8, o_work = o_ptr + 16,
-               o_okey = o_work + (size_t)4 * n * 8, o_out = o_okey + round_up((int64_t)kk * 4, 16), o_n = o_out + (size_t)4 * kk * 8,
-               total = o_n + 16;
-  char* d = nullptr;
-  MRAG_HIP(hipMalloc((void**)&d, total));
-  const int ptr[4] = {0, n_text, n_text + n_graph, n};
-  hipError_t e = hipMemcpyAsync(d, keys, (size_t)n * 4, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_scores, scores, (size_t)n * 8, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + o_ptr, ptr, 16, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(fuse_topk_kernel, dim3(1), dim3(1024), 0, stream, (const int32_t*)d, (const double*)(d + o_scores),
-                       (const int*)(d + o_ptr), alpha_text, alpha_graph, alpha_dense, kk, (int32_t*)(d + o_okey), (double*)(d + o_out),
-                       (int*)(d + o_n), (double*)(d + o_work));
-    e = hipGetLastError();
-  }
-  int n_out = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&n_out, d + o_n, 4, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess && n_out > 0) {
-    e = hipMemcpy(out_keys, d + o_okey, (size_t)n_out * 4, hipMemcpyDeviceToHost);
-    double* o = (double*)(d + o_out);
-    if (e == hipSuccess) e = hipMemcpy(out_scores, o, (size_t)n_out * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_text_norm, o + kk, (size_t)n_out * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_graph_norm, o + 2 * kk, (size_t)n_out * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_dense_norm, o + 3 * kk, (size_t)n_out * 8, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "fuse_topk failed: %s", hipGetErrorString(e));
-  *out_n = n_out;
-  return MRAG_OK;
-}

@@ -1,6 +1,12 @@
-// Batched channel fusion: the arithmetic of HybridRetrievalBackend.run (retrieval_backend.py:336-372) as fuse_topk_kernel
-// (bm25.hip) states it, for MANY questions per call.  Every question's answer is what mrag_fuse_topk returns for that
-// question alone -- same keys, same fp64 bits, same order -- wherever the question stands in the batch.
+// Channel fusion on the device (a7): the arithmetic of HybridRetrievalBackend.run (retrieval_backend.py:336-372) over the
+// three channels' (key, score) lists, for MANY questions per call -- key = the rank of the hit's NORMALISED id among the
+// ids the host binding ranks, so ascending key == ascending id, the declared tie order:
+//   per channel  dedupe by key, strictly larger score wins, the first one met among equals (:336-348)
+//                min-max over the kept scores, all-equal / empty -> 0.0 (:296-301)
+//   union        score = a_t*ts + a_g*gs + a_d*ds, left to right, no contraction (:363)
+//   sort (score desc, key asc), keep top_k (:371-372)
+// fp64, bit for bit the reference's values, wherever a question stands in the batch.  There is one fusion path:
+// mrag_fuse_topk_batch runs it for its questions, mrag_fuse_topk is a batch of one question without payloads.
 //
 //   grid       one workgroup per question; blockDim = half the largest question's padded size, 64 .. 1024 threads
 //   LDS        dynamic, sized by the largest question of the launch; a question of n entries works on P = the power of two
@@ -29,27 +35,26 @@
 //   output     the first min(top_k, U) of sort 2; the slots up to out_stride hold (-1, 0.0)
 // Work per question: O(P log^2 P) compare-exchanges in LDS; global memory is read once and written once.
 #include "common.h"
-#include "../../include/mrag_fuse_batch.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace mrag {
 
-constexpr int FUSEB_MAX = 4096;              // entries of one question over its three channels: mrag_fuse_topk's limit
-constexpr int FUSEB_HEAD = 64;               // bytes
-constexpr unsigned short FUSEB_NONE = 0xFFFF;
+constexpr int FUSE_MAX = 4096;               // entries of one question over its three channels
+constexpr int FUSE_HEAD = 64;                // bytes
+constexpr unsigned short FUSE_NONE = 0xFFFF;
 
-__host__ __device__ inline int fuseb_pow2(int n) {
+__host__ __device__ inline int fuse_pow2(int n) {
   int p = 2;
   while (p < n) p <<= 1;
   return p;
 }
-static inline size_t fuseb_lds_bytes(int P, int T) { return (size_t)FUSEB_HEAD + (size_t)34 * P + (size_t)4 * T; }
+static inline size_t fuse_lds_bytes(int P, int T) { return (size_t)FUSE_HEAD + (size_t)34 * P + (size_t)4 * T; }
 
 // bitonic sort of perm[0 .. P) (P a power of two, distinct elements) under a strict total order; ends on a barrier
 template <class Less>
-__device__ inline void fuseb_sort(unsigned short* perm, int P, Less less) {
+__device__ inline void fuse_sort(unsigned short* perm, int P, Less less) {
   for (int k = 2; k <= P; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
@@ -61,22 +66,22 @@ __device__ inline void fuseb_sort(unsigned short* perm, int P, Less less) {
     }
 }
 
-__global__ __launch_bounds__(1024) void fuse_batch_kernel(const int32_t* __restrict__ chan_ptr, const int32_t* __restrict__ keys,
-                                                          const double* __restrict__ scores, const int32_t* __restrict__ payload,
-                                                          const int32_t* __restrict__ top_k, double a_t, double a_g, double a_d,
-                                                          int out_stride, int32_t* __restrict__ out_key, double* __restrict__ out_fused,
-                                                          double* __restrict__ out_nt, double* __restrict__ out_ng,
-                                                          double* __restrict__ out_nd, int32_t* __restrict__ out_payload,
-                                                          int32_t* __restrict__ out_n) {
+__global__ __launch_bounds__(1024) void fuse_kernel(const int32_t* __restrict__ chan_ptr, const int32_t* __restrict__ keys,
+                                                    const double* __restrict__ scores, const int32_t* __restrict__ payload,
+                                                    const int32_t* __restrict__ top_k, double a_t, double a_g, double a_d,
+                                                    int out_stride, int32_t* __restrict__ out_key, double* __restrict__ out_fused,
+                                                    double* __restrict__ out_nt, double* __restrict__ out_ng,
+                                                    double* __restrict__ out_nd, int32_t* __restrict__ out_payload,
+                                                    int32_t* __restrict__ out_n) {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char fuseb_lds[];
+  extern __shared__ __attribute__((aligned(16))) char fuse_lds[];
   const int g = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   const int base = chan_ptr[3 * (size_t)g];
   const int c1 = chan_ptr[3 * (size_t)g + 1] - base, c2 = chan_ptr[3 * (size_t)g + 2] - base, n = chan_ptr[3 * (size_t)g + 3] - base;
-  const int P = fuseb_pow2(n);
-  double* s_lo = (double*)fuseb_lds;
+  const int P = fuse_pow2(n);
+  double* s_lo = (double*)fuse_lds;
   double* s_hi = s_lo + 3;
-  double* s_score = (double*)(fuseb_lds + FUSEB_HEAD);
+  double* s_score = (double*)(fuse_lds + FUSE_HEAD);
   double* s_fused = s_score + P;
   int32_t* s_key = (int32_t*)(s_fused + P);
   int32_t* s_pay = s_key + P;
@@ -96,12 +101,12 @@ __global__ __launch_bounds__(1024) void fuse_batch_kernel(const int32_t* __restr
     perm[i] = (unsigned short)i;
     kept[i] = 0;
     flag[i] = 0;
-    ent[i] = ent[P + i] = ent[2 * P + i] = FUSEB_NONE;
+    ent[i] = ent[P + i] = ent[2 * P + i] = FUSE_NONE;
   }
   __syncthreads();
 
   // 1) sort 1: real entries before the padding (index >= n), then (key, channel, score desc, index)
-  fuseb_sort(perm, P, [=](int a, int b) {
+  fuse_sort(perm, P, [=](int a, int b) {
     if (b >= n) return a < n || a < b;
     if (a >= n) return false;
     const int ka = s_key[a], kb = s_key[b];
@@ -193,14 +198,14 @@ __global__ __launch_bounds__(1024) void fuse_batch_kernel(const int32_t* __restr
   for (int u = tid; u < P; u += T) {
     if (u < U) {
       const unsigned short e0 = ent[u], e1 = ent[P + u], e2 = ent[2 * P + u];
-      const double ts = e0 != FUSEB_NONE ? s_score[e0] : 0.0, gs = e1 != FUSEB_NONE ? s_score[e1] : 0.0,
-                   ds = e2 != FUSEB_NONE ? s_score[e2] : 0.0;
+      const double ts = e0 != FUSE_NONE ? s_score[e0] : 0.0, gs = e1 != FUSE_NONE ? s_score[e1] : 0.0,
+                   ds = e2 != FUSE_NONE ? s_score[e2] : 0.0;
       s_fused[u] = a_t * ts + a_g * gs + a_d * ds;
     }
     perm[u] = (unsigned short)u;
   }
   __syncthreads();
-  fuseb_sort(perm, fuseb_pow2(U), [=](int a, int b) {
+  fuse_sort(perm, fuse_pow2(U), [=](int a, int b) {
     if (b >= U) return a < U || a < b;
     if (a >= U) return false;
     const double fa = s_fused[a], fb = s_fused[b];
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(1024) void fuse_batch_kernel(const int32_t* __restr
       f = s_fused[u];
       for (int c = 2; c >= 0; --c) {
         const unsigned short e = ent[c * P + u];
-        if (e == FUSEB_NONE) continue;
+        if (e == FUSE_NONE) continue;
         key = s_key[e];
         nm[c] = s_score[e];
         pay[c] = s_pay[e];
@@ -236,52 +241,18 @@ __global__ __launch_bounds__(1024) void fuse_batch_kernel(const int32_t* __restr
   if (tid == 0) out_n[g] = kk;
 }
 
-}  // namespace mrag
+namespace {
 
-using namespace mrag;
-
-extern "C" int mrag_fuse_topk_batch(int device, int n_questions, const int32_t* chan_ptr, const int32_t* keys, const double* scores,
-                                    const int32_t* payload, double alpha_text, double alpha_graph, double alpha_dense,
-                                    const int32_t* top_k, int out_stride, int32_t* out_keys, double* out_scores,
-                                    double* out_text_norm, double* out_graph_norm, double* out_dense_norm, int32_t* out_payload,
-                                    int32_t* out_n, void* stream_) {
-  if (n_questions < 0 || out_stride < 0) return fail(MRAG_ERR_INVALID, "negative n_questions / out_stride");
-  if (n_questions == 0) return MRAG_OK;
-  if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
-  std::fill(out_n, out_n + n_questions, 0);
-  if (!chan_ptr || !top_k) return fail(MRAG_ERR_INVALID, "NULL chan_ptr / top_k");
-  const size_t n_out = (size_t)n_questions * out_stride;
-  if (n_out && (!out_keys || !out_scores || !out_text_norm || !out_graph_norm || !out_dense_norm || (payload && !out_payload)))
-    return fail(MRAG_ERR_INVALID, "NULL output buffer");
-
-  // ---- the whole batch is validated before any device work
-  if (chan_ptr[0] != 0) return fail(MRAG_ERR_INVALID, "chan_ptr must start at 0");
+// The fusion of n_questions >= 1 validated questions that hold at least one entry, out_stride >= 1: question g's
+// out_stride slots of every output and its out_n[g].
+int fuse_questions(int device, int n_questions, const int32_t* chan_ptr, const int32_t* keys, const double* scores,
+                   const int32_t* payload, double alpha_text, double alpha_graph, double alpha_dense, const int32_t* top_k,
+                   int out_stride, int32_t* out_keys, double* out_scores, double* out_text_norm, double* out_graph_norm,
+                   double* out_dense_norm, int32_t* out_payload, int32_t* out_n, hipStream_t stream) {
+  const size_t n_out = (size_t)n_questions * out_stride, E = (size_t)chan_ptr[3 * (size_t)n_questions];
   int n_max = 0;
-  for (int g = 0; g < n_questions; ++g) {
-    const int32_t* p = chan_ptr + 3 * (size_t)g;
-    if (p[1] < p[0] || p[2] < p[1] || p[3] < p[2]) return fail(MRAG_ERR_INVALID, "chan_ptr decreases inside question %d", g);
-    if ((int64_t)p[3] - p[0] > FUSEB_MAX)
-      return fail(MRAG_ERR_UNSUPPORTED, "question %d has %lld fusion entries, more than %d", g, (long long)p[3] - p[0], FUSEB_MAX);
-    if (top_k[g] < 0 || top_k[g] > out_stride)
-      return fail(MRAG_ERR_INVALID, "top_k = %d of question %d outside [0, out_stride = %d]", top_k[g], g, out_stride);
-    n_max = std::max(n_max, p[3] - p[0]);
-  }
-  const size_t E = (size_t)chan_ptr[3 * (size_t)n_questions];
-  if (E && (!keys || !scores)) return fail(MRAG_ERR_INVALID, "NULL keys / scores");
-  for (int g = 0; g < n_questions; ++g)
-    for (int i = chan_ptr[3 * (size_t)g]; i < chan_ptr[3 * (size_t)g + 3]; ++i)
-      if (!(scores[i] == scores[i]))
-        return fail(MRAG_ERR_INVALID, "NaN score at fusion entry %d of question %d", i - chan_ptr[3 * (size_t)g], g);
-
-  auto fill_empty = [&]() {
-    std::fill(out_keys, out_keys + n_out, (int32_t)-1);
-    for (double* o : {out_scores, out_text_norm, out_graph_norm, out_dense_norm}) std::fill(o, o + n_out, 0.0);
-    if (payload) std::fill(out_payload, out_payload + 3 * n_out, (int32_t)-1);
-  };
-  if (n_out == 0) return MRAG_OK;                        // every top_k is 0
-  if (E == 0) { fill_empty(); return MRAG_OK; }          // only empty questions
-
-  // ---- one block of device memory: inputs | outputs, the 8-byte items first in each part
+  for (int g = 0; g < n_questions; ++g) n_max = std::max(n_max, chan_ptr[3 * (size_t)g + 3] - chan_ptr[3 * (size_t)g]);
+  // one block of device memory: inputs | outputs, the 8-byte items first in each part
   auto r8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
   const size_t n_ptr = 3 * (size_t)n_questions + 1;
   const size_t i_scores = 0, i_ptr = i_scores + E * 8, i_topk = i_ptr + r8(n_ptr * 4), i_keys = i_topk + r8((size_t)n_questions * 4),
@@ -296,18 +267,17 @@ extern "C" int mrag_fuse_topk_batch(int device, int n_questions, const int32_t* 
   if (payload) memcpy(h_in.data() + i_pay, payload, E * 4);
 
   MRAG_TRY(use_device(device));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int P = fuseb_pow2(n_max), T = std::min(1024, std::max(64, P / 2));
-  const size_t lds = fuseb_lds_bytes(P, T);
+  const int P = fuse_pow2(n_max), T = std::min(1024, std::max(64, P / 2));
+  const size_t lds = fuse_lds_bytes(P, T);
   if (lds > 65536)    // above HIP's default limit of dynamic LDS the kernel's own limit is raised (a process-wide, idempotent setting)
-    MRAG_HIP(hipFuncSetAttribute((const void*)fuse_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)fuseb_lds_bytes(FUSEB_MAX, 1024)));
+    MRAG_HIP(hipFuncSetAttribute((const void*)fuse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)fuse_lds_bytes(FUSE_MAX, 1024)));
   char* d = nullptr;
   MRAG_HIP(hipMalloc((void**)&d, in_bytes + out_bytes));
   char* d_out = d + in_bytes;
   hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(fuse_batch_kernel, dim3((unsigned)n_questions), dim3((unsigned)T), lds, stream, (const int32_t*)(d + i_ptr),
+    hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)n_questions), dim3((unsigned)T), lds, stream, (const int32_t*)(d + i_ptr),
                        (const int32_t*)(d + i_keys), (const double*)(d + i_scores), payload ? (const int32_t*)(d + i_pay) : nullptr,
                        (const int32_t*)(d + i_topk), alpha_text, alpha_graph, alpha_dense, out_stride, (int32_t*)(d_out + o_key),
                        (double*)(d_out + o_fused), (double*)(d_out + o_nt), (double*)(d_out + o_ng), (double*)(d_out + o_nd),
@@ -318,7 +288,7 @@ extern "C" int mrag_fuse_topk_batch(int device, int n_questions, const int32_t* 
   const hipError_t es = hipStreamSynchronize(stream);    // the staging buffers are in use until here, also after a failure
   if (e == hipSuccess) e = es;
   (void)hipFree(d);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "fuse_topk_batch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "fuse_topk failed: %s", hipGetErrorString(e));
   memcpy(out_scores, h_out.data() + o_fused, n_out * 8);
   memcpy(out_text_norm, h_out.data() + o_nt, n_out * 8);
   memcpy(out_graph_norm, h_out.data() + o_ng, n_out * 8);
@@ -328,3 +298,76 @@ extern "C" int mrag_fuse_topk_batch(int device, int n_questions, const int32_t* 
   memcpy(out_n, h_out.data() + o_n, (size_t)n_questions * 4);
   return MRAG_OK;
 }
+
+}  // namespace
+
+}  // namespace mrag
+
+using namespace mrag;
+
+extern "C" {
+
+// One question.  The caller's buffers hold min(top_k, entries) slots (mrag.h) and that is the stride of the one output
+// row, so they take the row as it is; slots past *out_n hold (-1, 0.0).
+int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_text, int n_graph, int n_dense,
+                   double alpha_text, double alpha_graph, double alpha_dense, int top_k, int32_t* out_keys,
+                   double* out_scores, double* out_text_norm, double* out_graph_norm, double* out_dense_norm,
+                   int* out_n, void* stream) {
+  if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
+  *out_n = 0;
+  if (n_text < 0 || n_graph < 0 || n_dense < 0 || top_k < 0) return fail(MRAG_ERR_INVALID, "negative size");
+  const int n = n_text + n_graph + n_dense;
+  if (n > FUSE_MAX) return fail(MRAG_ERR_UNSUPPORTED, "%d fusion entries exceed %d", n, FUSE_MAX);
+  if (n == 0 || top_k == 0) return MRAG_OK;
+  if (!keys || !scores || !out_keys || !out_scores || !out_text_norm || !out_graph_norm || !out_dense_norm)
+    return fail(MRAG_ERR_INVALID, "NULL buffer");
+  for (int i = 0; i < n; ++i)
+    if (!(scores[i] == scores[i])) return fail(MRAG_ERR_INVALID, "NaN score at fusion entry %d", i);
+  const int32_t chan_ptr[4] = {0, n_text, n_text + n_graph, n}, kk = std::min(top_k, n);
+  return fuse_questions(device, 1, chan_ptr, keys, scores, nullptr, alpha_text, alpha_graph, alpha_dense, &kk, kk, out_keys,
+                        out_scores, out_text_norm, out_graph_norm, out_dense_norm, nullptr, out_n, (hipStream_t)stream);
+}
+
+int mrag_fuse_topk_batch(int device, int n_questions, const int32_t* chan_ptr, const int32_t* keys, const double* scores,
+                         const int32_t* payload, double alpha_text, double alpha_graph, double alpha_dense,
+                         const int32_t* top_k, int out_stride, int32_t* out_keys, double* out_scores,
+                         double* out_text_norm, double* out_graph_norm, double* out_dense_norm, int32_t* out_payload,
+                         int32_t* out_n, void* stream) {
+  if (n_questions < 0 || out_stride < 0) return fail(MRAG_ERR_INVALID, "negative n_questions / out_stride");
+  if (n_questions == 0) return MRAG_OK;
+  if (!out_n) return fail(MRAG_ERR_INVALID, "out_n is NULL");
+  std::fill(out_n, out_n + n_questions, 0);
+  if (!chan_ptr || !top_k) return fail(MRAG_ERR_INVALID, "NULL chan_ptr / top_k");
+  const size_t n_out = (size_t)n_questions * out_stride;
+  if (n_out && (!out_keys || !out_scores || !out_text_norm || !out_graph_norm || !out_dense_norm || (payload && !out_payload)))
+    return fail(MRAG_ERR_INVALID, "NULL output buffer");
+
+  // ---- the whole batch is validated before any device work
+  if (chan_ptr[0] != 0) return fail(MRAG_ERR_INVALID, "chan_ptr must start at 0");
+  for (int g = 0; g < n_questions; ++g) {
+    const int32_t* p = chan_ptr + 3 * (size_t)g;
+    if (p[1] < p[0] || p[2] < p[1] || p[3] < p[2]) return fail(MRAG_ERR_INVALID, "chan_ptr decreases inside question %d", g);
+    if ((int64_t)p[3] - p[0] > FUSE_MAX)
+      return fail(MRAG_ERR_UNSUPPORTED, "question %d has %lld fusion entries, more than %d", g, (long long)p[3] - p[0], FUSE_MAX);
+    if (top_k[g] < 0 || top_k[g] > out_stride)
+      return fail(MRAG_ERR_INVALID, "top_k = %d of question %d outside [0, out_stride = %d]", top_k[g], g, out_stride);
+  }
+  const size_t E = (size_t)chan_ptr[3 * (size_t)n_questions];
+  if (E && (!keys || !scores)) return fail(MRAG_ERR_INVALID, "NULL keys / scores");
+  for (int g = 0; g < n_questions; ++g)
+    for (int i = chan_ptr[3 * (size_t)g]; i < chan_ptr[3 * (size_t)g + 3]; ++i)
+      if (!(scores[i] == scores[i]))
+        return fail(MRAG_ERR_INVALID, "NaN score at fusion entry %d of question %d", i - chan_ptr[3 * (size_t)g], g);
+
+  if (n_out == 0) return MRAG_OK;                        // every top_k is 0
+  if (E == 0) {                                          // only empty questions
+    std::fill(out_keys, out_keys + n_out, (int32_t)-1);
+    for (double* o : {out_scores, out_text_norm, out_graph_norm, out_dense_norm}) std::fill(o, o + n_out, 0.0);
+    if (payload) std::fill(out_payload, out_payload + 3 * n_out, (int32_t)-1);
+    return MRAG_OK;
+  }
+  return fuse_questions(device, n_questions, chan_ptr, keys, scores, payload, alpha_text, alpha_graph, alpha_dense, top_k, out_stride,
+                        out_keys, out_scores, out_text_norm, out_graph_norm, out_dense_norm, out_payload, out_n, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -91,13 +91,11 @@ def fuse_channels(text_hits, graph_hits, dense_scores: Dict[str, float], *, alph
 
 def fuse_channels_device(text_hits, graph_hits, dense_scores: Dict[str, float], *, alpha_text: float, alpha_graph: float,
                          alpha_dense: float, top_k: int, device: int = 0) -> List[Dict[str, Any]]:
-    """:func:`fuse_channels` with the arithmetic on the GPU (``mrag_fuse_topk``): ids are normalised and ranked
-    on the host (a key = the id's position among the call's sorted ids), the dedupe / min-max / weighted sum /
-    sort / truncate of retrieval_backend.py:336-372 run in one launch, and the host re-attaches ids and meta to
-    the ``top_k`` survivors.  Same values bit for bit (fp64, same operation order), same declared tie order."""
-    import ctypes as C
+    """:func:`fuse_channels` with the arithmetic on the GPU, as one question of :func:`fuse_entries_device_batch`: ids
+    are normalised and ranked on the host (a key = the id's position among the call's sorted ids), the dedupe / min-max /
+    weighted sum / sort / truncate of retrieval_backend.py:336-372 run in one launch, and the host re-attaches ids and
+    meta to the ``top_k`` survivors.  Same values bit for bit (fp64, same operation order), same declared tie order."""
     import numpy as np
-    from . import _native as N
     chans = []
     for hits in (text_hits, graph_hits):
         ent = []
@@ -112,23 +110,20 @@ def fuse_channels_device(text_hits, graph_hits, dense_scores: Dict[str, float], 
     key_of = {nid: i for i, nid in enumerate(ids)}
     keys = np.asarray([key_of[nid] for ent in chans for nid, _ in ent], dtype=np.int32)
     scores = np.asarray([v for ent in chans for _, v in ent], dtype=np.float64)
-    kk = int(min(top_k, len(ids)))
-    ok, osc = np.empty(kk, dtype=np.int32), np.empty(kk, dtype=np.float64)
-    nt, ng, nd = (np.empty(kk, dtype=np.float64) for _ in range(3))
-    n_out = C.c_int(0)
-    N.check(N.load().mrag_fuse_topk(device, keys.ctypes.data, scores.ctypes.data, len(chans[0]), len(chans[1]), len(chans[2]),
-                                    float(alpha_text), float(alpha_graph), float(alpha_dense), kk, ok.ctypes.data,
-                                    osc.ctypes.data, nt.ctypes.data, ng.ctypes.data, nd.ctypes.data, C.byref(n_out), None))
+    chan_ptr = np.cumsum([0] + [len(ent) for ent in chans], dtype=np.int32)
+    ok, osc, nt, ng, nd, _, n_out = fuse_entries_device_batch(
+        chan_ptr, keys, scores, None, alpha_text=alpha_text, alpha_graph=alpha_graph, alpha_dense=alpha_dense,
+        top_k=int(min(top_k, len(ids))), device=device)
     tmap, gmap = dedupe_by_norm_id(text_hits), dedupe_by_norm_id(graph_hits)        # meta merge of the survivors (host dicts)
     out = []
-    for i in range(n_out.value):
-        nid = ids[int(ok[i])]
+    for i in range(int(n_out[0])):
+        nid = ids[int(ok[0, i])]
         meta: Dict[str, Any] = {}
         for src in (tmap, gmap):
             if nid in src and isinstance(src[nid].get("meta"), dict):
                 meta.update(src[nid]["meta"])
-        meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[i]), float(ng[i]), float(nd[i])
-        out.append({"id": nid, "score": float(osc[i]), "meta": meta})
+        meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[0, i]), float(ng[0, i]), float(nd[0, i])
+        out.append({"id": nid, "score": float(osc[0, i]), "meta": meta})
     return out
 
 
@@ -164,8 +159,8 @@ def normalize_raw_hit(raw: Any, id_keys: Sequence[str] = ID_KEYS, score_keys: Se
     return {"id": str(hid), "score": score, "meta": meta}
 
 
-# ---- batched fusion (mrag_fuse_topk_batch): many questions, one launch ---------------------------------------------
-FUSE_MAX_ENTRIES = 4096          # entries of one question over its three channels: the limit of mrag_fuse_topk
+# ---- device fusion (mrag_fuse_topk_batch): many questions, one launch ----------------------------------------------
+FUSE_MAX_ENTRIES = 4096          # entries of one question over its three channels: the limit of the device call
 
 
 def corpus_norm_keys(rows: Sequence[Dict[str, Any]]):

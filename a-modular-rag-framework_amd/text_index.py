@@ -6,11 +6,11 @@
 (retrieval_backend.py:102-128: ``search(queries=, top_k=)`` -> hits with the same ids and meta).
 
 The index is built on the host like the reference builds it (same tokeniser, same counts) and uploaded once
-as CSR postings; every search then runs on the device (``mrag_bm25_search``): scores are the reference's
-fp64 sums bit for bit, order is (score desc, doc asc).  There is no CPU search path.
+as CSR postings; every search then runs on the device: scores are the reference's fp64 sums bit for bit, order is
+(score desc, doc asc).  There is no CPU search path.
 
-``search_batch`` answers many questions in one call (``mrag_bm25_search_batch``), each exactly as ``search`` answers
-it alone, and both take ``allow=``: the row filter of ``DenseIndex.search(allow=...)`` over the same docs.jsonl rows.
+``search_batch`` answers many questions in one call (``mrag_bm25_search_batch``); ``search`` is that call for one
+question.  Both take ``allow=``: the row filter of ``DenseIndex.search(allow=...)`` over the same docs.jsonl rows.
 """
 from __future__ import annotations
 
@@ -120,29 +120,11 @@ class HipBM25Index:
         return math.log((self.N - n + 0.5) / (n + 0.5) + 1.0) if self.N > 0 else 0.0
 
     def search(self, queries: List[str], top_k: int = 20, alpha_merge: str = "max", allow=None) -> List[Tuple[int, float]]:
-        """text_index.py:71-97 on the device.  ``[(doc_idx, score)]``, best first.  ``allow`` (see :meth:`search_batch`)
-        restricts the candidates to some documents; with a set the search runs as a batch of one question."""
-        if allow is not None:
-            return self.search_batch([queries], top_k=top_k, alpha_merge=alpha_merge, allow=allow)[0]
+        """text_index.py:71-97 on the device.  ``[(doc_idx, score)]``, best first: :meth:`search_batch` for the one
+        question ``queries``.  ``allow`` (see there) restricts the candidates to some documents."""
         if not self.N or not queries or top_k <= 0:
             return []
-        q_ptr, q_terms, q_idf = [0], [], []
-        for q in queries:
-            for t in tokenize(q):
-                q_terms.append(self._term_id.get(t, -1))
-                q_idf.append(self._idf(t))
-            q_ptr.append(len(q_terms))
-        k = int(min(top_k, self.N))
-        qp = np.asarray(q_ptr, dtype=np.int32)
-        qt = np.asarray(q_terms if q_terms else [0], dtype=np.int32)
-        qi = np.asarray(q_idf if q_idf else [0.0], dtype=np.float64)
-        docs = np.empty(k, dtype=np.int64)
-        scores = np.empty(k, dtype=np.float64)
-        n = C.c_int(0)
-        N.check(self._lib.mrag_bm25_search(self._h, len(queries), qp.ctypes.data, qt.ctypes.data, qi.ctypes.data,
-                                           1 if alpha_merge == "sum" else 0, k, docs.ctypes.data, scores.ctypes.data,
-                                           C.byref(n), None))
-        return [(int(d), float(s)) for d, s in zip(docs[:n.value], scores[:n.value])]
+        return self.search_batch([queries], top_k=top_k, alpha_merge=alpha_merge, allow=allow)[0]
 
     def _allow_words(self, allow) -> np.ndarray:
         """``allow`` -> the ABI's packed words (uint32 [ceil(N/32)], bit d%32 of word d/32).  A bool / uint8 mask over
@@ -157,19 +139,10 @@ class HipBM25Index:
             return np.ascontiguousarray(a)
         return np.ascontiguousarray(allow_bits(allow, self.N))
 
-    def search_batch(self, questions: Sequence[Sequence[str]], top_k: int = 20, alpha_merge: str = "max",
-                     allow=None) -> List[List[Tuple[int, float]]]:
-        """:meth:`search` for many questions in one call (``mrag_bm25_search_batch``).  ``questions[g]`` is the list of
-        expanded query strings of question g; the result holds one ``[(doc_idx, score)]`` list per question, each equal
-        to ``search(questions[g], top_k, alpha_merge)``: same documents, same score bits, same order.
-
-        ``allow`` restricts every question's candidates to a set of documents: a bool / uint8 mask over the documents,
-        integer document positions, or packed uint32 bits (:meth:`_allow_words`).  It changes no score -- idf and avgdl
-        stay the corpus's -- and ``None`` or an all-allowed set is the plain search."""
-        questions = [list(qs) for qs in questions]
-        if not self.N or not questions or top_k <= 0:
-            return [[] for _ in questions]
-        bits = self._allow_words(allow) if allow is not None else None
+    def _plan(self, questions: List[List[str]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``questions`` -> the call's ``(g_ptr, q_ptr, q_terms, q_idf)``: question g's expanded queries are
+        ``g_ptr[g] .. g_ptr[g+1]``, query q's tokens ``q_ptr[q] .. q_ptr[q+1]`` of ``q_terms`` (-1 = not in the
+        vocabulary) and ``q_idf``."""
         g_ptr, q_ptr, q_terms, q_idf = [0], [0], [], []
         known: Dict[str, Tuple[int, float]] = {}
         for qs in questions:
@@ -182,17 +155,33 @@ class HipBM25Index:
                     q_idf.append(e[1])
                 q_ptr.append(len(q_terms))
             g_ptr.append(len(q_ptr) - 1)
+        return (np.asarray(g_ptr, dtype=np.int32), np.asarray(q_ptr, dtype=np.int32),
+                np.asarray(q_terms if q_terms else [0], dtype=np.int32), np.asarray(q_idf if q_idf else [0.0], dtype=np.float64))
+
+    def _search_device(self, questions: List[List[str]], top_k: int, alpha_merge: str, allow):
+        """``mrag_bm25_search_batch`` over a non-empty index: ``(docs int64 [B][k], scores float64 [B][k], n int32 [B])``
+        with ``k = min(top_k, N)``."""
+        bits = self._allow_words(allow) if allow is not None else None
+        gp, qp, qt, qi = self._plan(questions)
         k, nq = int(min(top_k, self.N)), len(questions)
-        gp = np.asarray(g_ptr, dtype=np.int32)
-        qp = np.asarray(q_ptr, dtype=np.int32)
-        qt = np.asarray(q_terms if q_terms else [0], dtype=np.int32)
-        qi = np.asarray(q_idf if q_idf else [0.0], dtype=np.float64)
         docs = np.empty((nq, k), dtype=np.int64)
         scores = np.empty((nq, k), dtype=np.float64)
         n = np.zeros(nq, dtype=np.int32)
         N.check(self._lib.mrag_bm25_search_batch(self._h, nq, gp.ctypes.data, qp.ctypes.data, qt.ctypes.data, qi.ctypes.data,
                                                  1 if alpha_merge == "sum" else 0, k, bits.ctypes.data if bits is not None else None,
                                                  docs.ctypes.data, scores.ctypes.data, n.ctypes.data, None))
+        return docs, scores, n
+
+    def search_batch(self, questions: Sequence[Sequence[str]], top_k: int = 20, alpha_merge: str = "max",
+                     allow=None) -> List[List[Tuple[int, float]]]:
+        """Many questions in one call (``mrag_bm25_search_batch``).  ``questions[g]`` is the list of expanded query
+        strings of question g; the result holds one ``[(doc_idx, score)]`` list per question, best first, and a
+        question's answer does not depend on the batch it stands in.
+
+        ``allow`` restricts every question's candidates to a set of documents: a bool / uint8 mask over the documents,
+        integer document positions, or packed uint32 bits (:meth:`_allow_words`).  It changes no score -- idf and avgdl
+        stay the corpus's -- and ``None`` or an all-allowed set is the plain search."""
+        docs, scores, n = self.search_batch_arrays(questions, top_k=top_k, alpha_merge=alpha_merge, allow=allow)
         dl, sl = docs.tolist(), scores.tolist()
         return [list(zip(dl[g][:c], sl[g][:c])) for g, c in enumerate(n.tolist())]
 
@@ -205,31 +194,7 @@ class HipBM25Index:
         nq = len(questions)
         if not self.N or not questions or top_k <= 0:
             return np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0), dtype=np.float64), np.zeros(nq, dtype=np.int32)
-        bits = self._allow_words(allow) if allow is not None else None
-        g_ptr, q_ptr, q_terms, q_idf = [0], [0], [], []
-        known: Dict[str, Tuple[int, float]] = {}
-        for qs in questions:
-            for q in qs:
-                for t in tokenize(q):
-                    e = known.get(t)
-                    if e is None:
-                        e = known[t] = (self._term_id.get(t, -1), self._idf(t))
-                    q_terms.append(e[0])
-                    q_idf.append(e[1])
-                q_ptr.append(len(q_terms))
-            g_ptr.append(len(q_ptr) - 1)
-        k = int(min(top_k, self.N))
-        gp = np.asarray(g_ptr, dtype=np.int32)
-        qp = np.asarray(q_ptr, dtype=np.int32)
-        qt = np.asarray(q_terms if q_terms else [0], dtype=np.int32)
-        qi = np.asarray(q_idf if q_idf else [0.0], dtype=np.float64)
-        docs = np.empty((nq, k), dtype=np.int64)
-        scores = np.empty((nq, k), dtype=np.float64)
-        n = np.zeros(nq, dtype=np.int32)
-        N.check(self._lib.mrag_bm25_search_batch(self._h, nq, gp.ctypes.data, qp.ctypes.data, qt.ctypes.data, qi.ctypes.data,
-                                                 1 if alpha_merge == "sum" else 0, k, bits.ctypes.data if bits is not None else None,
-                                                 docs.ctypes.data, scores.ctypes.data, n.ctypes.data, None))
-        return docs, scores, n
+        return self._search_device(questions, top_k, alpha_merge, allow)
 
     def set_scratch_limit(self, nbytes: int) -> None:
         """Bytes of fp64 score rows (8 * N per expanded query) one chunk of :meth:`search_batch` may use

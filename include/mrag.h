@@ -370,7 +370,8 @@ int mrag_encoder_last_timing(mrag_handle h, float* out_ms);
  * search: n_queries token lists (q_ptr[n_queries+1] into q_terms / q_idf; a token outside the vocabulary is
  * id -1; q_idf = the reference's _idf of that token, :54-56).  fp64 throughout; a document's score is the
  * reference's left-to-right sum bit for bit.  merge_sum = 0: max over the queries (alpha_merge="max"), 1: sum.
- * Output: out_n <= k (doc, score) pairs, (score desc, doc asc), scores > 0 only.  Host buffers. */
+ * Output: out_n <= k (doc, score) pairs, (score desc, doc asc), scores > 0 only.  Host buffers of k slots; the
+ * slots past out_n are overwritten with (-1, 0.0). */
 int mrag_bm25_create(int device, int64_t n_docs, int64_t n_terms, const int64_t* indptr, const int32_t* post_doc,
                      const int32_t* post_tf, const double* doc_norm, double k1_plus_1, mrag_handle* out);
 int mrag_bm25_destroy(mrag_handle h);
@@ -384,7 +385,8 @@ int mrag_bm25_search(mrag_handle h, int n_queries, const int32_t* q_ptr, const i
  * Per channel: dedupe by key (strictly larger score wins, :336-348), min-max (:296-301); union:
  * alpha_t*ts + alpha_g*gs + alpha_d*ds (:363); order (score desc, key asc); top_k (:371-372).  fp64, the
  * reference's values bit for bit.  Outputs (host, length >= min(top_k, entries)): key, fused score and the three
- * score_*_norm values per kept hit; *out_n = hits written.  At most 4096 entries. */
+ * score_*_norm values per kept hit; *out_n = hits written, the slots past it up to that length are overwritten with
+ * key -1 and 0.0.  At most 4096 entries. */
 int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_text, int n_graph, int n_dense,
                    double alpha_text, double alpha_graph, double alpha_dense, int top_k, int32_t* out_keys,
                    double* out_scores, double* out_text_norm, double* out_graph_norm, double* out_dense_norm,

@@ -2,7 +2,7 @@
 
 A question is a dict ``{"n": (n_text, n_graph, n_dense), "keys": [...], "scores": [...], "payload": [...], "top_k": k}``:
 the three channels' entries back to back, as the C call takes them.  ``reference`` restates the rule of
-``fuse_topk_kernel`` with Python floats (IEEE fp64, no contraction) and dicts; ``as_channels`` turns a question into the
+``fuse_kernel`` (csrc/fuse.hip) with Python floats (IEEE fp64, no contraction) and dicts; ``as_channels`` turns a question into the
 hit dicts of ``fusion.fuse_channels`` so that tests/test_fuse_batch_host.py can tie ``reference`` to it.  Every case is
 built for one condition, which that file establishes with the host code alone.
 """

@@ -1,4 +1,4 @@
-"""The batched BM25 search (csrc/bm25_batch.hip, ``HipBM25Index.search_batch``) and the allow-set of the text channel on the
+"""The batched BM25 search (csrc/bm25.hip, ``HipBM25Index.search_batch``) and the allow-set of the text channel on the
 device -- the cases of ``tests/bm25_batch_cases.py``; ``tests/test_bm25_batch_host.py`` shows on the CPU what each can see.
 
 No tolerances: every comparison is documents plus score bits.  Expected values are ``oracle.bm25`` per question

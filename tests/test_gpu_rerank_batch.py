@@ -1,5 +1,6 @@
 """GPU tests of the batched dense re-rank: ``mrag_index_score_rows_batch`` against ``mrag_index_score_rows`` bit for bit on
-every index case and batch structure of ``tests/rerank_batch_cases.py``, its refusals through ctypes, and
+every index case and batch structure of ``tests/rerank_batch_cases.py``, both against the host's restatement of the
+summation order, its refusals through ctypes, and
 ``DenseRetrievalBackend(dense_mode="rerank")`` with ``run_batch`` against ``run``."""
 import ctypes as C
 import json
@@ -98,6 +99,36 @@ def test_a_search_is_not_disturbed_by_a_thousand_question_rerank():
     ix.score_rows_batch(rc.make_queries(200, "cosine", 300), [np.arange(5)] * 300)
     one_a = ix.search(qs[:1], 10)
     assert (one_b[1] == one_a[1]).all() and (_bits(one_b[0]) == _bits(one_a[0])).all() and (one_a[1][0] == after[1][0]).all()
+
+
+def test_a_search_is_not_disturbed_by_a_single_lookup():
+    """the single call prepares its query in row 0 of the search's query buffer and records that, so the next search
+    finds its zero padding as it needs it"""
+    ix = _index((200, "f16", "cosine"))
+    qs = rc.make_queries(200, "cosine", 5, seed=77)
+    lookup = rc.make_queries(200, "cosine", 1, seed=78)[0]
+    for part in (qs, qs[:1]):
+        before = ix.search(part, 10)
+        ix.score_rows(lookup, np.arange(200))
+        after = ix.search(part, 10)
+        assert (before[1] == after[1]).all() and (_bits(before[0]) == _bits(after[0])).all()
+
+
+@pytest.mark.parametrize("case", [c for c in rc.INDEX_CASES if c[2] == "wide"], ids=rc.case_id)
+def test_wide_scores_are_the_contracts_sum_bit_for_bit(case):
+    """A wide case is stored and asked without normalisation, so the kernel's operands are the storage roundings of the
+    host's values and its score is ``sum_kernel_order`` of their exact products.  Asked: the anchor query over the
+    cancelling rows, whose float32 score depends on that order (tests/test_rerank_batch_host.py), by both entry points."""
+    dim, dtype, kind = case
+    ix = _index(case)
+    q = rc.anchor_query(dim, kind)
+    ids = np.arange(rc.N_ROWS - rc.N_CANCEL, rc.N_ROWS, dtype=np.int64)
+    rows16 = rc.round_storage(rc.make_rows(dim, kind, dtype)[ids], dtype)
+    want = rc.sum_kernel_order(rc.products(rows16, rc.round_storage(q, dtype)))
+    single = ix.score_rows(q, ids, normalize=False)
+    batch = ix.score_rows_batch(q[None, :], [ids], normalize=False)[0]
+    assert (_bits(single) == _bits(want)).all(), np.flatnonzero(_bits(single) != _bits(want))
+    assert (_bits(batch) == _bits(want)).all(), np.flatnonzero(_bits(batch) != _bits(want))
 
 
 def test_refusals_name_the_question_and_leave_the_handle_usable():

@@ -1,4 +1,4 @@
-"""The text channel (csrc/bm25.hip), the fusion kernel and the fp64 cosine kernels (csrc/cosine_pairs.hip) at the sizes and
+"""The text channel (csrc/bm25.hip), the fusion kernel (csrc/fuse.hip) and the fp64 cosine kernels (csrc/cosine_pairs.hip) at the sizes and
 edges where their launches change shape -- the cases of ``oracle/text_cases.py``; ``tests/test_text_channel_host.py``
 shows on the CPU what each of them can see.
 
@@ -135,6 +135,56 @@ def test_fusion_refuses_4097_entries_and_nan():
             fusion.fuse_channels_device(bad, graph, dense, top_k=7, **_alphas(case))
     with pytest.raises(MragError):
         fusion.fuse_channels_device(text, graph, dict(dense, **{next(iter(dense)): float("nan")}), top_k=7, **_alphas(case))
+
+
+def test_the_single_question_entry_points_refuse_on_their_own():
+    """``mrag_bm25_search`` and ``mrag_fuse_topk`` through ctypes: the Python classes reach the device through the batch
+    entry points, so the checks the single-question entry points make before the shared path are asked here -- status,
+    message, ``*out_n = 0``, no output slot written, and the next good call served."""
+    from mrag_amd import _native as N
+    lib = N.load()
+    case = next(c for c in tc.BM25_CASES if c.via == "abi")
+    p = _postings(case)
+    n_terms = len(p["indptr"]) - 1
+    ix = _AbiIndex(p, case.k1)
+    n = C.c_int(9)
+    try:
+        docs, scores = np.full(4, 7, dtype=np.int64), np.full(4, 7.0)
+
+        def search(nq, q_ptr, terms, k=4):
+            qp, qt = np.asarray(q_ptr, dtype=np.int32), np.asarray(terms or [0], dtype=np.int32)
+            qi = np.ones(len(qt))
+            return lib.mrag_bm25_search(ix.h, nq, qp.ctypes.data, qt.ctypes.data, qi.ctypes.data, 0, k, docs.ctypes.data,
+                                        scores.ctypes.data, C.byref(n), None)
+
+        for want, word, args in ((-5, "exceeds", (1, [0, 1], [0], 4096 + 1)),
+                                 (-5, "queries", (tc.BM25_MAX_QUERIES + 1, [0] * (tc.BM25_MAX_QUERIES + 2), [])),
+                                 (-1, "monotone", (2, [0, 1, 0], [0])),
+                                 (-1, "vocabulary", (1, [0, 1], [n_terms]))):
+            n.value = 9
+            st = search(*args)
+            assert st == want and word in lib.mrag_last_error().decode(), (st, word, lib.mrag_last_error())
+            assert n.value == 0 and (docs == 7).all() and (scores == 7.0).all()
+        assert search(1, [0, 1], [0]) == 0 and 0 <= n.value <= 4
+    finally:
+        ix.close()
+
+    keys, zeros = np.zeros(tc.FUSE_MAX + 1, dtype=np.int32), np.zeros(tc.FUSE_MAX + 1)
+    nan_at_9 = np.zeros(10)
+    nan_at_9[9] = np.nan
+    ok, vals = np.full(4, 7, dtype=np.int32), [np.full(4, 7.0) for _ in range(4)]
+
+    def fuse(sizes, sc):
+        return lib.mrag_fuse_topk(0, keys.ctypes.data, sc.ctypes.data, *sizes, 0.4, 0.2, 0.4, 4, ok.ctypes.data,
+                                  *[v.ctypes.data for v in vals], C.byref(n), None)
+
+    for want, word, sizes, sc in ((-5, "exceed", (tc.FUSE_MAX + 1, 0, 0), zeros), (-5, "exceed", (2000, 97, 2000), zeros),
+                                  (-1, "negative", (3, -1, 3), zeros), (-1, "entry 9", (3, 3, 4), nan_at_9)):
+        n.value = 9
+        st = fuse(sizes, sc)
+        assert st == want and word in lib.mrag_last_error().decode(), (st, word, lib.mrag_last_error())
+        assert n.value == 0 and (ok == 7).all() and all((v == 7.0).all() for v in vals)
+    assert fuse((3, 3, 3), nan_at_9) == 0 and n.value == 1 and ok[0] == 0 and (ok[1:] == -1).all()   # one key, nine entries
 
 
 # ------------------------------------------------------------------------------------------------ cosine

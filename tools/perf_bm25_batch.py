@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Development timing of the batched BM25 search against a loop of single searches -- not the graded bench.
+"""Development timing of the BM25 search at batches of 1 ... 10 000 questions -- not the graded bench.
 
 The corpus of tools/perf_bm25.py (Zipf, 1 M documents, vocabulary of 30 000), top_k = 200, questions of 1 and of 3
 expanded queries with 4-5 tokens each, batches of 1, 32, 1 000 and 10 000 questions.  Per shape: ms per call and us per
-question of ``search_batch``, the same questions as a loop of ``search``, the number of chunks, and whether both give
-identical lists.
+question of ``search_batch``, the same questions as a loop of ``search`` (a batch of one question per call: the same
+kernels, so the loop shows what one call per question costs, not another implementation), the number of chunks, and
+whether both give identical lists.
 
-The baseline of a comparison is the PARENT build's loop, not this build's: build the parent's library (say into
-build_ab/base.so), then run, on one box and alternating as tools/ab.sh does,
-    MRAG_HIP_LIB=build_ab/base.so python tools/perf_bm25_batch.py --loop-only
-    python tools/perf_bm25_batch.py
-``--loop-only`` times only the loop; a library without the batch entry points is accepted there.
+First leg, ``mrag_bm25_search`` through ctypes: us per call of the C entry point for one question, median of 200 calls
+after 20 warm-ups.  It is the leg to compare two builds of the library with: build the other commit's library (say into
+build_ab/base.so) and run, on one box and alternating as tools/ab.sh does,
+    MRAG_HIP_LIB=build_ab/base.so python tools/perf_bm25_batch.py --loop-only --sizes 1
+    python tools/perf_bm25_batch.py --loop-only --sizes 1
+A build from before the single search became a batch of one runs its own single-question kernels there; the Python
+classes of this tree reach every build through ``mrag_bm25_search_batch``.  ``--loop-only`` leaves ``search_batch`` out.
 Every result is also printed as one JSON line (prefix "JSON ").
 """
 import argparse
@@ -49,7 +52,7 @@ def questions(n, per_question, p):
 
 
 def n_chunks(sizes, n_docs, limit):
-    """The chunking rule of csrc/bm25_batch.hip: whole questions in order while their rows fit, at most 1024 per chunk."""
+    """The chunking rule of csrc/bm25.hip: whole questions in order while their rows fit, at most 1024 per chunk."""
     cap = min(max(limit // (8 * n_docs), 1), 65535)
     chunks = rows = held = 0
     for s in sizes:
@@ -59,6 +62,28 @@ def n_chunks(sizes, n_docs, limit):
             chunks, rows, held = chunks + 1, 0, 0
         rows, held = rows + s, held + 1
     return chunks
+
+
+def abi_single_us(ix, question, reps=200):
+    """median us per call of ``mrag_bm25_search`` for the expanded queries of one question"""
+    import ctypes as C
+    from mrag_amd import _native as N
+    from mrag_amd.text_index import tokenize
+    q_ptr, terms, idf = [0], [], []
+    for q in question:
+        for t in tokenize(q):
+            terms.append(ix._term_id.get(t, -1))
+            idf.append(ix._idf(t))
+        q_ptr.append(len(terms))
+    qp, qt, qi = np.asarray(q_ptr, dtype=np.int32), np.asarray(terms or [0], dtype=np.int32), np.asarray(idf or [0.0])
+    k = min(TOP_K, ix.N)
+    docs, scores, n = np.empty(k, dtype=np.int64), np.empty(k), C.c_int(0)
+
+    def call():
+        N.check(ix._lib.mrag_bm25_search(ix._h, len(question), qp.ctypes.data, qt.ctypes.data, qi.ctypes.data, 0, k,
+                                         docs.ctypes.data, scores.ctypes.data, C.byref(n), None))
+    timed(call, 20)
+    return 1e6 * float(np.median(timed(call, reps)[1]))
 
 
 def timed(fn, reps):
@@ -78,12 +103,6 @@ def main():
     ap.add_argument("--limit", type=int, default=0, help="scratch limit in bytes (0 = the default)")
     a = ap.parse_args()
     from mrag_amd import _native as N
-    if a.loop_only:
-        import ctypes
-        lib = ctypes.CDLL(str(N.lib_path()))
-        for name in ("mrag_bm25_search_batch", "mrag_bm25_set_scratch_limit"):
-            if not hasattr(lib, name):
-                N.EXTENSION_SIGNATURES.pop(name, None)
     from mrag_amd.text_index import HipBM25Index
     rows, p = corpus(a.n_docs)
     t0 = time.perf_counter()
@@ -94,6 +113,9 @@ def main():
     sizes = [int(s) for s in a.sizes.split(",")]
     for per_question in (1, 3):
         pool = questions(max(sizes), per_question, p)
+        us = abi_single_us(ix, pool[0])
+        print(f"  {per_question} q/question: mrag_bm25_search through ctypes {us:7.1f} us/call", flush=True)
+        print("JSON " + json.dumps({"n_docs": a.n_docs, "queries_per_question": per_question, "abi_single_us": us}), flush=True)
         ix.search(pool[0], top_k=TOP_K)
         if not a.loop_only:
             ix.search_batch(pool[:2], top_k=TOP_K)

@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
-"""Development timing of the batched hybrid retrieval against its one-question forms -- not the graded bench.
+"""Development timing of the hybrid retrieval at batches of 1 ... 10 000 questions -- not the graded bench.
 
 Part 1, fusion: questions of 200 text + 0 graph + 200 dense hits (the reference's pools), batches of 1, 32, 1 000 and
-10 000 questions.  Per size: ms per call and us per question of ``fusion.fuse_channels_device_batch``, the same
-questions as a loop of ``fusion.fuse_channels_device``, and whether both give identical lists.
+10 000 questions.  First ``mrag_fuse_topk`` through ctypes: us per call of the C entry point for one question, median
+of 200 calls after 20 warm-ups.  Then per size: ms per call and us per question of ``fusion.fuse_channels_device_batch``,
+the same questions as a loop of ``fusion.fuse_channels_device`` (a batch of one question per call: the same kernel),
+and whether both give identical lists.
 
 Part 2, backend: ``DenseRetrievalBackend.run_batch`` on 1 000 requests over a 200 000-row corpus (``text_channel="bm25"``,
 ``fuse_on_device=True``, a stub router with 64-dimensional embeddings) against the loop of ``run``.
 
-The baseline of a comparison is the PARENT build's loop, not this build's: build the parent's library (say into
-build_ab/base.so), then run, on one box, three rounds of
+To compare two builds of the library, build the other commit's (say into build_ab/base.so), then run, on one box, three
+rounds of
     MRAG_HIP_LIB=build_ab/base.so python tools/perf_hybrid_batch.py --loop-only
-    python tools/perf_hybrid_batch.py
-alternating as tools/ab.sh does; the spread of the parent's three rounds is the noise a difference has to exceed.
-``--loop-only`` times only the loops; a library without the batch entry point is accepted there.
+    python tools/perf_hybrid_batch.py --loop-only
+alternating as tools/ab.sh does; the spread of one build's three rounds is the noise a difference has to exceed.  The
+ctypes leg is the one that reaches a build's own single-question kernel, where it has one (builds from before
+``mrag_fuse_topk`` became a batch of one); the Python functions of this tree reach every build through
+``mrag_fuse_topk_batch``.  ``--loop-only`` leaves the batch calls out.
 Every result is also printed as one JSON line (prefix "JSON ").
 """
 import argparse
@@ -43,6 +47,28 @@ def fusion_questions(n):
         text = [{"id": ids[i], "score": float(s), "meta": {"doc": f"T{g % 97}-{i}", "sent_id": i % 4, "text": "x"}} for i, s in zip(t_pick, t_sc)]
         out.append((text, [], {ids[i]: float(s) for i, s in zip(d_pick, d_sc)}))
     return out
+
+
+def abi_single_us(question, reps=200):
+    """median us per call of ``mrag_fuse_topk`` for one question's entries (keys = ranks of the sorted ids, as
+    ``fusion.fuse_channels_device`` builds them)"""
+    import ctypes as C
+    from mrag_amd import _native as N, fusion
+    text, graph, dense = question
+    chans = [[(fusion.normalize_id(h)[0], float(h["score"])) for h in hits] for hits in (text, graph)] + [list(dense.items())]
+    key_of = {nid: i for i, nid in enumerate(sorted({nid for ent in chans for nid, _ in ent}))}
+    keys = np.asarray([key_of[nid] for ent in chans for nid, _ in ent], dtype=np.int32)
+    scores = np.asarray([v for ent in chans for _, v in ent], dtype=np.float64)
+    kk = min(20, len(key_of))
+    ok, vals, n = np.empty(kk, dtype=np.int32), [np.empty(kk) for _ in range(4)], C.c_int(0)
+    lib = N.load()
+
+    def call():
+        N.check(lib.mrag_fuse_topk(0, keys.ctypes.data, scores.ctypes.data, *[len(ent) for ent in chans], ALPHAS["alpha_text"],
+                                   ALPHAS["alpha_graph"], ALPHAS["alpha_dense"], kk, ok.ctypes.data, *[v.ctypes.data for v in vals],
+                                   C.byref(n), None))
+    timed(call, 20)
+    return 1e6 * float(np.median(timed(call, reps)[1]))
 
 
 def timed(fn, reps):
@@ -116,16 +142,13 @@ def main():
     ap.add_argument("--skip-backend", action="store_true")
     a = ap.parse_args()
     from mrag_amd import _native as N
-    if a.loop_only:
-        import ctypes
-        lib = ctypes.CDLL(str(N.lib_path()))
-        for name in list(getattr(N, "FUSE_BATCH_SIGNATURES", {})):
-            if not hasattr(lib, name):
-                N.FUSE_BATCH_SIGNATURES.pop(name)
     from mrag_amd import fusion
     print(f"library {N.lib_path()}", flush=True)
     sizes = [int(s) for s in a.sizes.split(",")]
     pool = fusion_questions(max(sizes))
+    us = abi_single_us(pool[0])
+    print(f"  mrag_fuse_topk through ctypes, {2 * POOL} entries: {us:7.1f} us/call", flush=True)
+    print("JSON " + json.dumps({"part": "fusion", "entries": 2 * POOL, "abi_single_us": us}), flush=True)
     fusion.fuse_channels_device(*pool[0], top_k=20, **ALPHAS)
     if not a.loop_only:
         fusion.fuse_channels_device_batch(pool[:2], top_k=20, **ALPHAS)
