@@ -1,5 +1,5 @@
 """ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h,
-include/mrag_rerank_batch.h).  There is no CPU fallback: a missing
+include/mrag_rerank_batch.h, include/mrag_filter_batch.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -132,6 +132,12 @@ RERANK_BATCH_SIGNATURES = {
     "mrag_index_score_rows_batch": [_h, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp],
 }
 
+# include/mrag_filter_batch.h (a table of its own, as the two before it: EXTENSION_SIGNATURES stays the BM25 header's)
+FILTER_BATCH_SIGNATURES = {
+    "mrag_index_search_sets": [_h, _vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mrag_index_last_sets": [_h, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -151,7 +157,8 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(str(p))
-    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES}.items():
+    for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES,
+                           **FILTER_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

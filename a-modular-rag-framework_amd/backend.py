@@ -237,7 +237,7 @@ class DenseRetrievalBackend:
                  graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None,
                  text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
                  fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
-                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search"):
+                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -262,6 +262,9 @@ class DenseRetrievalBackend:
         if dense_row_filter is not None and not callable(dense_row_filter):
             raise TypeError(f"dense_row_filter must be callable or a 'pkg.mod:func' string, got {type(dense_row_filter)}")
         self.dense_row_filter = dense_row_filter
+        # run_batch: the requests whose filter returns a set share ONE DenseIndex.search_sets call instead of one filtered
+        # search each (off by default: their diagnostics then name the path "sets", not the single search's)
+        self.dense_filter_batch = bool(dense_filter_batch)
         self._own_text_search = None                     # the searcher _bm25_searcher() made over index_path, if any
         if text_channel not in (None, "bm25"):
             raise ValueError(f"unknown text_channel {text_channel!r} (supported: 'bm25')")
@@ -574,11 +577,14 @@ class DenseRetrievalBackend:
         and one ``mrag_fuse_topk_batch``.  ``top_k``, ``trace_id`` and the pool are each request's own: the searches run
         at the list's largest pool and every question uses the leading part of its lists that its own pool covers (both
         searches are exact with a declared order, so a prefix is the smaller search's answer).  Requests for which
-        ``dense_row_filter`` returns a set are searched one by one with their ``allow``; an injected ``text_search`` and
+        ``dense_row_filter`` returns a set are searched one by one with their ``allow`` -- or, with
+        ``dense_filter_batch=True``, all together in one ``DenseIndex.search_sets`` call in which sets of equal content
+        are shared and whose diagnostics read ``dense_filter = {"path": "sets", "allowed": m}``; an injected ``text_search`` and
         ``graph_expand`` are called once per request.  Like :meth:`run` it degrades and never raises out of the dense
         channel.  Diagnostics are :meth:`run`'s plus ``batch_size``.  With ``dense_mode="rerank"`` the dense search is
         replaced by one ``DenseIndex.score_rows_batch`` over every question's leading text candidates (own BM25 searcher)
         or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`."""
+        from .index import pack_sets
         from .text_index import HipBM25TextSearcher
         reqs = list(reqs)
         B = len(reqs)
@@ -643,6 +649,10 @@ class DenseRetrievalBackend:
                     d_ids = np.full((B, max(min(pool_max, len(rows)), 0)), -1, dtype=np.int64)
                     d_sc = np.full(d_ids.shape, -np.inf, dtype=np.float32)
                     plain = []
+                    in_sets: List[int] = []                  # dense_filter_batch: the requests that share the search_sets call
+                    set_index: Dict[bytes, int] = {}         # ... the distinct sets by content -> position in set_list
+                    set_list: List[np.ndarray] = []
+                    set_of: List[int] = []
                     for g, r in enumerate(reqs):
                         try:
                             allow = self.dense_row_filter(r, rows) if self.dense_row_filter is not None else None
@@ -650,6 +660,15 @@ class DenseRetrievalBackend:
                                 plain.append(g)
                                 continue
                             k_eff[g] = min(pool[g], len(rows), k_one)
+                            if self.dense_filter_batch:
+                                set_rows = pack_sets([allow], len(rows))[1]
+                                key = set_rows.tobytes()
+                                if key not in set_index:
+                                    set_index[key] = len(set_list)
+                                    set_list.append(set_rows)
+                                in_sets.append(g)
+                                set_of.append(set_index[key])
+                                continue
                             sc, ids = ix.search(Q[g:g + 1], k_eff[g], allow=allow)
                             dense_filter[g] = ix.last_filter()
                             d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
@@ -657,6 +676,18 @@ class DenseRetrievalBackend:
                             dense_error[g] = repr(e)
                             d_ids[g] = -1
                             logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
+                    if in_sets:
+                        try:
+                            sc, ids = ix.search_sets(Q[in_sets], max(k_eff[g] for g in in_sets), set_list,
+                                                     set_of=np.asarray(set_of, dtype=np.int32))
+                            for j, g in enumerate(in_sets):
+                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
+                                dense_filter[g] = {"path": "sets", "allowed": int(set_list[set_of[j]].shape[0])}
+                        except Exception as e:
+                            for g in in_sets:
+                                dense_error[g] = repr(e)
+                                d_ids[g] = -1
+                            logger.error("[DenseRetrievalBackend] dense channel failed for the filtered requests: %s", e)
                     if plain:
                         try:
                             k_batch = min(max(pool[g] for g in plain), len(rows), k_many)

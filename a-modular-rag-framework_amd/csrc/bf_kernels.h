@@ -113,6 +113,22 @@ int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<R
 int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const RerankDesc* desc, int64_t n_desc,
                         const int64_t* ids, int64_t n_rows, float* out, hipStream_t stream);
 
+// The gathered-set scan of mrag_index_search_sets (bf_filter_batch.hip).  One descriptor = one chunk of <= SETS_CHUNK rows
+// of one set x <= SETS_CHUNK of the questions that use it:
+//   [0] first slot in qlist (the questions sorted by set)     [1] questions (<= 128)
+//   [2] first position in set_rows                            [3] rows (<= 128)      [4] index of the first row inside the set
+//   [5],[6] float offset of the first question's score segment (low, high)           [7] segment pitch (floats, % 32 == 0)
+// Slot s of the descriptor writes S[offset + s * pitch + [4] ...]: the questions of a set hold consecutive segments.
+constexpr int SETS_DESC_WORDS = 8;
+constexpr int SETS_CHUNK = 128;
+// Largest set the scan route serves: the register-path capacity of the select kernel (SEL_CAP in ivf_scan.hip, 256 threads
+// x 32 entries).  The project's own constant, not a tuned one: a measured crossover would replace it, with its measurement
+// in DESIGN.md.
+constexpr int SETS_SCAN_MAX_ROWS = 8192;
+// scores of every descriptor's (row, question) pairs -> S; all pointers are device pointers, `zero` is a row of ld zeros
+int launch_sets_scan(const uint16_t* corpus, const uint16_t* queries, const uint16_t* zero, int ld, int dtype, const int* desc,
+                     int n_desc, const int64_t* set_rows, const int* qlist, float* S, hipStream_t stream);
+
 #if defined(__HIPCC__)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -98,6 +98,37 @@ def _allow_buffer(allow, n: int, device: int):
     return bits, bits.ctypes.data, N.ALLOW_BITS32, 0
 
 
+def pack_sets(sets, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host allow-sets -> the CSR of ``mrag_index_search_sets``: ``(set_ptr int64 [len(sets) + 1], set_rows int64)``.
+
+    Every entry of ``sets`` is what :func:`allow_bits` takes: a bool / uint8 mask of length ``n`` or a 1-D array of row
+    positions ``0 .. n-1``.  Positions come out sorted and deduplicated, as a mask gives them; a wrong mask length, a
+    position outside the rows or an input that is not 1-D raises ``ValueError``.  No GPU is needed."""
+    rows = []
+    for s, one in enumerate(sets):
+        if _is_torch(one):
+            one = one.cpu().numpy()
+        a = np.asarray(one)
+        if a.ndim != 1:
+            raise ValueError(f"set {s} must be 1-D, got shape {a.shape}")
+        if a.dtype == np.bool_ or a.dtype == np.uint8:
+            if a.shape[0] != n:
+                raise ValueError(f"set {s}: the mask has {a.shape[0]} entries, the index holds {n} rows")
+            r = np.flatnonzero(a).astype(np.int64)
+        elif np.issubdtype(a.dtype, np.integer) or a.size == 0:
+            r = np.unique(a.astype(np.int64))
+            if r.size and (int(r[0]) < 0 or int(r[-1]) >= n):
+                raise ValueError(f"set {s}: row positions must lie in [0, {n}), got [{int(r[0])}, {int(r[-1])}]")
+        else:
+            raise ValueError(f"set {s} must be a bool/uint8 mask or integer row positions, got dtype {a.dtype}")
+        rows.append(r)
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        np.cumsum([r.shape[0] for r in rows], out=ptr[1:])
+    flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, dtype=np.int64)
+    return ptr, flat.astype(np.int64, copy=False)
+
+
 IVF_FILTER_PATHS = {"auto": N.IVF_FILTER_AUTO, "probe": N.IVF_FILTER_PROBE, "exact": N.IVF_FILTER_EXACT}
 _IVF_FILTER_NAMES = {N.IVF_FILTER_PROBE: "probe", N.IVF_FILTER_EXACT: "exact"}
 
@@ -412,6 +443,48 @@ class DenseIndex:
         p, m = C.c_int(0), C.c_int64(0)
         N.check(self._lib.mrag_index_last_filter(self._h, C.byref(p), C.byref(m)))
         return {"path": _FILTER_NAMES[p.value], "allowed": m.value}
+
+    def search_sets(self, queries, k: int, sets, set_of=None, normalize: Optional[bool] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`search` with ``allow=`` for a batch of questions that each have their own allow-set, in one call
+        (``mrag_index_search_sets``) -> (scores [nq,k] fp32, ids [nq,k] int64), numpy.
+
+        ``sets`` is a sequence of bool masks over the ``len(self)`` rows or of row-position arrays (:func:`pack_sets`), and
+        question q searches ``sets[set_of[q]]``; ``set_of``
+        defaults to one set per question when there are as many sets as questions.  Per question: the top-k of its
+        set's rows, (score desc, row asc), (-inf, -1) past the set's size.  Sets of up to 8 192 rows are gathered and
+        scored by one scan launch for the whole batch; a larger set is one filtered search over all of its questions
+        (:meth:`last_sets`, :meth:`last_filter`).  Host queries only."""
+        if normalize is None:
+            normalize = self.metric == "cosine"
+        k = _check_k(k, 256)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        if is_dev:
+            raise ValueError("search_sets takes host queries")
+        set_ptr, set_rows = pack_sets(sets, len(self))
+        n_sets = set_ptr.shape[0] - 1
+        if set_of is None:
+            if n_sets != nq:
+                raise ValueError(f"{n_sets} sets for {nq} questions: pass set_of")
+            set_of = np.arange(nq, dtype=np.int32)
+        so = np.asarray(set_of)
+        if so.ndim != 1 or so.shape[0] != nq or not (np.issubdtype(so.dtype, np.integer) or so.size == 0):
+            raise ValueError(f"set_of must hold one set index per question ({nq}), got shape {so.shape} dtype {so.dtype}")
+        if so.size and (int(so.min()) < 0 or int(so.max()) >= n_sets):
+            raise ValueError(f"set_of must lie in [0, {n_sets}), got [{int(so.min())}, {int(so.max())}]")
+        so = np.ascontiguousarray(so, dtype=np.int32)
+        sc = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        N.check(self._lib.mrag_index_search_sets(self._h, ptr, nq, dt, int(bool(normalize)), k, n_sets, set_ptr.ctypes.data,
+                                                 set_rows.ctypes.data, so.ctypes.data, sc.ctypes.data, ids.ctypes.data, None))
+        del keep
+        return sc, ids
+
+    def last_sets(self) -> dict:
+        """What the last :meth:`search_sets` did (``mrag_index_last_sets``): ``{"scanned": questions served by the scan,
+        "routed": questions served by filtered searches, "descriptors": scan descriptors launched}``."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        N.check(self._lib.mrag_index_last_sets(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"scanned": a.value, "routed": b.value, "descriptors": c.value}
 
     def last_fp8(self) -> dict:
         """Refine pool and regime of the last fp8 search on this index (``mrag_index_last_fp8``):

@@ -401,5 +401,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 #include "mrag_bm25_batch.h"
 #include "mrag_fuse_batch.h"
 #include "mrag_rerank_batch.h"
+#include "mrag_filter_batch.h"
 
 #endif /* MRAG_H_ */
