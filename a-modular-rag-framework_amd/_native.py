@@ -1,5 +1,5 @@
 """ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h,
-include/mrag_rerank_batch.h, include/mrag_filter_batch.h).  There is no CPU fallback: a missing
+include/mrag_rerank_batch.h, include/mrag_filter_batch.h, include/mrag_search_groups.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -138,6 +138,12 @@ FILTER_BATCH_SIGNATURES = {
     "mrag_index_last_sets": [_h, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
 }
 
+# include/mrag_search_groups.h
+SEARCH_GROUPS_SIGNATURES = {
+    "mrag_index_search_groups": [_h, _vp, _i64, _i, _i, _i, _i, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _vp],
+    "mrag_index_last_groups": [_h, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -158,7 +164,7 @@ def load():
         pass
     lib = C.CDLL(str(p))
     for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES,
-                           **FILTER_BATCH_SIGNATURES}.items():
+                           **FILTER_BATCH_SIGNATURES, **SEARCH_GROUPS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

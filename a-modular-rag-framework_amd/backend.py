@@ -237,7 +237,8 @@ class DenseRetrievalBackend:
                  graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None,
                  text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
                  fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
-                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False):
+                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False,
+                 query_expander: Optional[Any] = None, dense_expanded: bool = False):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -275,6 +276,20 @@ class DenseRetrievalBackend:
         if dense_mode == "rerank" and dense_row_filter is not None:
             raise ValueError("dense_row_filter restricts the corpus-wide search: it has no meaning with dense_mode='rerank'")
         self.dense_mode = dense_mode
+        # query_expander(query=, trace_id=) -> List[str] (the signature of the reference's LLMQueryExpander.expand): the
+        # reference's Expand step, queries = [req.query] + expanded (retrieval_backend.py:307-310); a "pkg.mod:func"
+        # string is resolved like dense_row_filter.  The text channel always receives the list; the dense channel embeds
+        # and searches all of it, max-merged per row (DenseIndex.search_groups), only with dense_expanded=True
+        if isinstance(query_expander, str):
+            from .adapter import import_from_string
+            query_expander = import_from_string(query_expander)
+        if query_expander is not None and not callable(query_expander):
+            raise TypeError(f"query_expander must be callable or a 'pkg.mod:func' string, got {type(query_expander)}")
+        self.query_expander = query_expander
+        self.dense_expanded = bool(dense_expanded)
+        if self.dense_expanded and dense_mode == "rerank":
+            raise ValueError("dense_mode='rerank' scores the candidates with req.query alone (retrieval_backend.py:333): "
+                             "it does not combine with dense_expanded=True")
         self._state = None
 
     # -- corpus index: built once per (file signature, model), shared process-wide --------------
@@ -427,11 +442,26 @@ class DenseRetrievalBackend:
         return self._state
 
     # -- the backend protocol ---------------------------------------------------------------------
+    def _expand(self, req, trace_id: str):
+        """The reference's Expand step (retrieval_backend.py:307-310) -> (``[req.query] + expanded``, error text or None).
+        Without a ``query_expander`` there is no step and no span; an expander that raises is logged and the request
+        runs with ``[req.query]``."""
+        if self.query_expander is None:
+            return [req.query], None
+        with span("Backend/Expand", self.sink, trace_id):
+            try:
+                expanded = self.query_expander(query=req.query, trace_id=trace_id)
+                return [req.query] + [str(q) for q in (expanded or [])], None
+            except Exception as e:
+                logger.error("[DenseRetrievalBackend] query expansion failed: %s", e)
+                return [req.query], repr(e)
+
     def run(self, req) -> Dict[str, Any]:
         trace_id = getattr(req, "trace_id", None) or "trace-demo"                       # :304
         top_k = int(getattr(req, "top_k", None) or self.default_top_k)                  # :305
         model_hint = resolve_embed_model(self.router)
         pool = max(top_k, self.dense_pool_k)
+        queries, expand_error = self._expand(req, trace_id)
 
         t_hits: List[Dict[str, Any]] = []
         g_hits: List[Dict[str, Any]] = []
@@ -448,12 +478,12 @@ class DenseRetrievalBackend:
         if self.text_search is not None:
             with span("Backend/TextSearch", self.sink, trace_id):
                 if own:
-                    ranked = (self.text_search.index.search([req.query], top_k=pool, alpha_merge="max")
+                    ranked = (self.text_search.index.search(queries, top_k=pool, alpha_merge="max")
                               if self.text_search.index.N > 0 else [])
                     t_docs = [int(d) for d, _ in ranked]
                     t_hits = self.text_search._hits(ranked)
                 else:
-                    t_hits = list(self.text_search(queries=[req.query], top_k=pool) or [])
+                    t_hits = list(self.text_search(queries=queries, top_k=pool) or [])
         if self.graph_expand is not None:
             with span("Backend/GraphExpand", self.sink, trace_id):
                 g_hits = list(self.graph_expand(query=req.query, graph_id=getattr(req, "graph_id", "") or "",
@@ -469,7 +499,16 @@ class DenseRetrievalBackend:
                 if rerank and t_hits:
                     dense_hits = self._rerank_one(req, t_hits[:pool], t_docs[:pool] if own else None, pool, model_hint, trace_id)
                     k_eff = len(dense_hits)
-                if state is not None and state["index"] is not None:
+                if state is not None and state["index"] is not None and self.dense_expanded:
+                    # every query of the request, max-merged per row on the device: one group
+                    Qv = self._embed_texts(queries, model_hint, trace_id, dim=state["dim"])
+                    k_eff = min(pool, len(state["rows"]), state["index"].max_k(1))
+                    allow = self.dense_row_filter(req, state["rows"]) if self.dense_row_filter is not None else None
+                    sc, ids = state["index"].search_groups(Qv, k_eff, sizes=[len(queries)], allow=allow)
+                    if allow is not None:
+                        dense_filter = state["index"].last_filter()
+                    dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
+                elif state is not None and state["index"] is not None:
                     qv = np.asarray(_vectors(self.router.embed(model_hint=model_hint, texts=[req.query],
                                                                require={"trace_id": trace_id}))[0], dtype=np.float32)
                     if qv.shape[0] != state["dim"]:
@@ -484,12 +523,7 @@ class DenseRetrievalBackend:
                     else:
                         sc, ids = state["index"].search(qv[None, :], k_eff, allow=allow)
                         dense_filter = state["index"].last_filter()
-                    for s, i in zip(sc[0], ids[0]):
-                        if i < 0:
-                            continue
-                        row = state["rows"][int(i)]
-                        dense_hits.append({"id": _fusion.raw_hit_id(row), "score": float(s),
-                                           "meta": _fusion.row_meta(row, "dense")})
+                    dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
             except Exception as e:     # reference policy: degrade, never raise out of run() (:229-231)
                 dense_error = repr(e)
                 logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
@@ -509,7 +543,7 @@ class DenseRetrievalBackend:
                 h["meta"] = meta
         fused = fused[:top_k]
         diagnostics = {
-            "queries": [req.query],
+            "queries": queries,
             "bm25_candidates": len(t_hits),
             "graph_candidates": len(g_hits),
             "dense_scored": len(dense_scores),
@@ -524,7 +558,15 @@ class DenseRetrievalBackend:
             diagnostics["dense_mode"] = "rerank"
         if dense_filter is not None:
             diagnostics["dense_filter"] = dense_filter
+        if expand_error is not None:
+            diagnostics["expand_error"] = expand_error
         return {"hits": fused, "diagnostics": diagnostics}
+
+    @staticmethod
+    def _dense_hits(rows, scores, ids) -> List[Dict[str, Any]]:
+        """one result row of a dense search as the dense channel's hits; the (-inf, -1) slots are left out"""
+        return [{"id": _fusion.raw_hit_id(rows[int(i)]), "score": float(s), "meta": _fusion.row_meta(rows[int(i)], "dense")}
+                for s, i in zip(scores, ids) if i >= 0]
 
     # -- dense_mode="rerank": the dense channel scores the text channel's candidates ------------------------------------
     def _is_own_searcher(self) -> bool:
@@ -583,7 +625,10 @@ class DenseRetrievalBackend:
         ``graph_expand`` are called once per request.  Like :meth:`run` it degrades and never raises out of the dense
         channel.  Diagnostics are :meth:`run`'s plus ``batch_size``.  With ``dense_mode="rerank"`` the dense search is
         replaced by one ``DenseIndex.score_rows_batch`` over every question's leading text candidates (own BM25 searcher)
-        or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`."""
+        or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`.  With a ``query_expander``
+        every request is expanded first (``Backend/Expand``) and the text channel receives each request's list; with
+        ``dense_expanded=True`` the dense channel embeds all of those queries and makes ONE ``DenseIndex.search_groups``
+        call over the unfiltered requests and one per filtered request (``dense_filter_batch`` then has no effect)."""
         from .index import pack_sets
         from .text_index import HipBM25TextSearcher
         reqs = list(reqs)
@@ -595,6 +640,8 @@ class DenseRetrievalBackend:
         top_k = [int(getattr(r, "top_k", None) or self.default_top_k) for r in reqs]
         pool = [max(k, self.dense_pool_k) for k in top_k]
         pool_max = max(pool)
+        expanded = [self._expand(r, trace[g]) for g, r in enumerate(reqs)]
+        queries = [e[0] for e in expanded]
 
         # ---- text and graph channels
         text_error = None
@@ -614,12 +661,12 @@ class DenseRetrievalBackend:
         if bm25:
             with span("Backend/TextSearch", self.sink, trace[0]):
                 if self.text_search.index.N > 0:
-                    t_arrays = self.text_search.index.search_batch_arrays([[r.query] for r in reqs], top_k=pool_max,
+                    t_arrays = self.text_search.index.search_batch_arrays(queries, top_k=pool_max,
                                                                           alpha_merge="max")
         elif self.text_search is not None:
             for g, r in enumerate(reqs):
                 with span("Backend/TextSearch", self.sink, trace[g]):
-                    t_hits[g] = list(self.text_search(queries=[r.query], top_k=pool[g]) or [])
+                    t_hits[g] = list(self.text_search(queries=queries[g], top_k=pool[g]) or [])
         if self.graph_expand is not None:
             for g, r in enumerate(reqs):
                 with span("Backend/GraphExpand", self.sink, trace[g]):
@@ -644,7 +691,12 @@ class DenseRetrievalBackend:
                     state = self._get_state(model_hint, trace[0])
                 if not rerank and state["index"] is not None:
                     ix, rows = state["index"], state["rows"]
-                    Q = self._embed_texts([r.query for r in reqs], model_hint, trace[0], dim=state["dim"])
+                    if self.dense_expanded:              # every query of every request: request g owns Q[qp[g]:qp[g + 1]]
+                        qp = np.zeros(B + 1, dtype=np.int64)
+                        np.cumsum([len(q) for q in queries], out=qp[1:])
+                        Q = self._embed_texts([q for qs in queries for q in qs], model_hint, trace[0], dim=state["dim"])
+                    else:
+                        Q = self._embed_texts([r.query for r in reqs], model_hint, trace[0], dim=state["dim"])
                     k_one, k_many = ix.max_k(1), ix.max_k(B)
                     d_ids = np.full((B, max(min(pool_max, len(rows)), 0)), -1, dtype=np.int64)
                     d_sc = np.full(d_ids.shape, -np.inf, dtype=np.float32)
@@ -660,6 +712,11 @@ class DenseRetrievalBackend:
                                 plain.append(g)
                                 continue
                             k_eff[g] = min(pool[g], len(rows), k_one)
+                            if self.dense_expanded:          # one grouped search per filtered request, as run()
+                                sc, ids = ix.search_groups(Q[qp[g]:qp[g + 1]], k_eff[g], sizes=[len(queries[g])], allow=allow)
+                                dense_filter[g] = ix.last_filter()
+                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
+                                continue
                             if self.dense_filter_batch:
                                 set_rows = pack_sets([allow], len(rows))[1]
                                 key = set_rows.tobytes()
@@ -688,7 +745,34 @@ class DenseRetrievalBackend:
                                 dense_error[g] = repr(e)
                                 d_ids[g] = -1
                             logger.error("[DenseRetrievalBackend] dense channel failed for the filtered requests: %s", e)
-                    if plain:
+                    if plain and self.dense_expanded:
+                        # ONE grouped search at the largest pool; a request whose queries x that pool exceed the merge's
+                        # 4096 entries is searched alone at its own pool, where run() would succeed or fail as well
+                        k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
+                        alone = [g for g in plain if len(queries[g]) * k_batch > 4096]
+                        plain = [g for g in plain if len(queries[g]) * k_batch <= 4096]
+                        for g in alone:
+                            try:
+                                k_eff[g] = min(pool[g], len(rows), k_one)
+                                sc, ids = ix.search_groups(Q[qp[g]:qp[g + 1]], k_eff[g], sizes=[len(queries[g])])
+                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
+                            except Exception as e:
+                                dense_error[g] = repr(e)
+                                d_ids[g] = -1
+                                logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
+                        if plain:
+                            try:
+                                rows_of = np.concatenate([np.arange(qp[g], qp[g + 1]) for g in plain])
+                                sc, ids = ix.search_groups(Q[rows_of], k_batch, sizes=[len(queries[g]) for g in plain])
+                                for j, g in enumerate(plain):
+                                    k_eff[g] = min(pool[g], k_batch)
+                                    d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
+                            except Exception as e:
+                                for g in plain:
+                                    dense_error[g] = repr(e)
+                                    d_ids[g] = -1
+                                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+                    elif plain:
                         try:
                             k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
                             sc, ids = ix.search(Q[plain] if len(plain) < B else Q, k_batch)
@@ -768,7 +852,7 @@ class DenseRetrievalBackend:
         out = []
         for g, (hits, n_text, n_dense) in enumerate(results):
             diagnostics = {
-                "queries": [reqs[g].query],
+                "queries": queries[g],
                 "bm25_candidates": n_text,
                 "graph_candidates": len(g_hits[g]),
                 "dense_scored": n_dense,
@@ -784,6 +868,8 @@ class DenseRetrievalBackend:
                 diagnostics["dense_mode"] = "rerank"
             if dense_filter[g] is not None:
                 diagnostics["dense_filter"] = dense_filter[g]
+            if expanded[g][1] is not None:
+                diagnostics["expand_error"] = expanded[g][1]
             out.append({"hits": hits, "diagnostics": diagnostics})
         return out
 

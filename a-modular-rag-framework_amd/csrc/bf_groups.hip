@@ -1,0 +1,143 @@
+// Grouped max-merge of dense search results (mrag_index_search_groups): several query vectors that are ONE question.
+// The search leaves [nq][k] (score, id) lists on the device, each in the index's declared order (score desc, id asc),
+// padded with (-inf, -1); question g owns the queries group_ptr[g] .. group_ptr[g+1).  Per question:
+//   drop the padding (id -1); per distinct id keep its largest score, among equal scores the lowest query position inside
+//   the group; order the survivors by (score desc, id asc); write the first k as (score, id, which = that query position);
+//   the slots past the distinct ids hold (-inf, -1, -1); an empty group is such a row.
+// Exact: the union of the per-query top-k lists holds the top-k of the row-wise maximum over the group's queries, ties
+// included (DESIGN.md §3 "Grouped queries").
+//
+//   grid       one workgroup per question; blockDim = half the largest question's padded size, 64 .. 1024 threads
+//   LDS        dynamic, sized by the largest question of the launch; a question of n = q * k entries works on P = the power
+//              of two >= n (at least 2).  Entry e = j * k + r is slot r of the group's j-th query: `which` is e / k and is
+//              not stored.  The entries are staged ONCE and stay until the outputs are written:
+//                id     8 P       int64, after id_base
+//                score  4 P
+//                perm   2 P       entry indexes, sorted twice in place
+//                head   1 P       by entry: 1 = the entry that represents its id
+//              15 P bytes: 7.5 KiB for a question of 2 queries at k = 200 (P = 512), 60 KiB at the limit of 4096 entries --
+//              below the 64 KiB a kernel gets without raising its dynamic-LDS limit, two workgroups per 160 KiB CU.
+//              Both sorts read score / id THROUGH perm, so their LDS addresses are data dependent whatever the layout; the
+//              sequential accesses (staging, perm itself, head, the outputs) are unit stride per array: 4-byte and 8-byte
+//              arrays conflict free, neighbouring 2-byte / 1-byte elements share a dword, which is a broadcast.
+//   sort 1     bitonic over entry indexes by (real before padding, id asc, score desc, entry asc).  Scores are compared as
+//              floats, never as bit patterns: -0.0 == +0.0, and the lower entry -- the lower query position -- stays in
+//              front.  The first entry of an id run is the one kept.
+//   heads      head[e] = 1 for the first entry of every id run
+//   sort 2     bitonic over the same perm by (head before the rest, score desc, id asc)
+//   output     slot r < k: the r-th entry of sort 2 if it is a head, else (-inf, -1, -1)
+// Work per question: O(P log^2 P) compare-exchanges in LDS; global memory is read once and written once.  A question's
+// three outputs depend on its own entries alone (P on its own n; blockDim only shares the work out).
+#include "bf_kernels.h"
+
+namespace mrag {
+
+static_assert(15 * GROUPS_MAX_ENTRIES <= 65536, "the grouped merge stays inside the default dynamic-LDS limit");
+
+__host__ __device__ inline int groups_pow2(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+static inline size_t groups_lds_bytes(int P) { return (size_t)15 * P; }
+
+// bitonic sort of perm[0 .. P) (P a power of two, distinct elements) under a strict total order; ends on a barrier
+template <class Less>
+__device__ inline void groups_sort(unsigned short* perm, int P, Less less) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+        const unsigned short a = perm[i], b = perm[l];
+        if (less((int)b, (int)a) == ((i & k) == 0)) { perm[i] = b; perm[l] = a; }
+      }
+      __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(1024) void groups_merge_kernel(const float* __restrict__ in_sc, const int64_t* __restrict__ in_id,
+                                                            const int64_t* __restrict__ group_ptr, int k,
+                                                            float* __restrict__ out_sc, int64_t* __restrict__ out_id,
+                                                            int32_t* __restrict__ out_which) {
+  extern __shared__ __attribute__((aligned(16))) char groups_lds[];
+  const int g = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const int64_t q0 = group_ptr[g];
+  const int n = (int)(group_ptr[g + 1] - q0) * k;          // <= GROUPS_MAX_ENTRIES (validated on the host)
+  const int P = groups_pow2(n);
+  int64_t* s_id = (int64_t*)groups_lds;
+  float* s_sc = (float*)(s_id + P);
+  unsigned short* perm = (unsigned short*)(s_sc + P);
+  unsigned char* head = (unsigned char*)(perm + P);
+
+  // the group's lists are consecutive: entry e is element e of in_sc / in_id behind query q0
+  for (int e = tid; e < P; e += T) {
+    s_id[e] = e < n ? in_id[(size_t)q0 * k + e] : (int64_t)-1;
+    s_sc[e] = e < n ? in_sc[(size_t)q0 * k + e] : -INFINITY;
+    perm[e] = (unsigned short)e;
+    head[e] = 0;
+  }
+  __syncthreads();
+
+  // 1) real entries before the padding, then (id asc, score desc, entry asc)
+  groups_sort(perm, P, [=](int a, int b) {
+    const int64_t ia = s_id[a], ib = s_id[b];
+    if (ib == -1) return ia != -1 || a < b;
+    if (ia == -1) return false;
+    if (ia != ib) return ia < ib;
+    const float sa = s_sc[a], sb = s_sc[b];
+    if (sa > sb) return true;
+    if (sa < sb) return false;
+    return a < b;
+  });
+
+  // 2) the first entry of an id run represents the id
+  for (int p = tid; p < P; p += T) {
+    const int e = perm[p];
+    const int64_t id = s_id[e];
+    if (id != -1 && (p == 0 || s_id[perm[p - 1]] != id)) head[e] = 1;
+  }
+  __syncthreads();
+
+  // 3) heads first, by (score desc, id asc): two heads never share an id
+  groups_sort(perm, P, [=](int a, int b) {
+    const int ha = head[a], hb = head[b];
+    if (!hb) return ha || a < b;
+    if (!ha) return false;
+    const float sa = s_sc[a], sb = s_sc[b];
+    if (sa > sb) return true;
+    if (sa < sb) return false;
+    return s_id[a] < s_id[b];
+  });
+
+  // 4) the first k heads, then (-inf, -1, -1)
+  for (int r = tid; r < k; r += T) {
+    float sc = -INFINITY;
+    int64_t id = -1;
+    int32_t which = -1;
+    if (r < P) {
+      const int e = perm[r];
+      if (head[e]) { sc = s_sc[e]; id = s_id[e]; which = e / k; }
+    }
+    const size_t o = (size_t)g * k + r;
+    out_sc[o] = sc;
+    out_id[o] = id;
+    if (out_which) out_which[o] = which;
+  }
+}
+
+// n_groups >= 1 questions of at most max_entries = (largest group) * k <= GROUPS_MAX_ENTRIES entries each; every pointer
+// is a device pointer, in_sc / in_id are the [nq][k] lists of a search, out_which may be NULL
+int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
+                        float* out_sc, int64_t* out_id, int32_t* out_which, hipStream_t stream) {
+  if (max_entries > GROUPS_MAX_ENTRIES) return fail(MRAG_ERR_UNSUPPORTED, "%d entries in one question exceed %d", max_entries, GROUPS_MAX_ENTRIES);
+  if (n_groups > 2147483647ll) return fail(MRAG_ERR_UNSUPPORTED, "%lld questions exceed one launch", (long long)n_groups);
+  const int P = groups_pow2(max_entries), T = std::min(1024, std::max(64, P / 2));
+  const size_t lds = groups_lds_bytes(P);
+  if (lds > 65536) return fail(MRAG_ERR_UNSUPPORTED, "%zu bytes of LDS for one question exceed 65536", lds);
+  hipLaunchKernelGGL(groups_merge_kernel, dim3((unsigned)n_groups), dim3((unsigned)T), lds, stream, in_sc, in_id, group_ptr, k, out_sc,
+                     out_id, out_which);
+  MRAG_HIP(hipGetLastError());
+  return MRAG_OK;
+}
+
+}  // namespace mrag

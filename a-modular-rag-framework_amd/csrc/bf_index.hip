@@ -72,7 +72,13 @@ struct BfIndex : Object {
   // (descriptors | question list | segment table), the scanned sets' rows, the score segments
   DevBuf sets_q, sets_plan, sets_rows, sets_S;
   int64_t last_sets[3] = {-1, -1, -1};      // of the last mrag_index_search_sets: scanned questions, routed questions, descriptors
+  // grouped queries (mrag_index_search_groups): the search's [nq][k] lists (ids | scores), group_ptr on the device (uploaded
+  // from grp_host, which outlives the call), the merged rows of a call with host outputs (ids | scores | which)
+  DevBuf grp_in, grp_ptr, grp_out;
+  std::vector<int64_t> grp_host;
+  int64_t last_groups[3] = {-1, -1, -1};    // of the last mrag_index_search_groups: queries, questions, entries of the largest question
   ~BfIndex() override {
+    grp_in.release(); grp_ptr.release(); grp_out.release();
     sets_q.release(); sets_plan.release(); sets_rows.release(); sets_S.release();
     if (rows) (void)hipFree(rows);
     if (rows8) (void)hipFree(rows8);
@@ -1056,6 +1062,87 @@ int mrag_index_last_sets(mrag_handle h, int64_t* out_scanned_questions, int64_t*
   if (out_scanned_questions) *out_scanned_questions = ix->last_sets[0];
   if (out_routed_questions) *out_routed_questions = ix->last_sets[1];
   if (out_descriptors) *out_descriptors = ix->last_sets[2];
+  return MRAG_OK;
+}
+
+int mrag_index_search_groups(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                             int k, int64_t n_groups, const int64_t* group_ptr, const void* allow, int64_t allow_rows,
+                             int allow_format, float* out_scores, int64_t* out_ids, int32_t* out_which, int out_is_device,
+                             void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_nq_k(nq, k));
+  if (n_groups < 0) return fail(MRAG_ERR_INVALID, "n_groups < 0");
+  if (n_groups == 0 && nq == 0) return MRAG_OK;
+  if (!group_ptr || !out_scores || !out_ids || (nq > 0 && !queries)) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  if (!dtype_size(q_dtype)) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  if (group_ptr[0] != 0) return fail(MRAG_ERR_INVALID, "group_ptr[0] = %lld, not 0 (question 0)", (long long)group_ptr[0]);
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (group_ptr[g + 1] < group_ptr[g])
+      return fail(MRAG_ERR_INVALID, "group_ptr decreases at question %lld (%lld -> %lld)", (long long)g, (long long)group_ptr[g],
+                  (long long)group_ptr[g + 1]);
+  if (group_ptr[n_groups] != nq)
+    return fail(MRAG_ERR_INVALID, "group_ptr ends at %lld behind question %lld, not at nq = %lld", (long long)group_ptr[n_groups],
+                (long long)n_groups - 1, (long long)nq);
+  int64_t q_max = 0;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    const int64_t q = group_ptr[g + 1] - group_ptr[g];
+    if (q * k > GROUPS_MAX_ENTRIES)
+      return fail(MRAG_ERR_UNSUPPORTED, "question %lld has %lld queries x k = %d = %lld entries, more than %d", (long long)g, (long long)q,
+                  k, (long long)(q * k), GROUPS_MAX_ENTRIES);
+    q_max = std::max(q_max, q);
+  }
+  if (allow) MRAG_TRY(check_allow_args(allow_rows, ix->n, allow_format, MRAG_FILTER_AUTO, "filter"));
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  ix->last_groups[0] = -1;
+
+  // ---- one search of all nq queries into index-owned scratch (mrag_index_max_k is 256 for every nq: never cut)
+  const size_t n_in = (size_t)nq * k, n_out = (size_t)n_groups * k;
+  MRAG_TRY(ix->grp_in.ensure(std::max<size_t>(n_in, 1) * 12));
+  int64_t* s_id = (int64_t*)ix->grp_in.p;
+  float* s_sc = (float*)(s_id + n_in);
+  if (nq > 0) {
+    if (allow)
+      MRAG_TRY(search_allowed(h, queries, nq, q_dtype, normalize, queries_is_device, k, nullptr, allow, allow_rows, allow_format, 0,
+                              MRAG_FILTER_AUTO, s_sc, s_id, nullptr, 1, stream_));
+    else
+      MRAG_TRY(mrag_index_search(h, queries, nq, q_dtype, normalize, queries_is_device, k, s_sc, s_id, 1, stream_));
+  }
+
+  // ---- one merge launch, straight into device outputs
+  ix->grp_host.assign(group_ptr, group_ptr + n_groups + 1);
+  MRAG_TRY(ix->grp_ptr.ensure((size_t)(n_groups + 1) * 8));
+  float* d_sc = out_scores;
+  int64_t* d_id = out_ids;
+  int32_t* d_wh = out_which;
+  if (!out_is_device) {
+    MRAG_TRY(ix->grp_out.ensure(n_out * 16));
+    d_id = (int64_t*)ix->grp_out.p;
+    d_sc = (float*)(d_id + n_out);
+    d_wh = out_which ? (int32_t*)(d_sc + n_out) : nullptr;
+  }
+  MRAG_HIP(hipMemcpyAsync(ix->grp_ptr.p, ix->grp_host.data(), (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, stream));
+  MRAG_TRY(launch_groups_merge(s_sc, s_id, (const int64_t*)ix->grp_ptr.p, n_groups, k, (int)(q_max * k), d_sc, d_id, d_wh, stream));
+  if (!out_is_device) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, n_out * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, n_out * 8, hipMemcpyDeviceToHost, stream));
+    if (out_which) MRAG_HIP(hipMemcpyAsync(out_which, d_wh, n_out * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+  }
+  ix->last_groups[0] = nq;
+  ix->last_groups[1] = n_groups;
+  ix->last_groups[2] = q_max * k;
+  return MRAG_OK;
+}
+
+int mrag_index_last_groups(mrag_handle h, int64_t* out_queries, int64_t* out_groups, int64_t* out_max_entries) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_groups[0] < 0) return fail(MRAG_ERR_INVALID, "no completed search over grouped queries on this index");
+  if (out_queries) *out_queries = ix->last_groups[0];
+  if (out_groups) *out_groups = ix->last_groups[1];
+  if (out_max_entries) *out_max_entries = ix->last_groups[2];
   return MRAG_OK;
 }
 

@@ -129,6 +129,14 @@ constexpr int SETS_SCAN_MAX_ROWS = 8192;
 int launch_sets_scan(const uint16_t* corpus, const uint16_t* queries, const uint16_t* zero, int ld, int dtype, const int* desc,
                      int n_desc, const int64_t* set_rows, const int* qlist, float* S, hipStream_t stream);
 
+// The grouped max-merge of mrag_index_search_groups (bf_groups.hip): question g owns the search's lists of the queries
+// group_ptr[g] .. group_ptr[g+1); per question the k best distinct ids by their largest score, (score desc, id asc), with
+// the position inside the group of the query that gave it.  One workgroup per question sorts its entries in LDS, which
+// bounds a question at GROUPS_MAX_ENTRIES = queries * k entries (fuse.hip's limit).  All pointers are device pointers.
+constexpr int GROUPS_MAX_ENTRIES = 4096;
+int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
+                        float* out_sc, int64_t* out_id, int32_t* out_which, hipStream_t stream);
+
 #if defined(__HIPCC__)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -129,6 +129,29 @@ def pack_sets(sets, n: int) -> Tuple[np.ndarray, np.ndarray]:
     return ptr, flat.astype(np.int64, copy=False)
 
 
+def group_ptr_of(group_ptr, sizes, nq: int) -> np.ndarray:
+    """The ``group_ptr`` of ``mrag_index_search_groups`` (int64 [n_groups + 1]) from itself or from the questions' group
+    ``sizes`` (exactly one of the two), checked against ``nq`` query rows: it starts at 0, never decreases and ends at
+    ``nq``.  ``ValueError`` otherwise.  No GPU is needed."""
+    if (group_ptr is None) == (sizes is None):
+        raise ValueError("pass exactly one of group_ptr and sizes")
+    a = np.asarray(group_ptr if sizes is None else sizes)
+    if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0) or a.dtype == np.bool_:
+        raise ValueError(f"group_ptr / sizes must be 1-D integers, got shape {a.shape} dtype {a.dtype}")
+    a = a.astype(np.int64)
+    if sizes is not None:
+        if a.size and int(a.min()) < 0:
+            raise ValueError(f"question {int(np.flatnonzero(a < 0)[0])} has a negative group size")
+        a = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(a, dtype=np.int64)])
+    if a.size == 0 or a[0] != 0:
+        raise ValueError("group_ptr must start at 0")
+    if (np.diff(a) < 0).any():
+        raise ValueError(f"group_ptr decreases at question {int(np.flatnonzero(np.diff(a) < 0)[0])}")
+    if int(a[-1]) != nq:
+        raise ValueError(f"the groups hold {int(a[-1])} queries, {nq} were given")
+    return np.ascontiguousarray(a)
+
+
 IVF_FILTER_PATHS = {"auto": N.IVF_FILTER_AUTO, "probe": N.IVF_FILTER_PROBE, "exact": N.IVF_FILTER_EXACT}
 _IVF_FILTER_NAMES = {N.IVF_FILTER_PROBE: "probe", N.IVF_FILTER_EXACT: "exact"}
 
@@ -485,6 +508,63 @@ class DenseIndex:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         N.check(self._lib.mrag_index_last_sets(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"scanned": a.value, "routed": b.value, "descriptors": c.value}
+
+    def search_groups(self, queries, k: int, group_ptr=None, sizes=None, allow=None, normalize: Optional[bool] = None,
+                      stream=None, out=None, return_which: bool = False):
+        """:meth:`search` for questions that each come as several query vectors (the question and its expansions), merged
+        per row with the maximum on the device (``mrag_index_search_groups``) -> (scores [n_groups,k] fp32, ids
+        [n_groups,k] int64), with ``return_which=True`` also which [n_groups,k] int32.
+
+        Question g owns the rows ``group_ptr[g] .. group_ptr[g+1]`` of ``queries`` (``group_ptr``: n_groups + 1
+        non-decreasing integers from 0 to ``len(queries)``); ``sizes``, the number of queries of every question, is
+        accepted instead (:func:`group_ptr_of`).  Per question: a row scores the largest of its scores under the
+        question's queries, and the result is the top-k of those in (score desc, id asc) order -- bit for bit the merge
+        of the per-query :meth:`search` results.  ``which`` is the position inside the question of the query that gave
+        the kept score (the lowest among equals); slots past the distinct rows found are (-inf, -1, -1), and so is the
+        row of a question without queries.  ``1 <= k <= 256`` and at most 4096 // k queries per question.
+
+        Host queries give numpy results; CUDA tensors give CUDA tensors written on ``stream`` (default: torch's current
+        stream); ``out=(scores, ids)`` or ``(scores, ids, which)`` reuses buffers.  ``allow`` is one allow-set for the
+        whole call, as in :meth:`search` (packed on the host).  :meth:`last_groups` tells what the call did.  Exact
+        precision only; the fp8 scan copy, the sharded indexes and ``IVFFlatIndex`` have no grouped search."""
+        if normalize is None:
+            normalize = self.metric == "cosine"
+        k = _check_k(k, 256)
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        gp = group_ptr_of(group_ptr, sizes, nq)
+        n_groups = gp.shape[0] - 1
+        n, abits, aptr = 0, None, None
+        if allow is not None:
+            n = len(self)
+            abits = np.ascontiguousarray(allow_bits(allow, n))
+            aptr = abits.ctypes.data
+        if out is not None and return_which and len(out) < 3:
+            raise ValueError("return_which=True needs out=(scores, ids, which)")
+        which = None
+        if out is not None and len(out) > 2:
+            which = out[2]
+        elif return_which and is_dev:
+            import torch
+            which = torch.empty((n_groups, k), dtype=torch.int32, device=keep.device)
+        elif return_which:
+            which = np.empty((n_groups, k), dtype=np.int32)
+        wptr = None if which is None else (which.data_ptr() if is_dev else which.ctypes.data)
+        norm = int(bool(normalize))
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_index_search_groups(self._h, ptr, nq, dt, norm, is_dev, k, n_groups, gp.ctypes.data, aptr, n,
+                                                      N.ALLOW_BITS32, sc, ids, wptr, out_dev, st)
+        sc, ids = _run_search(call, keep, n_groups, k, is_dev, self.device, stream, bool(is_dev),
+                              None if out is None else (out[0], out[1]))
+        del abits
+        return (sc, ids, which) if return_which else (sc, ids)
+
+    def last_groups(self) -> dict:
+        """What the last :meth:`search_groups` did (``mrag_index_last_groups``): ``{"queries": query vectors searched,
+        "groups": questions merged, "max_entries": queries x k of the largest question}``."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        N.check(self._lib.mrag_index_last_groups(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"queries": a.value, "groups": b.value, "max_entries": c.value}
 
     def last_fp8(self) -> dict:
         """Refine pool and regime of the last fp8 search on this index (``mrag_index_last_fp8``):

@@ -402,5 +402,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 #include "mrag_fuse_batch.h"
 #include "mrag_rerank_batch.h"
 #include "mrag_filter_batch.h"
+#include "mrag_search_groups.h"
 
 #endif /* MRAG_H_ */
