@@ -1,5 +1,6 @@
 """ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h,
-include/mrag_rerank_batch.h, include/mrag_filter_batch.h, include/mrag_search_groups.h).  There is no CPU fallback: a missing
+include/mrag_rerank_batch.h, include/mrag_filter_batch.h, include/mrag_search_groups.h,
+include/mrag_search_collapsed.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -144,6 +145,13 @@ SEARCH_GROUPS_SIGNATURES = {
     "mrag_index_last_groups": [_h, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
 }
 
+# include/mrag_search_collapsed.h
+SEARCH_COLLAPSED_SIGNATURES = {
+    "mrag_index_set_row_keys": [_h, _vp, _i64, _i],
+    "mrag_index_search_collapsed": [_h, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "mrag_index_last_collapsed": [_h, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -164,7 +172,8 @@ def load():
         pass
     lib = C.CDLL(str(p))
     for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES,
-                           **FILTER_BATCH_SIGNATURES, **SEARCH_GROUPS_SIGNATURES}.items():
+                           **FILTER_BATCH_SIGNATURES, **SEARCH_GROUPS_SIGNATURES,
+                           **SEARCH_COLLAPSED_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

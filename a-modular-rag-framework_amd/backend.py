@@ -238,7 +238,8 @@ class DenseRetrievalBackend:
                  text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
                  fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
                  dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False,
-                 query_expander: Optional[Any] = None, dense_expanded: bool = False):
+                 query_expander: Optional[Any] = None, dense_expanded: bool = False,
+                 dense_collapse: Optional[Any] = None):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -290,7 +291,32 @@ class DenseRetrievalBackend:
         if self.dense_expanded and dense_mode == "rerank":
             raise ValueError("dense_mode='rerank' scores the candidates with req.query alone (retrieval_backend.py:333): "
                              "it does not combine with dense_expanded=True")
+        # dense_collapse: the dense channel returns the best DOCUMENTS, each by its best row (DenseIndex.search_collapsed),
+        # instead of the best rows.  A row field name ("title"), a callable row -> hashable, or a "pkg.mod:func" string
+        # resolved like dense_row_filter gives every row its document
+        if isinstance(dense_collapse, str) and ":" in dense_collapse:
+            from .adapter import import_from_string
+            dense_collapse = import_from_string(dense_collapse)
+        if dense_collapse is not None and not isinstance(dense_collapse, str) and not callable(dense_collapse):
+            raise TypeError(f"dense_collapse must be a row field name, a callable or a 'pkg.mod:func' string, got {type(dense_collapse)}")
+        if dense_collapse is not None and (dense_mode == "rerank" or dense_row_filter is not None or self.dense_expanded):
+            raise ValueError("dense_collapse does not combine with dense_mode='rerank', dense_row_filter or dense_expanded=True")
+        self.dense_collapse = dense_collapse
         self._state = None
+
+    def _collapse_keys(self, state):
+        """The row keys of ``dense_collapse`` over the state's rows -> ``(keys, distinct keys, max rows per key)``: built
+        once per state and per ``dense_collapse`` value, and set on the (shared) index unless it already holds that array."""
+        from .index import row_keys_of
+        made = state.setdefault("collapse_keys", {})
+        if self.dense_collapse not in made:
+            by = self.dense_collapse
+            made[by] = row_keys_of([by(r) if callable(by) else r.get(by) for r in state["rows"]])
+        entry = made[self.dense_collapse]
+        if state.get("collapse_on_index") is not entry[0]:
+            state["index"].set_row_keys(entry[0])
+            state["collapse_on_index"] = entry[0]
+        return entry
 
     # -- corpus index: built once per (file signature, model), shared process-wide --------------
     def _embed_texts(self, texts: List[str], model_hint: str, trace_id: str, dim: Optional[int] = None) -> np.ndarray:
@@ -492,6 +518,7 @@ class DenseRetrievalBackend:
         dense_hits: List[Dict[str, Any]] = []
         dense_error = None
         dense_filter = None
+        dense_collapse = None
         k_eff = 0
         with span("Backend/DenseRerank", self.sink, trace_id):      # same span name as :332
             try:
@@ -518,7 +545,13 @@ class DenseRetrievalBackend:
                     k = min(pool, len(state["rows"]))
                     k_eff = min(k, state["index"].max_k(1))
                     allow = self.dense_row_filter(req, state["rows"]) if self.dense_row_filter is not None else None
-                    if allow is None:
+                    if self.dense_collapse is not None:      # the best documents, each by its best row
+                        _, n_keys, m = self._collapse_keys(state)
+                        k_eff = min(pool, n_keys, state["index"].max_k(1))
+                        sc, ids = state["index"].search_collapsed(qv[None, :], k_eff, return_keys=False)
+                        lc = state["index"].last_collapsed()
+                        dense_collapse = {"keys": n_keys, "max_rows_per_key": m, "scan_k": lc["scan_k"], "redone": lc["redone_queries"]}
+                    elif allow is None:
                         sc, ids = state["index"].search(qv[None, :], k_eff)
                     else:
                         sc, ids = state["index"].search(qv[None, :], k_eff, allow=allow)
@@ -558,6 +591,8 @@ class DenseRetrievalBackend:
             diagnostics["dense_mode"] = "rerank"
         if dense_filter is not None:
             diagnostics["dense_filter"] = dense_filter
+        if dense_collapse is not None:
+            diagnostics["dense_collapse"] = dense_collapse
         if expand_error is not None:
             diagnostics["expand_error"] = expand_error
         return {"hits": fused, "diagnostics": diagnostics}
@@ -628,7 +663,10 @@ class DenseRetrievalBackend:
         or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`.  With a ``query_expander``
         every request is expanded first (``Backend/Expand``) and the text channel receives each request's list; with
         ``dense_expanded=True`` the dense channel embeds all of those queries and makes ONE ``DenseIndex.search_groups``
-        call over the unfiltered requests and one per filtered request (``dense_filter_batch`` then has no effect)."""
+        call over the unfiltered requests and one per filtered request (``dense_filter_batch`` then has no effect).
+        With ``dense_collapse`` the dense search is ONE ``DenseIndex.search_collapsed`` over all requests at the list's
+        largest pool -- one hit per document, a prefix per request -- and ``diagnostics["dense_collapse"]`` describes
+        that call."""
         from .index import pack_sets
         from .text_index import HipBM25TextSearcher
         reqs = list(reqs)
@@ -676,6 +714,7 @@ class DenseRetrievalBackend:
         # ---- dense channel: d_ids / d_sc [B][kd], (-1, -inf) where a request has no row
         dense_error: List[Optional[str]] = [None] * B
         dense_filter: List[Any] = [None] * B
+        dense_collapse = None
         k_eff = [0] * B
         state = None
         d_ids = np.full((B, 0), -1, dtype=np.int64)
@@ -775,7 +814,15 @@ class DenseRetrievalBackend:
                     elif plain:
                         try:
                             k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
-                            sc, ids = ix.search(Q[plain] if len(plain) < B else Q, k_batch)
+                            if self.dense_collapse is not None:      # ONE collapsed search at the largest pool, a prefix each
+                                _, n_keys, m = self._collapse_keys(state)
+                                k_batch = min(max(pool[g] for g in plain), n_keys, k_many)
+                                sc, ids = ix.search_collapsed(Q, k_batch, return_keys=False)
+                                lc = ix.last_collapsed()
+                                dense_collapse = {"keys": n_keys, "max_rows_per_key": m, "scan_k": lc["scan_k"],
+                                                  "redone": lc["redone_queries"]}
+                            else:
+                                sc, ids = ix.search(Q[plain] if len(plain) < B else Q, k_batch)
                             for j, g in enumerate(plain):
                                 k_eff[g] = min(pool[g], k_batch)
                                 d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
@@ -868,6 +915,8 @@ class DenseRetrievalBackend:
                 diagnostics["dense_mode"] = "rerank"
             if dense_filter[g] is not None:
                 diagnostics["dense_filter"] = dense_filter[g]
+            if dense_collapse is not None and dense_error[g] is None:
+                diagnostics["dense_collapse"] = dense_collapse
             if expanded[g][1] is not None:
                 diagnostics["expand_error"] = expanded[g][1]
             out.append({"hits": hits, "diagnostics": diagnostics})

@@ -77,7 +77,16 @@ struct BfIndex : Object {
   DevBuf grp_in, grp_ptr, grp_out;
   std::vector<int64_t> grp_host;
   int64_t last_groups[3] = {-1, -1, -1};    // of the last mrag_index_search_groups: queries, questions, entries of the largest question
+  // collapsed search (mrag_index_search_collapsed): the row keys on the device, the rows they were set for (-1 = none),
+  // the largest number of rows that share a key and the distinct keys (counted on the host when the keys are set); round
+  // 0's [nq][scan_k] lists and a redo round's one list (ids | scores each), the redo allow-set bitset, the per-query
+  // {heads, valid} words with their host copy, the [nq][k] results (ids | scores | keys) when the caller's are on the host
+  DevBuf col_keys, col_in, col_redo, col_mask, col_words, col_out;
+  int64_t col_n = -1, col_m = 0, col_distinct = 0;
+  std::vector<int32_t> col_host;
+  int64_t last_collapsed[3] = {-1, -1, -1}; // of the last mrag_index_search_collapsed: scan_k, redone queries, redo searches
   ~BfIndex() override {
+    col_keys.release(); col_in.release(); col_redo.release(); col_mask.release(); col_words.release(); col_out.release();
     grp_in.release(); grp_ptr.release(); grp_out.release();
     sets_q.release(); sets_plan.release(); sets_rows.release(); sets_S.release();
     if (rows) (void)hipFree(rows);
@@ -1143,6 +1152,144 @@ int mrag_index_last_groups(mrag_handle h, int64_t* out_queries, int64_t* out_gro
   if (out_queries) *out_queries = ix->last_groups[0];
   if (out_groups) *out_groups = ix->last_groups[1];
   if (out_max_entries) *out_max_entries = ix->last_groups[2];
+  return MRAG_OK;
+}
+
+int mrag_index_set_row_keys(mrag_handle h, const int32_t* keys, int64_t n, int keys_is_device) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (n < 0) return fail(MRAG_ERR_INVALID, "n < 0");
+  if (n == 0 && !keys) { ix->col_n = -1; ix->col_m = 0; ix->col_distinct = 0; return MRAG_OK; }
+  if (!keys) return fail(MRAG_ERR_INVALID, "keys is NULL");
+  if (n != ix->n) return fail(MRAG_ERR_INVALID, "keys for %lld rows, the index holds %lld", (long long)n, (long long)ix->n);
+  MRAG_TRY(use_device(ix->device));
+  // the host copy: validated, then sorted to count the distinct keys and the longest run
+  std::vector<int32_t> hk((size_t)n);
+  if (n > 0) {
+    if (keys_is_device) MRAG_HIP(hipMemcpy(hk.data(), keys, (size_t)n * 4, hipMemcpyDeviceToHost));
+    else memcpy(hk.data(), keys, (size_t)n * 4);
+  }
+  for (int64_t r = 0; r < n; ++r)
+    if (hk[(size_t)r] < 0) return fail(MRAG_ERR_INVALID, "row %lld has the negative key %d", (long long)r, (int)hk[(size_t)r]);
+  // an earlier collapsed search with device outputs may still read the old keys on the caller's stream
+  MRAG_HIP(hipDeviceSynchronize());
+  MRAG_TRY(ix->col_keys.ensure(std::max<size_t>((size_t)n, 1) * 4));
+  if (n > 0) MRAG_HIP(hipMemcpy(ix->col_keys.p, hk.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  std::sort(hk.begin(), hk.end());
+  int64_t distinct = 0, longest = 0, run = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (r == 0 || hk[(size_t)r] != hk[(size_t)r - 1]) { ++distinct; run = 0; }
+    longest = std::max(longest, ++run);
+  }
+  ix->col_n = n;
+  ix->col_m = longest;
+  ix->col_distinct = distinct;
+  return MRAG_OK;
+}
+
+// The default scan depth of the collapsed search.  With m rows per key at most, the first (k - 1) * m + 1 rows of the
+// declared order hold k keys, so at that depth no query is ever redone; the search serves 256 at most, and a depth beyond
+// the rows (or below k) buys nothing.  Nobody has measured whether this depth or a shallower scan with an occasional redo
+// is faster: tools/perf_search_collapsed.py times both (DESIGN.md §3 "Collapsed search").
+static int collapse_default_scan_k(int k, int64_t m, int64_t n) {
+  const int64_t safe = std::max<int64_t>(k, (int64_t)(k - 1) * m + 1);
+  return (int)std::max<int64_t>(k, std::min<int64_t>(std::min<int64_t>(KMAX_WIDE, n), safe));
+}
+
+int mrag_index_search_collapsed(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                                int k, int scan_k, float* out_scores, int64_t* out_ids, int32_t* out_keys, int out_is_device,
+                                void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_nq_k(nq, k));
+  if (scan_k != 0 && (scan_k < k || scan_k > KMAX_WIDE))
+    return fail(MRAG_ERR_INVALID, "scan_k = %d lies outside [k, %d] = [%d, %d] (0 picks the default)", scan_k, KMAX_WIDE, k, KMAX_WIDE);
+  const int64_t n = ix->n;
+  if (ix->col_n < 0 && n > 0) return fail(MRAG_ERR_INVALID, "no row keys set on this index (mrag_index_set_row_keys)");
+  if (ix->col_n >= 0 && ix->col_n != n)
+    return fail(MRAG_ERR_INVALID, "row keys were set for %lld rows, the index holds %lld: set them again", (long long)ix->col_n, (long long)n);
+  if (nq == 0) return MRAG_OK;
+  if (!queries || !out_scores || !out_ids) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  if (nq > (1ll << 26)) return fail(MRAG_ERR_UNSUPPORTED, "nq too large for one call; batch the queries");
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  ix->last_collapsed[0] = -1;
+  const int scan = scan_k ? scan_k : collapse_default_scan_k(k, ix->col_m, n);
+
+  const size_t n_in = (size_t)nq * scan, n_out = (size_t)nq * k;
+  MRAG_TRY(ix->col_in.ensure(n_in * 12));
+  MRAG_TRY(ix->col_words.ensure((size_t)nq * 8));
+  MRAG_TRY(ix->col_out.ensure(n_out * 16));
+  int64_t* s_id = (int64_t*)ix->col_in.p;
+  float* s_sc = (float*)(s_id + n_in);
+  int32_t* words = (int32_t*)ix->col_words.p;
+  const int32_t* key_of = (const int32_t*)ix->col_keys.p;       // (NULL only over an empty index: no list entry is valid)
+  // the found keys feed the redo masks, so they are kept also when the caller does not ask for them
+  int64_t* d_id = out_is_device ? out_ids : (int64_t*)ix->col_out.p;
+  float* d_sc = out_is_device ? out_scores : (float*)((int64_t*)ix->col_out.p + n_out);
+  int32_t* d_key = out_is_device && out_keys ? out_keys : (int32_t*)((char*)ix->col_out.p + n_out * 12);
+
+  // ---- round 0: one search of all queries at depth `scan`, one collapse launch, the words read back
+  MRAG_TRY(mrag_index_search(h, queries, nq, q_dtype, normalize, queries_is_device, scan, s_sc, s_id, 1, stream_));
+  MRAG_TRY(launch_collapse_heads(s_sc, s_id, nq, scan, key_of, n, ix->id_base, k, 0, 0, words, d_sc, d_id, d_key, stream));
+  ix->col_host.resize((size_t)nq * 2);
+  int32_t* hw = ix->col_host.data();
+  MRAG_HIP(hipMemcpyAsync(hw, words, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
+  MRAG_HIP(hipStreamSynchronize(stream));
+  // incomplete: fewer than k keys, and the list was full (rows may stand behind it)
+  std::vector<int64_t> todo;
+  for (int64_t q = 0; q < nq; ++q)
+    if (hw[2 * q] < k && hw[2 * q + 1] >= scan) todo.push_back(q);
+  const int64_t redone = (int64_t)todo.size();
+  int64_t searches = 0;
+
+  // ---- redo rounds: each incomplete query alone over the rows whose key it has not found; every round adds a key
+  if (redone) {
+    MRAG_TRY(ix->col_redo.ensure((size_t)scan * 12));
+    MRAG_TRY(ix->col_mask.ensure((size_t)collapse_mask_words(n) * 4));
+  }
+  int64_t* r_id = (int64_t*)ix->col_redo.p;
+  float* r_sc = (float*)(r_id + scan);
+  while (!todo.empty()) {
+    for (const int64_t q : todo) {
+      MRAG_TRY(launch_collapse_mask(key_of, n, d_key + (size_t)q * k, words + 2 * q, k, (uint32_t*)ix->col_mask.p, stream));
+      MRAG_TRY(search_allowed(h, (const char*)queries + (size_t)q * ix->dim * esz, 1, q_dtype, normalize, queries_is_device, scan,
+                              nullptr, ix->col_mask.p, n, MRAG_ALLOW_BITS32, 1, MRAG_FILTER_AUTO, r_sc, r_id, nullptr, 1, stream_));
+      MRAG_TRY(launch_collapse_heads(r_sc, r_id, 1, scan, key_of, n, ix->id_base, k, q, 1, words, d_sc, d_id, d_key, stream));
+      ++searches;
+    }
+    MRAG_HIP(hipMemcpyAsync(hw, words, (size_t)nq * 8, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+    std::vector<int64_t> next;
+    for (const int64_t q : todo)
+      if (hw[2 * q] < k && hw[2 * q + 1] >= scan) next.push_back(q);
+    todo.swap(next);
+  }
+
+  if (!out_is_device) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, d_sc, n_out * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipMemcpyAsync(out_ids, d_id, n_out * 8, hipMemcpyDeviceToHost, stream));
+    if (out_keys) MRAG_HIP(hipMemcpyAsync(out_keys, d_key, n_out * 4, hipMemcpyDeviceToHost, stream));
+    MRAG_HIP(hipStreamSynchronize(stream));
+  }
+  ix->last_collapsed[0] = scan;
+  ix->last_collapsed[1] = redone;
+  ix->last_collapsed[2] = searches;
+  return MRAG_OK;
+}
+
+int mrag_index_last_collapsed(mrag_handle h, int* out_scan_k, int64_t* out_redone_queries, int64_t* out_redo_rounds,
+                              int64_t* out_max_rows_per_key, int64_t* out_distinct_keys) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (ix->last_collapsed[0] < 0) return fail(MRAG_ERR_INVALID, "no completed collapsed search on this index");
+  if (out_scan_k) *out_scan_k = (int)ix->last_collapsed[0];
+  if (out_redone_queries) *out_redone_queries = ix->last_collapsed[1];
+  if (out_redo_rounds) *out_redo_rounds = ix->last_collapsed[2];
+  if (out_max_rows_per_key) *out_max_rows_per_key = ix->col_m;
+  if (out_distinct_keys) *out_distinct_keys = ix->col_distinct;
   return MRAG_OK;
 }
 

@@ -137,6 +137,19 @@ constexpr int GROUPS_MAX_ENTRIES = 4096;
 int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
                         float* out_sc, int64_t* out_id, int32_t* out_which, hipStream_t stream);
 
+// The two kernels of mrag_index_search_collapsed (bf_collapse.hip): the heads of sorted search lists (the first entry of
+// every row key, written behind the heads of earlier rounds) with one {heads so far, valid entries} word pair per query,
+// and the allow-set of a redo round (the rows whose key the query has not found yet) as a bitset of
+// collapse_mask_words(n_rows) words.  One thread per list entry bounds a list at COLLAPSE_MAX_SCAN entries (= KMAX_WIDE,
+// the deepest search).  All pointers are device pointers.
+constexpr int COLLAPSE_MAX_SCAN = 256;
+int launch_collapse_heads(const float* in_sc, const int64_t* in_id, int64_t nq, int scan_k, const int32_t* key_of, int64_t n_rows,
+                          int64_t id_base, int k, int64_t q0, int append, int32_t* words, float* out_sc, int64_t* out_id,
+                          int32_t* out_key, hipStream_t stream);
+int64_t collapse_mask_words(int64_t n_rows);
+int launch_collapse_mask(const int32_t* key_of, int64_t n_rows, const int32_t* found, const int32_t* word, int k, uint32_t* bits,
+                         hipStream_t stream);
+
 #if defined(__HIPCC__)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

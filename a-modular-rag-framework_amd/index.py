@@ -152,6 +152,28 @@ def group_ptr_of(group_ptr, sizes, nq: int) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def row_keys_of(values) -> Tuple[np.ndarray, int, int]:
+    """One hashable value per row (a title, a document id, a tenant) -> ``(keys, n_keys, m)``: int32 keys numbered in order
+    of first appearance (the form ``mrag_index_set_row_keys`` takes), the number of distinct keys and the largest number
+    of rows that share one.  No GPU is needed."""
+    seen: dict = {}
+    keys = np.empty(len(values), dtype=np.int32)
+    for r, v in enumerate(values):
+        keys[r] = seen.setdefault(v, len(seen))
+    m = int(np.bincount(keys).max()) if len(keys) else 0
+    return keys, len(seen), m
+
+
+def collapse_scan_k(k: int, m: int, n: int) -> int:
+    """The default scan depth of :meth:`DenseIndex.search_collapsed` for ``k`` keys over ``n`` rows of which at most ``m``
+    share a key: ``min(256, n, max(k, (k - 1) * m + 1))``, never below ``k``.  The first ``(k - 1) * m + 1`` rows of the
+    declared order hold ``k`` keys, so below the 256 cap this depth never needs a redo round.  Nobody has measured
+    whether it, or a shallower scan with an occasional redo, is the faster default (``tools/perf_search_collapsed.py``
+    times both)."""
+    k = _check_k(k, 256)
+    return max(k, min(256, int(n), max(k, (k - 1) * int(m) + 1)))
+
+
 IVF_FILTER_PATHS = {"auto": N.IVF_FILTER_AUTO, "probe": N.IVF_FILTER_PROBE, "exact": N.IVF_FILTER_EXACT}
 _IVF_FILTER_NAMES = {N.IVF_FILTER_PROBE: "probe", N.IVF_FILTER_EXACT: "exact"}
 
@@ -565,6 +587,85 @@ class DenseIndex:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         N.check(self._lib.mrag_index_last_groups(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"queries": a.value, "groups": b.value, "max_entries": c.value}
+
+    def set_row_keys(self, keys):
+        """One int32 key per stored row, ``0 <= key < 2**31`` (``mrag_index_set_row_keys``): a 1-D integer array of
+        ``len(self)`` entries, numpy or a CUDA int32 tensor; :func:`row_keys_of` makes one from any hashable per row.
+        ``None`` clears the keys.  Rows added afterwards have no key: set the keys again before the next
+        :meth:`search_collapsed`."""
+        if keys is None:
+            N.check(self._lib.mrag_index_set_row_keys(self._h, None, 0, 0))
+            return
+        if _is_torch(keys) and keys.is_cuda:
+            import torch
+            if keys.dim() != 1 or keys.dtype != torch.int32:
+                raise ValueError(f"device keys must be a 1-D int32 tensor, got {tuple(keys.shape)} {keys.dtype}")
+            t = keys.contiguous()
+            torch.cuda.current_stream(t.device).synchronize()      # the call copies them back on its own
+            N.check(self._lib.mrag_index_set_row_keys(self._h, t.data_ptr(), t.shape[0], 1))
+            return
+        a = np.asarray(keys.numpy() if _is_torch(keys) else keys)
+        if a.ndim != 1 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+            raise ValueError(f"keys must be 1-D integers, got shape {a.shape} dtype {a.dtype}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 2 ** 31 - 1):
+            raise ValueError(f"keys must lie in [0, 2**31), got [{int(a.min())}, {int(a.max())}]")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        N.check(self._lib.mrag_index_set_row_keys(self._h, a.ctypes.data, a.shape[0], 0))
+
+    def search_collapsed(self, queries, k: int, scan_k: Optional[int] = None, normalize: Optional[bool] = None, stream=None,
+                         out=None, return_keys: bool = True):
+        """:meth:`search` with one hit per row key (``mrag_index_search_collapsed``; :meth:`set_row_keys` first) ->
+        (scores [nq,k] fp32, ids [nq,k] int64, keys [nq,k] int32), without the keys when ``return_keys=False``.
+
+        A key scores what its best row scores and is represented by the first of its rows in (score desc, row asc) order;
+        the result is the top-k keys in that order of their representatives, exactly: hits carry the representative's
+        score and id and the key, slots past the distinct keys are (-inf, -1, -1).  With all keys distinct scores and
+        ids are those of :meth:`search`.  ``1 <= k <= 256``.
+
+        ``scan_k`` (``k .. 256``; None: :func:`collapse_scan_k`) is the depth of the one search that all queries share;
+        a query that did not meet k keys in it is searched again alone, over the rows of the keys it has not found, until
+        it has (:meth:`last_collapsed` counts those).  Host queries give numpy results; CUDA tensors give CUDA tensors
+        written on ``stream`` (default: torch's current stream), and the call waits for that stream at least once either
+        way; ``out=(scores, ids, keys)`` (or ``(scores, ids)`` with ``return_keys=False``) reuses buffers.  Exact
+        precision only; the fp8 scan copy, the sharded indexes and ``IVFFlatIndex`` have no collapsed search."""
+        if normalize is None:
+            normalize = self.metric == "cosine"
+        k = _check_k(k, 256)
+        if scan_k is None:
+            scan = 0
+        else:
+            scan = _check_k(scan_k, 256)
+            if scan < k:
+                raise ValueError(f"scan_k must lie in [k, 256] = [{k}, 256], got {scan_k!r}")
+        keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
+        if out is not None and return_keys and len(out) < 3:
+            raise ValueError("return_keys=True needs out=(scores, ids, keys)")
+        keys = None
+        if out is not None and len(out) > 2:
+            keys = out[2]
+        elif return_keys and is_dev:
+            import torch
+            keys = torch.empty((nq, k), dtype=torch.int32, device=keep.device)
+        elif return_keys:
+            keys = np.empty((nq, k), dtype=np.int32)
+        kptr = None if keys is None else (keys.data_ptr() if is_dev else keys.ctypes.data)
+        norm = int(bool(normalize))
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_index_search_collapsed(self._h, ptr, nq, dt, norm, is_dev, k, scan, sc, ids, kptr, out_dev, st)
+        sc, ids = _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev),
+                              None if out is None else (out[0], out[1]))
+        return (sc, ids, keys) if return_keys else (sc, ids)
+
+    def last_collapsed(self) -> dict:
+        """What the last :meth:`search_collapsed` did (``mrag_index_last_collapsed``): ``{"scan_k": the depth it used,
+        "redone_queries": queries incomplete after the shared search, "redo_rounds": filtered searches run for them in
+        all, "max_rows_per_key", "distinct_keys": of the keys it searched under}``."""
+        a = C.c_int(0)
+        b, c, d, e = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        N.check(self._lib.mrag_index_last_collapsed(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
+        return {"scan_k": a.value, "redone_queries": b.value, "redo_rounds": c.value, "max_rows_per_key": d.value,
+                "distinct_keys": e.value}
 
     def last_fp8(self) -> dict:
         """Refine pool and regime of the last fp8 search on this index (``mrag_index_last_fp8``):

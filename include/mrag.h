@@ -403,5 +403,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 #include "mrag_rerank_batch.h"
 #include "mrag_filter_batch.h"
 #include "mrag_search_groups.h"
+#include "mrag_search_collapsed.h"
 
 #endif /* MRAG_H_ */
