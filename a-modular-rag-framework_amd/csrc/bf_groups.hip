@@ -28,7 +28,7 @@
 //   output     slot r < k: the r-th entry of sort 2 if it is a head, else (-inf, -1, -1)
 // Work per question: O(P log^2 P) compare-exchanges in LDS; global memory is read once and written once.  A question's
 // three outputs depend on its own entries alone (P on its own n; blockDim only shares the work out).
-#include "bf_kernels.h"
+#include "bf_index.h"
 
 namespace mrag {
 
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(1024) void groups_merge_kernel(const float* __restr
 
 // n_groups >= 1 questions of at most max_entries = (largest group) * k <= GROUPS_MAX_ENTRIES entries each; every pointer
 // is a device pointer, in_sc / in_id are the [nq][k] lists of a search, out_which may be NULL
-int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
+static int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
                         float* out_sc, int64_t* out_id, int32_t* out_which, hipStream_t stream) {
   if (max_entries > GROUPS_MAX_ENTRIES) return fail(MRAG_ERR_UNSUPPORTED, "%d entries in one question exceed %d", max_entries, GROUPS_MAX_ENTRIES);
   if (n_groups > 2147483647ll) return fail(MRAG_ERR_UNSUPPORTED, "%lld questions exceed one launch", (long long)n_groups);
@@ -140,4 +140,76 @@ int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t*
   return MRAG_OK;
 }
 
+// group_ptr [n_groups + 1] against the nq queries and k; *q_max = the queries of the largest question
+static int groups_check_ptr(const int64_t* group_ptr, int64_t n_groups, int64_t nq, int k, int64_t* q_max) {
+  MRAG_TRY(check_csr(group_ptr, n_groups, "group_ptr", "question"));
+  if (group_ptr[n_groups] != nq)
+    return fail(MRAG_ERR_INVALID, "group_ptr ends at %lld behind question %lld, not at nq = %lld", (long long)group_ptr[n_groups],
+                (long long)n_groups - 1, (long long)nq);
+  *q_max = 0;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    const int64_t q = group_ptr[g + 1] - group_ptr[g];
+    if (q * k > GROUPS_MAX_ENTRIES)
+      return fail(MRAG_ERR_UNSUPPORTED, "question %lld has %lld queries x k = %d = %lld entries, more than %d", (long long)g, (long long)q,
+                  k, (long long)(q * k), GROUPS_MAX_ENTRIES);
+    *q_max = std::max(*q_max, q);
+  }
+  return MRAG_OK;
+}
+
 }  // namespace mrag
+
+using namespace mrag;
+
+extern "C" {
+
+int mrag_index_search_groups(mrag_handle h, const void* queries, int64_t nq, int q_dtype, int normalize, int queries_is_device,
+                             int k, int64_t n_groups, const int64_t* group_ptr, const void* allow, int64_t allow_rows,
+                             int allow_format, float* out_scores, int64_t* out_ids, int32_t* out_which, int out_is_device,
+                             void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  MRAG_TRY(check_nq_k(nq, k));
+  if (n_groups < 0) return fail(MRAG_ERR_INVALID, "n_groups < 0");
+  if (n_groups == 0 && nq == 0) return MRAG_OK;
+  if (!group_ptr || !out_scores || !out_ids || (nq > 0 && !queries)) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  if (!dtype_size(q_dtype)) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  int64_t q_max = 0;
+  MRAG_TRY(groups_check_ptr(group_ptr, n_groups, nq, k, &q_max));
+  if (allow) MRAG_TRY(check_allow_args(allow_rows, ix->n, allow_format, MRAG_FILTER_AUTO, "filter"));
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  GroupsState& w = ix->groups;
+  w.last.open();
+
+  // ---- one search of all nq queries into index-owned scratch (mrag_index_max_k is 256 for every nq: never cut)
+  ListScratch in;
+  MRAG_TRY(in.bind(w.in, (size_t)nq * k));
+  if (nq > 0) {
+    if (allow)
+      MRAG_TRY(search_allowed(ix, queries, nq, q_dtype, normalize, queries_is_device, k, nullptr, allow, allow_rows, allow_format, 0,
+                              MRAG_FILTER_AUTO, in.scores, in.ids, nullptr, 1, stream));
+    else
+      MRAG_TRY(bf_search(ix, queries, nq, q_dtype, normalize, queries_is_device, k, in.scores, in.ids, 1, stream));
+  }
+
+  // ---- one merge launch, straight into device outputs
+  w.host.assign(group_ptr, group_ptr + n_groups + 1);
+  MRAG_TRY(w.ptr.ensure((size_t)(n_groups + 1) * 8));
+  OutTriple out;
+  MRAG_TRY(out.bind(w.out, (size_t)n_groups * k, out_scores, out_ids, out_which, out_is_device, false));
+  MRAG_HIP(hipMemcpyAsync(w.ptr.p, w.host.data(), (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, stream));
+  MRAG_TRY(launch_groups_merge(in.scores, in.ids, (const int64_t*)w.ptr.p, n_groups, k, (int)(q_max * k), out.scores, out.ids, out.third,
+                               stream));
+  MRAG_TRY(out.copy_back(stream));
+  w.last.close(nq, n_groups, q_max * k);
+  return MRAG_OK;
+}
+
+int mrag_index_last_groups(mrag_handle h, int64_t* out_queries, int64_t* out_groups, int64_t* out_max_entries) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  return ix->groups.last.read("search over grouped queries", out_queries, out_groups, out_max_entries);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// What the dense-index sources (bf_batch, bf_stream, bf_merge, bf_filter, bf_fp8, bf_index) share among themselves: the
+// What the dense-index sources (bf_*.hip) share among themselves: the
 // tile and list constants, the kernel parameter blocks, the orderable-key and LDS helpers, the regime rule and the plain
 // host launchers each source exports.  Internal to those sources; what other translation units use is in common.h.
 #pragma once
@@ -97,58 +97,20 @@ int launch_merge(MergeParams mp, int* flags, int* need, hipStream_t stream);
 // range search (bf_merge.hip): the per-query sums of the count slots of one launch (T query tiles x S splits) -> out[0 .. nq)
 int launch_range_sum(const int* slots, int S, int64_t nq, int64_t* out, hipStream_t stream);
 
-// The batched candidate lookup (bf_rerank_batch.hip).  One workgroup scores one descriptor: entries [first, first + count)
-// of the flat id list, all of question `question`.  64 rows per descriptor: each of the 4 waves amortises the one read of
-// its question's query row over 16 stored rows (6 % extra traffic), the reference's 200-candidate pool still spreads
-// over 4 workgroups, and a 10 000 x 200 batch is 40 000 workgroups -- some 150 per CU, so a tail does not show.
+// ---- limits of the composite searches that tests and documents cite (each search's kernels, launchers and entry points are
+// in its own source) ----
+// bf_rerank_batch.hip: rows per descriptor of the batched candidate lookup.  Each of the 4 waves amortises the one read of its
+// question's query row over 16 stored rows (6 % extra traffic), the reference's 200-candidate pool still spreads over 4
+// workgroups, and a 10 000 x 200 batch is 40 000 workgroups -- some 150 per CU, so a tail does not show.
 constexpr int RERANK_ROWS = 64;
-struct RerankDesc {
-  int64_t question, first;
-  int32_t count, pad;
-};
-// host: the descriptors of row_ptr [n_questions + 1] (validated by the caller), in question order; empty questions get none
-int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<RerankDesc>& desc);
-// out[e] = <queries[question of e], rows[ids[e]]> for every entry the n_desc descriptors cover (0.0 for an id outside
-// [0, n_rows)); prepared queries at pitch ld; one launch per 2^31 - 1 descriptors
-int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const RerankDesc* desc, int64_t n_desc,
-                        const int64_t* ids, int64_t n_rows, float* out, hipStream_t stream);
-
-// The gathered-set scan of mrag_index_search_sets (bf_filter_batch.hip).  One descriptor = one chunk of <= SETS_CHUNK rows
-// of one set x <= SETS_CHUNK of the questions that use it:
-//   [0] first slot in qlist (the questions sorted by set)     [1] questions (<= 128)
-//   [2] first position in set_rows                            [3] rows (<= 128)      [4] index of the first row inside the set
-//   [5],[6] float offset of the first question's score segment (low, high)           [7] segment pitch (floats, % 32 == 0)
-// Slot s of the descriptor writes S[offset + s * pitch + [4] ...]: the questions of a set hold consecutive segments.
-constexpr int SETS_DESC_WORDS = 8;
-constexpr int SETS_CHUNK = 128;
-// Largest set the scan route serves: the register-path capacity of the select kernel (SEL_CAP in ivf_scan.hip, 256 threads
-// x 32 entries).  The project's own constant, not a tuned one: a measured crossover would replace it, with its measurement
-// in DESIGN.md.
+// bf_filter_batch.hip: largest set the scan route of mrag_index_search_sets serves: the register-path capacity of the select
+// kernel (SEL_CAP in ivf_scan.hip, 256 threads x 32 entries).  The project's own constant, not a tuned one: a measured
+// crossover would replace it, with its measurement in DESIGN.md.
 constexpr int SETS_SCAN_MAX_ROWS = 8192;
-// scores of every descriptor's (row, question) pairs -> S; all pointers are device pointers, `zero` is a row of ld zeros
-int launch_sets_scan(const uint16_t* corpus, const uint16_t* queries, const uint16_t* zero, int ld, int dtype, const int* desc,
-                     int n_desc, const int64_t* set_rows, const int* qlist, float* S, hipStream_t stream);
-
-// The grouped max-merge of mrag_index_search_groups (bf_groups.hip): question g owns the search's lists of the queries
-// group_ptr[g] .. group_ptr[g+1); per question the k best distinct ids by their largest score, (score desc, id asc), with
-// the position inside the group of the query that gave it.  One workgroup per question sorts its entries in LDS, which
-// bounds a question at GROUPS_MAX_ENTRIES = queries * k entries (fuse.hip's limit).  All pointers are device pointers.
+// bf_groups.hip: one workgroup per question sorts its queries * k entries in LDS (fuse.hip's limit)
 constexpr int GROUPS_MAX_ENTRIES = 4096;
-int launch_groups_merge(const float* in_sc, const int64_t* in_id, const int64_t* group_ptr, int64_t n_groups, int k, int max_entries,
-                        float* out_sc, int64_t* out_id, int32_t* out_which, hipStream_t stream);
-
-// The two kernels of mrag_index_search_collapsed (bf_collapse.hip): the heads of sorted search lists (the first entry of
-// every row key, written behind the heads of earlier rounds) with one {heads so far, valid entries} word pair per query,
-// and the allow-set of a redo round (the rows whose key the query has not found yet) as a bitset of
-// collapse_mask_words(n_rows) words.  One thread per list entry bounds a list at COLLAPSE_MAX_SCAN entries (= KMAX_WIDE,
-// the deepest search).  All pointers are device pointers.
+// bf_collapse.hip: one thread per list entry bounds a list at this many entries (= KMAX_WIDE, the deepest search)
 constexpr int COLLAPSE_MAX_SCAN = 256;
-int launch_collapse_heads(const float* in_sc, const int64_t* in_id, int64_t nq, int scan_k, const int32_t* key_of, int64_t n_rows,
-                          int64_t id_base, int k, int64_t q0, int append, int32_t* words, float* out_sc, int64_t* out_id,
-                          int32_t* out_key, hipStream_t stream);
-int64_t collapse_mask_words(int64_t n_rows);
-int launch_collapse_mask(const int32_t* key_of, int64_t n_rows, const int32_t* found, const int32_t* word, int k, uint32_t* bits,
-                         hipStream_t stream);
 
 #if defined(__HIPCC__)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

@@ -1,8 +1,8 @@
-// The batched candidate lookup of the dense index (mrag_index_score_rows_batch, include/mrag_rerank_batch.h): the
-// scores of a ragged batch of (question, stored row) pairs in one launch.  The entry point is in bf_index.hip, next to
-// mrag_index_score_rows; here are the host plan that cuts the lists into descriptors and the kernel.
+// The candidate lookups of the dense index: mrag_index_score_rows (one question, score_rows_kernel) and the batched
+// mrag_index_score_rows_batch (include/mrag_rerank_batch.h): the scores of a ragged batch of (question, stored row) pairs
+// in one launch.  Here are both kernels, the host plan that cuts the lists into descriptors and the two entry points.
 //
-// What stays from score_rows_kernel (bf_index.hip), because fp64 accumulation is not order-independent for bf16 rows
+// What stays from score_rows_kernel, because fp64 accumulation is not order-independent for bf16 rows
 // or un-normalised rows and the batch must return the single call's bits: one wave per row, lane l accumulates the
 // exact products of columns l, l + 64, ... in that order in fp64, then the __shfl_xor butterfly at 32 .. 1.
 // What is new is everything around it: one 256-thread workgroup per descriptor (question, first entry, <= 64 entries),
@@ -12,9 +12,38 @@
 //
 // A row is read as 2 bytes per lane per instruction -- one 128-byte line per wave instruction -- which is what the
 // fixed assignment of columns to lanes gives without a transpose through LDS.
-#include "bf_kernels.h"
+#include "bf_index.h"
 
 namespace mrag {
+
+// one wave per listed row: score = <prepared query, stored row> (fp64 accumulation of the exact 16-bit products)
+__global__ __launch_bounds__(256) void score_rows_kernel(const uint16_t* __restrict__ rows, const uint16_t* __restrict__ q, int ld,
+                                                         int is_bf16, const int64_t* __restrict__ ids, int64_t n, int64_t n_rows,
+                                                         float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int64_t r = ids[i];
+  if (r < 0 || r >= n_rows) { if (lane == 0) out[i] = 0.0f; return; }   // unknown row: the reference's 0.0 for an unusable vector
+  const uint16_t* row = rows + (size_t)r * ld;
+  double acc = 0.0;
+  for (int c = lane; c < ld; c += 64) {
+    float a, b;
+    if (is_bf16) { a = __uint_as_float((uint32_t)row[c] << 16); b = __uint_as_float((uint32_t)q[c] << 16); }
+    else { _Float16 ha, hb; __builtin_memcpy(&ha, &row[c], 2); __builtin_memcpy(&hb, &q[c], 2); a = (float)ha; b = (float)hb; }
+    acc += (double)a * (double)b;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  if (lane == 0) out[i] = (float)acc;
+}
+
+// One workgroup of the batch kernel scores one descriptor: entries [first, first + count) of the flat id list, all of
+// question `question`, count <= RERANK_ROWS (bf_kernels.h).
+struct RerankDesc {
+  int64_t question, first;
+  int32_t count, pad;
+};
 
 namespace {
 
@@ -118,7 +147,8 @@ __global__ __launch_bounds__(256) void rerank_batch_kernel(const uint16_t* __res
 
 }  // namespace
 
-int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<RerankDesc>& desc) {
+// the descriptors of row_ptr [n_questions + 1] (validated by the caller), in question order; empty questions get none
+static int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<RerankDesc>& desc) {
   int64_t n_desc = 0;
   for (int64_t g = 0; g < n_questions; ++g) n_desc += (row_ptr[g + 1] - row_ptr[g] + RERANK_ROWS - 1) / RERANK_ROWS;
   try {
@@ -133,7 +163,9 @@ int rerank_batch_plan(int64_t n_questions, const int64_t* row_ptr, std::vector<R
   return MRAG_OK;
 }
 
-int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const RerankDesc* desc, int64_t n_desc,
+// out[e] = <queries[question of e], rows[ids[e]]> for every entry the n_desc descriptors cover (0.0 for an id outside
+// [0, n_rows)); prepared queries at pitch ld; every pointer is a device pointer; one launch per 2^31 - 1 descriptors
+static int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, int is_bf16, const RerankDesc* desc, int64_t n_desc,
                         const int64_t* ids, int64_t n_rows, float* out, hipStream_t stream) {
   if (ld <= 0 || ld % 64) return fail(MRAG_ERR_INVALID, "re-rank batch: row pitch %d is not a positive multiple of 64", ld);
   const bool reg = ld <= RERANK_REG_LD;
@@ -155,3 +187,82 @@ int launch_rerank_batch(const uint16_t* rows, const uint16_t* queries, int ld, i
 }
 
 }  // namespace mrag
+
+using namespace mrag;
+
+extern "C" {
+
+int mrag_index_score_rows(mrag_handle h, const void* query, int q_dtype, int normalize, const int64_t* row_ids, int64_t n,
+                          float* out_scores, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (n < 0) return fail(MRAG_ERR_INVALID, "n < 0");
+  if (n == 0) return MRAG_OK;
+  if (!query || !row_ids || !out_scores) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  // staging: [query src | row ids | scores]; prepared query in qbuf (one row)
+  const size_t qb = round_up((int64_t)(ix->dim * esz), 256), ib = round_up(n * 8, 256), ob = (size_t)n * 4;
+  MRAG_TRY(ix->stage_in.ensure(qb + ib + ob));
+  MRAG_TRY(ix->qbuf.ensure((size_t)(TQ + SQ) * ix->ld * 2));
+  char* st = (char*)ix->stage_in.p;
+  // (the uploads read the caller's host buffers asynchronously)
+  return run_synced(stream, [&]() -> int {
+    MRAG_HIP(hipMemcpyAsync(st, query, (size_t)ix->dim * esz, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(st + qb, row_ids, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    MRAG_TRY(launch_prep_rows(st, q_dtype, 1, ix->dim, ix->qbuf.p, ix->ld, ix->dtype,
+                              normalize && ix->metric == MRAG_METRIC_COSINE, stream));
+    if (ix->qbuf.p == ix->q_cleared_buf) ix->q_dirty_rows = std::max<int64_t>(ix->q_dirty_rows, 1);   // row 0 of the query buffer was written
+    hipLaunchKernelGGL(score_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, ix->rows, (const uint16_t*)ix->qbuf.p,
+                       ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0, (const int64_t*)(st + qb), n, ix->n, (float*)(st + qb + ib));
+    MRAG_HIP(hipGetLastError());
+    MRAG_HIP(hipMemcpyAsync(out_scores, st + qb + ib, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  });
+}
+
+int mrag_index_score_rows_batch(mrag_handle h, const void* queries, int q_dtype, int normalize, int64_t n_questions,
+                                const int64_t* row_ptr, const int64_t* row_ids, float* out_scores, void* stream_) {
+  BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
+  if (!ix) return MRAG_ERR_INVALID;
+  if (n_questions < 0) return fail(MRAG_ERR_INVALID, "n_questions < 0");
+  if (n_questions == 0) return MRAG_OK;
+  if (!row_ptr) return fail(MRAG_ERR_INVALID, "row_ptr is NULL");
+  MRAG_TRY(check_csr(row_ptr, n_questions, "row_ptr", "question"));
+  const int64_t n = row_ptr[n_questions];
+  if (n == 0) return MRAG_OK;                 // a batch of empty questions
+  if (!queries || !row_ids || !out_scores) return fail(MRAG_ERR_INVALID, "NULL buffer");
+  const size_t esz = dtype_size(q_dtype);
+  if (!esz) return fail(MRAG_ERR_INVALID, "unknown query dtype %d", q_dtype);
+  std::vector<RerankDesc> desc;
+  MRAG_TRY(rerank_batch_plan(n_questions, row_ptr, desc));
+  MRAG_TRY(use_device(ix->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  // staging: [query src | descriptors | row ids | scores]; prepared queries in rr_q
+  const size_t qbytes = (size_t)n_questions * ix->dim * esz, dbytes = desc.size() * sizeof(RerankDesc);
+  const size_t qb = round_up((int64_t)qbytes, 256), db = round_up((int64_t)dbytes, 256), ib = round_up(n * 8, 256), ob = (size_t)n * 4;
+  MRAG_TRY(ix->stage_in.ensure(qb + db + ib + ob));
+  MRAG_TRY(ix->rr_q.ensure((size_t)n_questions * ix->ld * 2));
+  if ((n_questions + 3) / 4 > 2147483647ll)   // (out of reach: the two buffers above do not fit any device at this size)
+    return fail(MRAG_ERR_HIP, "row preparation grid for %lld questions outside HIP's limits", (long long)n_questions);
+  char* st = (char*)ix->stage_in.p;
+  // (the uploads read `desc` and the caller's host buffers asynchronously)
+  return run_synced(stream, [&]() -> int {
+    MRAG_HIP(hipMemcpyAsync(st, queries, qbytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(st + qb, desc.data(), dbytes, hipMemcpyHostToDevice, stream));
+    MRAG_HIP(hipMemcpyAsync(st + qb + db, row_ids, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    // the single call's preparation of its one row, for every row (row g's source keeps the 16-byte alignment of row 0
+    // wherever launch_prep_rows asks for it: dim % 8 == 0 there)
+    MRAG_TRY(launch_prep_rows(st, q_dtype, n_questions, ix->dim, ix->rr_q.p, ix->ld, ix->dtype,
+                              normalize && ix->metric == MRAG_METRIC_COSINE, stream));
+    MRAG_TRY(launch_rerank_batch(ix->rows, (const uint16_t*)ix->rr_q.p, ix->ld, ix->dtype == MRAG_BF16 ? 1 : 0,
+                                 (const RerankDesc*)(st + qb), (int64_t)desc.size(), (const int64_t*)(st + qb + db), ix->n,
+                                 (float*)(st + qb + db + ib), stream));
+    MRAG_HIP(hipMemcpyAsync(out_scores, st + qb + db + ib, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  });
+}
+
+}  // extern "C"

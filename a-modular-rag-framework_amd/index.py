@@ -268,6 +268,22 @@ def _run_search(call, queries, nq: int, k: int, is_dev: int, device: int, stream
     return sc, ids
 
 
+def _third_output(out, wanted: bool, name: str, shape, keep, is_dev):
+    """The optional int32 third output (``which`` / ``keys``) of a search -> (array or None, its pointer or None): ``out[2]``
+    when the caller passes three buffers, else a new array beside the queries when it is wanted."""
+    if out is not None and wanted and len(out) < 3:
+        raise ValueError(f"return_{name}=True needs out=(scores, ids, {name})")
+    third = None
+    if out is not None and len(out) > 2:
+        third = out[2]
+    elif wanted and is_dev:
+        import torch
+        third = torch.empty(shape, dtype=torch.int32, device=keep.device)
+    elif wanted:
+        third = np.empty(shape, dtype=np.int32)
+    return third, None if third is None else (third.data_ptr() if is_dev else third.ctypes.data)
+
+
 class DenseIndex:
     """Brute-force cosine (or inner-product) top-k index on one GPU."""
 
@@ -304,6 +320,15 @@ class DenseIndex:
         N.check(self._lib.mrag_index_size(self._h, C.byref(n)))
         return n.value
 
+    def _norm(self, normalize):
+        return int(bool(self.metric == "cosine" if normalize is None else normalize))
+
+    def _last_record(self, fn, *names) -> dict:
+        """the three int64 figures of a ``mrag_index_last_*`` call under ``names``"""
+        v = [C.c_int64(0) for _ in names]
+        N.check(fn(self._h, *[C.byref(x) for x in v]))
+        return {name: x.value for name, x in zip(names, v)}
+
     # -- build ----------------------------------------------------------------------------
     def reserve(self, n_rows: int):
         N.check(self._lib.mrag_index_reserve(self._h, int(n_rows)))
@@ -316,13 +341,12 @@ class DenseIndex:
         """Append rows ([n, dim] numpy / torch, host or device).  ``normalize`` defaults to
         True for the cosine metric; pass False for rows that are already normalised and
         rounded (they are then stored bit-for-bit when their dtype is the storage dtype)."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         keep, ptr, n, dt, is_dev = _as_buffer(rows, self.dim)
         if is_dev and stream is None:
             import torch
             stream = torch.cuda.current_stream(self.device)   # stream-ordered with the producer of `rows`
-        N.check(self._lib.mrag_index_add(self._h, ptr, n, dt, int(bool(normalize)), is_dev, _stream_ptr(stream)))
+        N.check(self._lib.mrag_index_add(self._h, ptr, n, dt, norm, is_dev, _stream_ptr(stream)))
         del keep
 
     def rows(self, row0: int = 0, n: Optional[int] = None) -> np.ndarray:
@@ -359,12 +383,10 @@ class DenseIndex:
         re-scores them exactly against the 16-bit rows: the scores are exact, the row set is approximate (measured
         recall in DESIGN.md).  It does not combine with ``allow``."""
         fp8, r = _check_precision(precision, refine, allow)
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         if allow is not None:
-            return self._search_filtered(queries, k, normalize, stream, out, allow, filter_path)
+            return self._search_filtered(queries, k, norm, stream, out, allow, filter_path)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
-        norm = int(bool(normalize))
         if fp8:
             def call(sc, ids, out_dev, st):
                 return self._lib.mrag_index_search_fp8(self._h, ptr, nq, dt, norm, is_dev, int(k), r, sc, ids, out_dev, st)
@@ -373,7 +395,7 @@ class DenseIndex:
                 return self._lib.mrag_index_search(self._h, ptr, nq, dt, norm, is_dev, int(k), sc, ids, out_dev, st)
         return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev), out)
 
-    def _search_filtered(self, queries, k, normalize, stream, out, allow, filter_path):
+    def _search_filtered(self, queries, k, norm, stream, out, allow, filter_path):
         if filter_path not in FILTER_PATHS:
             raise ValueError(f"filter_path must be one of {sorted(FILTER_PATHS)}, got {filter_path!r}")
         n = len(self)
@@ -382,7 +404,7 @@ class DenseIndex:
         path = FILTER_PATHS[filter_path]
 
         def call(sc, ids, out_dev, st):
-            return self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, int(bool(normalize)), is_dev, int(k), aptr, n, afmt,
+            return self._lib.mrag_index_search_filtered(self._h, ptr, nq, dt, norm, is_dev, int(k), aptr, n, afmt,
                                                         adev, path, sc, ids, out_dev, st)
         return _run_search(call, keep, nq, k, is_dev, self.device, stream, bool(is_dev or adev), out)
 
@@ -406,8 +428,7 @@ class DenseIndex:
         k = _check_k(k, self.max_k())
         if filter_path not in FILTER_PATHS:
             raise ValueError(f"filter_path must be one of {sorted(FILTER_PATHS)}, got {filter_path!r}")
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         n, akeep, aptr, afmt, adev = 0, None, None, N.ALLOW_BITS32, 0
         if allow is not None:
             n = len(self)
@@ -421,7 +442,6 @@ class DenseIndex:
         else:
             counts = np.empty(nq, dtype=np.int64)
         path = FILTER_PATHS[filter_path]
-        norm = int(bool(normalize))
 
         def call(sc, ids, out_dev, st):
             cptr = counts.data_ptr() if out_dev else counts.ctypes.data
@@ -499,8 +519,7 @@ class DenseIndex:
         set's rows, (score desc, row asc), (-inf, -1) past the set's size.  Sets of up to 8 192 rows are gathered and
         scored by one scan launch for the whole batch; a larger set is one filtered search over all of its questions
         (:meth:`last_sets`, :meth:`last_filter`).  Host queries only."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         k = _check_k(k, 256)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         if is_dev:
@@ -519,7 +538,7 @@ class DenseIndex:
         so = np.ascontiguousarray(so, dtype=np.int32)
         sc = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        N.check(self._lib.mrag_index_search_sets(self._h, ptr, nq, dt, int(bool(normalize)), k, n_sets, set_ptr.ctypes.data,
+        N.check(self._lib.mrag_index_search_sets(self._h, ptr, nq, dt, norm, k, n_sets, set_ptr.ctypes.data,
                                                  set_rows.ctypes.data, so.ctypes.data, sc.ctypes.data, ids.ctypes.data, None))
         del keep
         return sc, ids
@@ -527,9 +546,7 @@ class DenseIndex:
     def last_sets(self) -> dict:
         """What the last :meth:`search_sets` did (``mrag_index_last_sets``): ``{"scanned": questions served by the scan,
         "routed": questions served by filtered searches, "descriptors": scan descriptors launched}``."""
-        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        N.check(self._lib.mrag_index_last_sets(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return {"scanned": a.value, "routed": b.value, "descriptors": c.value}
+        return self._last_record(self._lib.mrag_index_last_sets, "scanned", "routed", "descriptors")
 
     def search_groups(self, queries, k: int, group_ptr=None, sizes=None, allow=None, normalize: Optional[bool] = None,
                       stream=None, out=None, return_which: bool = False):
@@ -549,8 +566,7 @@ class DenseIndex:
         stream); ``out=(scores, ids)`` or ``(scores, ids, which)`` reuses buffers.  ``allow`` is one allow-set for the
         whole call, as in :meth:`search` (packed on the host).  :meth:`last_groups` tells what the call did.  Exact
         precision only; the fp8 scan copy, the sharded indexes and ``IVFFlatIndex`` have no grouped search."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         k = _check_k(k, 256)
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
         gp = group_ptr_of(group_ptr, sizes, nq)
@@ -560,18 +576,7 @@ class DenseIndex:
             n = len(self)
             abits = np.ascontiguousarray(allow_bits(allow, n))
             aptr = abits.ctypes.data
-        if out is not None and return_which and len(out) < 3:
-            raise ValueError("return_which=True needs out=(scores, ids, which)")
-        which = None
-        if out is not None and len(out) > 2:
-            which = out[2]
-        elif return_which and is_dev:
-            import torch
-            which = torch.empty((n_groups, k), dtype=torch.int32, device=keep.device)
-        elif return_which:
-            which = np.empty((n_groups, k), dtype=np.int32)
-        wptr = None if which is None else (which.data_ptr() if is_dev else which.ctypes.data)
-        norm = int(bool(normalize))
+        which, wptr = _third_output(out, return_which, "which", (n_groups, k), keep, is_dev)
 
         def call(sc, ids, out_dev, st):
             return self._lib.mrag_index_search_groups(self._h, ptr, nq, dt, norm, is_dev, k, n_groups, gp.ctypes.data, aptr, n,
@@ -584,9 +589,7 @@ class DenseIndex:
     def last_groups(self) -> dict:
         """What the last :meth:`search_groups` did (``mrag_index_last_groups``): ``{"queries": query vectors searched,
         "groups": questions merged, "max_entries": queries x k of the largest question}``."""
-        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        N.check(self._lib.mrag_index_last_groups(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return {"queries": a.value, "groups": b.value, "max_entries": c.value}
+        return self._last_record(self._lib.mrag_index_last_groups, "queries", "groups", "max_entries")
 
     def set_row_keys(self, keys):
         """One int32 key per stored row, ``0 <= key < 2**31`` (``mrag_index_set_row_keys``): a 1-D integer array of
@@ -628,8 +631,7 @@ class DenseIndex:
         written on ``stream`` (default: torch's current stream), and the call waits for that stream at least once either
         way; ``out=(scores, ids, keys)`` (or ``(scores, ids)`` with ``return_keys=False``) reuses buffers.  Exact
         precision only; the fp8 scan copy, the sharded indexes and ``IVFFlatIndex`` have no collapsed search."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         k = _check_k(k, 256)
         if scan_k is None:
             scan = 0
@@ -638,18 +640,7 @@ class DenseIndex:
             if scan < k:
                 raise ValueError(f"scan_k must lie in [k, 256] = [{k}, 256], got {scan_k!r}")
         keep, ptr, nq, dt, is_dev = _as_buffer(queries, self.dim)
-        if out is not None and return_keys and len(out) < 3:
-            raise ValueError("return_keys=True needs out=(scores, ids, keys)")
-        keys = None
-        if out is not None and len(out) > 2:
-            keys = out[2]
-        elif return_keys and is_dev:
-            import torch
-            keys = torch.empty((nq, k), dtype=torch.int32, device=keep.device)
-        elif return_keys:
-            keys = np.empty((nq, k), dtype=np.int32)
-        kptr = None if keys is None else (keys.data_ptr() if is_dev else keys.ctypes.data)
-        norm = int(bool(normalize))
+        keys, kptr = _third_output(out, return_keys, "keys", (nq, k), keep, is_dev)
 
         def call(sc, ids, out_dev, st):
             return self._lib.mrag_index_search_collapsed(self._h, ptr, nq, dt, norm, is_dev, k, scan, sc, ids, kptr, out_dev, st)
@@ -690,14 +681,13 @@ class DenseIndex:
     def score_rows(self, query, row_ids, normalize: Optional[bool] = None) -> np.ndarray:
         """<query, stored row i> for every listed row (``mrag_index_score_rows``): the re-ranker's
         candidate lookup by row id.  Ids outside the index score 0.0."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         q = np.ascontiguousarray(np.asarray(query, dtype=np.float32).reshape(-1))
         if q.shape[0] != self.dim:
             raise ValueError(f"query has dim {q.shape[0]}, index has {self.dim}")
         ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
         out = np.empty(ids.shape[0], dtype=np.float32)
-        N.check(self._lib.mrag_index_score_rows(self._h, q.ctypes.data, N.MRAG_F32, int(bool(normalize)), ids.ctypes.data,
+        N.check(self._lib.mrag_index_score_rows(self._h, q.ctypes.data, N.MRAG_F32, norm, ids.ctypes.data,
                                                 ids.shape[0], out.ctypes.data, None))
         return out
 
@@ -706,8 +696,7 @@ class DenseIndex:
         ``[nq, dim]``, ``row_ids`` either a sequence of nq int arrays -- the result is then a list of nq float32 arrays --
         or a pair ``(row_ptr int64 [nq + 1], flat_ids)`` -- the result is then ``(row_ptr, flat_scores)``.  Question g's
         scores are bit for bit ``score_rows(queries[g], ids of g)``.  No library call for nq = 0 or no entries."""
-        if normalize is None:
-            normalize = self.metric == "cosine"
+        norm = self._norm(normalize)
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
         if q.ndim == 1 and q.shape[0] == 0:
             q = q.reshape(0, self.dim)
@@ -731,7 +720,7 @@ class DenseIndex:
             ids = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros(0, dtype=np.int64)
         out = np.empty(ids.shape[0], dtype=np.float32)
         if nq and ids.shape[0]:
-            N.check(self._lib.mrag_index_score_rows_batch(self._h, q.ctypes.data, N.MRAG_F32, int(bool(normalize)), nq,
+            N.check(self._lib.mrag_index_score_rows_batch(self._h, q.ctypes.data, N.MRAG_F32, norm, nq,
                                                           ptr.ctypes.data, ids.ctypes.data, out.ctypes.data, None))
         if csr:
             return ptr, out
