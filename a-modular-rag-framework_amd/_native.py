@@ -1,6 +1,6 @@
 """ctypes binding of libmrag_hip.so (include/mrag.h, include/mrag_bm25_batch.h, include/mrag_fuse_batch.h,
 include/mrag_rerank_batch.h, include/mrag_filter_batch.h, include/mrag_search_groups.h,
-include/mrag_search_collapsed.h).  There is no CPU fallback: a missing
+include/mrag_search_collapsed.h, include/mrag_neighbors.h).  There is no CPU fallback: a missing
 library or a missing GPU raises."""
 from __future__ import annotations
 
@@ -152,6 +152,12 @@ SEARCH_COLLAPSED_SIGNATURES = {
     "mrag_index_last_collapsed": [_h, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
 }
 
+# include/mrag_neighbors.h
+NEIGHBORS_SIGNATURES = {
+    "mrag_index_expand_neighbors": [_h, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "mrag_index_last_neighbors": [_h, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+}
+
 
 def load():
     """dlopen the library once and declare every entry point."""
@@ -173,7 +179,7 @@ def load():
     lib = C.CDLL(str(p))
     for name, argtypes in {**SIGNATURES, **EXTENSION_SIGNATURES, **FUSE_BATCH_SIGNATURES, **RERANK_BATCH_SIGNATURES,
                            **FILTER_BATCH_SIGNATURES, **SEARCH_GROUPS_SIGNATURES,
-                           **SEARCH_COLLAPSED_SIGNATURES}.items():
+                           **SEARCH_COLLAPSED_SIGNATURES, **NEIGHBORS_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError = ABI drift, surface it
         fn.argtypes = argtypes
         fn.restype = C.c_char_p if name == "mrag_last_error" else C.c_int

@@ -15,7 +15,9 @@ injected when declared).
                           with the reference's hit shape and fused with the reference's
                           min-max + alpha rule.  ``dense_mode="rerank"``: the dense channel
                           scores the text channel's candidates (the reference's step 4, :332-334)
-                          instead of searching the corpus.
+                          instead of searching the corpus.  ``graph_channel="neighbors"``:
+                          the graph channel on the device, the sentences around the leading
+                          dense hits inside their documents (``DenseIndex.expand_neighbors``).
 """
 from __future__ import annotations
 
@@ -239,7 +241,9 @@ class DenseRetrievalBackend:
                  fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
                  dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False,
                  query_expander: Optional[Any] = None, dense_expanded: bool = False,
-                 dense_collapse: Optional[Any] = None):
+                 dense_collapse: Optional[Any] = None,
+                 graph_channel: Optional[str] = None, graph_window: int = 2, graph_seed_k: Optional[int] = None,
+                 graph_doc: Any = "title"):
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
@@ -302,21 +306,74 @@ class DenseRetrievalBackend:
         if dense_collapse is not None and (dense_mode == "rerank" or dense_row_filter is not None or self.dense_expanded):
             raise ValueError("dense_collapse does not combine with dense_mode='rerank', dense_row_filter or dense_expanded=True")
         self.dense_collapse = dense_collapse
+        # graph_channel="neighbors": the reference's graph channel (retrieval_backend.py:134-182, graph_utils.py:58-129)
+        # over the corpus rows, on the device (DenseIndex.expand_neighbors): the sentences within graph_window rows of the
+        # request's leading graph_seed_k dense hits (None: its top_k), inside their own document.  graph_doc names every
+        # row's document like dense_collapse does (a row field, a callable or a "pkg.mod:func" string); the index holds ONE
+        # key array, so with dense_collapse both must name the same keys
+        if graph_channel not in (None, "neighbors"):
+            raise ValueError(f"unknown graph_channel {graph_channel!r} (supported: 'neighbors')")
+        if graph_channel is not None and graph_expand is not None:
+            raise ValueError("graph_channel and an injected graph_expand both fill the graph channel: give one")
+        if graph_channel is not None and dense_mode == "rerank":
+            raise ValueError("graph_channel seeds from the corpus-wide dense search: it does not combine with dense_mode='rerank'")
+        if isinstance(graph_doc, str) and ":" in graph_doc:
+            from .adapter import import_from_string
+            graph_doc = import_from_string(graph_doc)
+        if not isinstance(graph_doc, str) and not callable(graph_doc):
+            raise TypeError(f"graph_doc must be a row field name, a callable or a 'pkg.mod:func' string, got {type(graph_doc)}")
+        if graph_channel is not None and dense_collapse is not None and graph_doc != dense_collapse:
+            raise ValueError("graph_doc and dense_collapse must name the same row keys: the index holds one key array")
+        if isinstance(graph_window, bool) or not isinstance(graph_window, int) or graph_window < 0:
+            raise ValueError(f"graph_window must be a non-negative integer, got {graph_window!r}")
+        if graph_seed_k is not None and (isinstance(graph_seed_k, bool) or not isinstance(graph_seed_k, int) or graph_seed_k < 1):
+            raise ValueError(f"graph_seed_k must be a positive integer or None, got {graph_seed_k!r}")
+        self.graph_channel, self.graph_window, self.graph_seed_k, self.graph_doc = graph_channel, graph_window, graph_seed_k, graph_doc
         self._state = None
 
-    def _collapse_keys(self, state):
-        """The row keys of ``dense_collapse`` over the state's rows -> ``(keys, distinct keys, max rows per key)``: built
-        once per state and per ``dense_collapse`` value, and set on the (shared) index unless it already holds that array."""
+    def _row_keys(self, state, by):
+        """The row keys ``by`` (a row field or a callable) gives the state's rows -> ``(keys, distinct keys, max rows per
+        key)``: built once per state and per ``by``, and set on the (shared) index unless it already holds that array."""
         from .index import row_keys_of
         made = state.setdefault("collapse_keys", {})
-        if self.dense_collapse not in made:
-            by = self.dense_collapse
+        if by not in made:
             made[by] = row_keys_of([by(r) if callable(by) else r.get(by) for r in state["rows"]])
-        entry = made[self.dense_collapse]
+        entry = made[by]
         if state.get("collapse_on_index") is not entry[0]:
             state["index"].set_row_keys(entry[0])
             state["collapse_on_index"] = entry[0]
         return entry
+
+    def _collapse_keys(self, state):
+        """:meth:`_row_keys` of ``dense_collapse``"""
+        return self._row_keys(state, self.dense_collapse)
+
+    # -- graph_channel="neighbors" ------------------------------------------------------------------------------------------
+    def _graph_window_of(self, req) -> int:
+        """the request's own integer ``graph_window``, else the backend's (retrieval_backend.py:318-324, :156)"""
+        gw = getattr(req, "graph_window", None)
+        return max(0, int(gw if isinstance(gw, int) else self.graph_window))
+
+    def _graph_seeds_of(self, top_k: int, window: int) -> int:
+        """how many leading dense hits seed the expansion: ``graph_seed_k`` or the request's ``top_k``, inside the call's limits"""
+        k = top_k if self.graph_seed_k is None else self.graph_seed_k
+        return max(0, min(int(k), 256, 4096 // (2 * window + 1)))
+
+    def _graph_expand_rows(self, state, seeds: np.ndarray, window: int, m: int):
+        """ONE ``expand_neighbors`` call over the seed rows [n, s] -> (ids [n, m], dist [n, m]) under ``graph_doc``'s keys"""
+        self._row_keys(state, self.graph_doc)
+        _, ids, dist, _ = state["index"].expand_neighbors(np.ascontiguousarray(seeds, dtype=np.int64), window, m=m, return_from=True)
+        return ids, dist
+
+    @staticmethod
+    def _graph_hits(rows, ids, dist, window: int) -> List[Dict[str, Any]]:
+        """one result row of the expansion as the graph channel's hits (retrieval_backend.py:168-175): the score is the
+        reference's own fp64 decay value of the distance, the meta the row's plus ``distance``"""
+        from .index import reference_decay
+        decay = reference_decay(window)
+        return [{"id": _fusion.raw_hit_id(rows[i]), "score": float(decay[d]),
+                 "meta": dict(_fusion.row_meta(rows[i], "graph"), distance=int(d))}
+                for i, d in zip(np.asarray(ids).tolist(), np.asarray(dist).tolist()) if i >= 0]
 
     # -- corpus index: built once per (file signature, model), shared process-wide --------------
     def _embed_texts(self, texts: List[str], model_hint: str, trace_id: str, dim: Optional[int] = None) -> np.ndarray:
@@ -519,6 +576,8 @@ class DenseRetrievalBackend:
         dense_error = None
         dense_filter = None
         dense_collapse = None
+        dense_rows = None                                # the dense list's row ids, the seeds of graph_channel="neighbors"
+        state = None
         k_eff = 0
         with span("Backend/DenseRerank", self.sink, trace_id):      # same span name as :332
             try:
@@ -535,6 +594,7 @@ class DenseRetrievalBackend:
                     if allow is not None:
                         dense_filter = state["index"].last_filter()
                     dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
+                    dense_rows = ids[0]
                 elif state is not None and state["index"] is not None:
                     qv = np.asarray(_vectors(self.router.embed(model_hint=model_hint, texts=[req.query],
                                                                require={"trace_id": trace_id}))[0], dtype=np.float32)
@@ -557,9 +617,30 @@ class DenseRetrievalBackend:
                         sc, ids = state["index"].search(qv[None, :], k_eff, allow=allow)
                         dense_filter = state["index"].last_filter()
                     dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
+                    dense_rows = ids[0]
             except Exception as e:     # reference policy: degrade, never raise out of run() (:229-231)
                 dense_error = repr(e)
                 logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+
+        # the device graph channel: the neighbours of the leading dense hits inside their documents (after the dense search,
+        # which gives the seeds; the reference's step 3, retrieval_backend.py:317-329)
+        graph_error = None
+        graph_info = None
+        if self.graph_channel is not None:
+            window = self._graph_window_of(req)
+            with span("Backend/GraphExpand", self.sink, trace_id):
+                try:
+                    if dense_error is not None:
+                        raise RuntimeError(f"no seeds, the dense channel failed: {dense_error}")
+                    n_seeds = min(self._graph_seeds_of(top_k, window), len(dense_rows)) if dense_rows is not None else 0
+                    if n_seeds > 0:
+                        g_ids, g_dist = self._graph_expand_rows(state, np.asarray(dense_rows[:n_seeds])[None, :], window, min(pool, 4096))
+                        g_hits = self._graph_hits(state["rows"], g_ids[0], g_dist[0], window)
+                    graph_info = {"seeds": n_seeds, "window": window, "max_entries": n_seeds * (2 * window + 1)}
+                except Exception as e:
+                    graph_error = repr(e)
+                    g_hits = []
+                    logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
 
         # dense hits double as candidates (their meta gives the normalised id); scores fused per :350-372
         dense_norm_hits = _fusion.dedupe_by_norm_id(dense_hits)
@@ -595,6 +676,12 @@ class DenseRetrievalBackend:
             diagnostics["dense_collapse"] = dense_collapse
         if expand_error is not None:
             diagnostics["expand_error"] = expand_error
+        if self.graph_channel is not None:
+            diagnostics["graph_window_used"] = window
+            if graph_info is not None:
+                diagnostics["graph_channel"] = graph_info
+            if graph_error is not None:
+                diagnostics["graph_error"] = graph_error
         return {"hits": fused, "diagnostics": diagnostics}
 
     @staticmethod
@@ -666,7 +753,9 @@ class DenseRetrievalBackend:
         call over the unfiltered requests and one per filtered request (``dense_filter_batch`` then has no effect).
         With ``dense_collapse`` the dense search is ONE ``DenseIndex.search_collapsed`` over all requests at the list's
         largest pool -- one hit per document, a prefix per request -- and ``diagnostics["dense_collapse"]`` describes
-        that call."""
+        that call.  With ``graph_channel="neighbors"`` the graph channel is ONE ``DenseIndex.expand_neighbors`` call per
+        distinct ``graph_window`` of the list (normally one) over every request's leading dense hits, and the array
+        path carries its rows into the fusion launch."""
         from .index import pack_sets
         from .text_index import HipBM25TextSearcher
         reqs = list(reqs)
@@ -837,6 +926,44 @@ class DenseRetrievalBackend:
                 d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
                 logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
 
+        # ---- device graph channel: ONE expand_neighbors call per distinct window of the batch (normally one); a request's
+        # seed row is padded with -1 beyond its own seeds, which changes nothing of its result
+        graph_on = self.graph_channel is not None
+        g_win = [self._graph_window_of(r) for r in reqs] if graph_on else [0] * B
+        g_error: List[Optional[str]] = [None] * B
+        g_info: List[Any] = [None] * B
+        g_n = np.zeros(B, dtype=np.int64)                # graph hits per request: the leading slots of g_rows / g_dist
+        g_rows = np.full((B, min(pool_max, 4096) if graph_on else 0), -1, dtype=np.int64)
+        g_dist = np.full(g_rows.shape, -1, dtype=np.int32)
+        if graph_on:
+            with span("Backend/GraphExpand", self.sink, trace[0]):
+                have = state is not None and state["index"] is not None and d_ids.shape[1] > 0
+                n_seeds = [0] * B
+                for g in range(B):
+                    if dense_error[g] is not None:
+                        g_error[g] = repr(RuntimeError(f"no seeds, the dense channel failed: {dense_error[g]}"))
+                    elif have:
+                        n_seeds[g] = min(self._graph_seeds_of(top_k[g], g_win[g]), k_eff[g])
+                for w in sorted({g_win[g] for g in range(B) if n_seeds[g] > 0}):
+                    grp = [g for g in range(B) if n_seeds[g] > 0 and g_win[g] == w]
+                    try:
+                        seeds = np.full((len(grp), max(n_seeds[g] for g in grp)), -1, dtype=np.int64)
+                        for j, g in enumerate(grp):
+                            seeds[j, :n_seeds[g]] = d_ids[g, :n_seeds[g]]
+                        ids, dist = self._graph_expand_rows(state, seeds, w, min(max(pool[g] for g in grp), 4096))
+                        for j, g in enumerate(grp):
+                            c = min(pool[g], 4096)       # the request's own m: a prefix of the call's (strict declared order)
+                            g_rows[g, :c], g_dist[g, :c] = ids[j, :c], dist[j, :c]
+                            g_n[g] = int((ids[j, :c] >= 0).sum())
+                    except Exception as e:
+                        for g in grp:
+                            g_error[g] = repr(e)
+                            g_rows[g], g_dist[g], g_n[g] = -1, -1, 0
+                        logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
+                for g in range(B):
+                    if g_error[g] is None:
+                        g_info[g] = {"seeds": n_seeds[g], "window": g_win[g], "max_entries": n_seeds[g] * (2 * g_win[g] + 1)}
+
         alphas = dict(alpha_text=self.alpha_text, alpha_graph=self.alpha_graph, alpha_dense=self.alpha_dense)
         fast = (own and self.graph_expand is None and state is not None and state["index"] is not None
                 and (t_arrays is None or len(self.text_search.index.docs) == len(state["rows"])))
@@ -844,8 +971,15 @@ class DenseRetrievalBackend:
             norm_keys, sorted_ids = self._norm_keys(state)
             if t_arrays is None:
                 t_arrays = (np.full((B, 0), -1, dtype=np.int64), np.zeros((B, 0), dtype=np.float64), np.zeros(B, dtype=np.int32))
+            graph_arrays = {}
+            if graph_on:                                 # the reference's own fp64 decay values, looked up by distance
+                from .index import reference_decay
+                g_sc = np.zeros(g_rows.shape, dtype=np.float64)
+                for g in range(B):
+                    g_sc[g, :g_n[g]] = reference_decay(g_win[g])[g_dist[g, :g_n[g]]]
+                graph_arrays = dict(graph_rows=g_rows, graph_scores=g_sc, graph_n=g_n)
             chan_ptr, keys, scores, payload = _fusion.batch_entries(t_arrays[0], t_arrays[1], t_arrays[2], d_ids, d_sc, norm_keys,
-                                                                    pool=pool)
+                                                                    pool=pool, **graph_arrays)
             sizes = chan_ptr[3::3] - chan_ptr[0:-1:3]
             fast = int(sizes.max()) <= _fusion.FUSE_MAX_ENTRIES
         results = []
@@ -855,9 +989,12 @@ class DenseRetrievalBackend:
                                                                               device=self.device, **alphas)
             for g in range(B):
                 hits = []
+                dist_of = dict(zip(g_rows[g, :g_n[g]].tolist(), g_dist[g, :g_n[g]].tolist())) if g_n[g] else {}
                 for i in range(int(n_out[g])):
-                    rt, rd = int(op[g, i, 0]), int(op[g, i, 2])
+                    rt, rg, rd = int(op[g, i, 0]), int(op[g, i, 1]), int(op[g, i, 2])
                     meta = _fusion.row_meta(rows[rt], "bm25") if rt >= 0 else {}
+                    if rg >= 0:                                    # the graph meta overlays the text meta, as fuse_channels does
+                        meta.update(_fusion.row_meta(rows[rg], "graph"), distance=dist_of[rg])
                     if not meta.get("text") and rd >= 0:           # dense-only ids carry their own meta
                         meta = _fusion.row_meta(rows[rd], "dense")
                     meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[g, i]), float(ng[g, i]), float(nd[g, i])
@@ -872,6 +1009,8 @@ class DenseRetrievalBackend:
                     t_hits[g] = self.text_search._hits(list(zip(dl[g][:c], sl[g][:c])))
             dense_norm, questions = [], []
             for g in range(B):
+                if g_n[g]:
+                    g_hits[g] = self._graph_hits(state["rows"], g_rows[g, :g_n[g]], g_dist[g, :g_n[g]], g_win[g])
                 dense_hits = []
                 if rr_hits is not None:
                     dense_hits = rr_hits[g]
@@ -901,7 +1040,7 @@ class DenseRetrievalBackend:
             diagnostics = {
                 "queries": queries[g],
                 "bm25_candidates": n_text,
-                "graph_candidates": len(g_hits[g]),
+                "graph_candidates": int(g_n[g]) if graph_on else len(g_hits[g]),
                 "dense_scored": n_dense,
                 "weights": dict(alphas),
                 "pool": {"dense_pool_k": self.dense_pool_k, "final_top_k": top_k[g], "dense_pool_k_effective": k_eff[g]},
@@ -919,6 +1058,12 @@ class DenseRetrievalBackend:
                 diagnostics["dense_collapse"] = dense_collapse
             if expanded[g][1] is not None:
                 diagnostics["expand_error"] = expanded[g][1]
+            if graph_on:
+                diagnostics["graph_window_used"] = g_win[g]
+                if g_info[g] is not None:
+                    diagnostics["graph_channel"] = g_info[g]
+                if g_error[g] is not None:
+                    diagnostics["graph_error"] = g_error[g]
             out.append({"hits": hits, "diagnostics": diagnostics})
         return out
 

@@ -34,26 +34,9 @@ namespace mrag {
 
 static_assert(15 * GROUPS_MAX_ENTRIES <= 65536, "the grouped merge stays inside the default dynamic-LDS limit");
 
-__host__ __device__ inline int groups_pow2(int n) {
-  int p = 2;
-  while (p < n) p <<= 1;
-  return p;
-}
 static inline size_t groups_lds_bytes(int P) { return (size_t)15 * P; }
 
-// bitonic sort of perm[0 .. P) (P a power of two, distinct elements) under a strict total order; ends on a barrier
-template <class Less>
-__device__ inline void groups_sort(unsigned short* perm, int P, Less less) {
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
-        const unsigned short a = perm[i], b = perm[l];
-        if (less((int)b, (int)a) == ((i & k) == 0)) { perm[i] = b; perm[l] = a; }
-      }
-      __syncthreads();
-    }
-}
+// (groups_pow2 and groups_sort, which bf_neighbors.hip uses too, are in bf_kernels.h)
 
 __global__ __launch_bounds__(1024) void groups_merge_kernel(const float* __restrict__ in_sc, const int64_t* __restrict__ in_id,
                                                             const int64_t* __restrict__ group_ptr, int k,

@@ -151,6 +151,15 @@ struct GroupsState {
   ~GroupsState() { in.release(); ptr.release(); out.release(); }
 };
 
+// neighbour expansion (mrag_index_expand_neighbors, bf_neighbors.hip); its row keys are CollapseState's
+struct NeighborsState {
+  DevBuf seeds;                 // host seeds on the device
+  DevBuf out;                   // the rows of a call with host outputs (ids | scores | dist | seed) ...
+  std::vector<char> host;       // ... and their host copy, downloaded in one piece
+  LastCall last;                // questions, entries of the largest question, window
+  ~NeighborsState() { seeds.release(); out.release(); }
+};
+
 // collapsed search (mrag_index_search_collapsed, bf_collapse.hip)
 struct CollapseState {
   DevBuf keys;                            // the row keys on the device
@@ -188,6 +197,7 @@ struct BfIndex : Object {
                                             // bookkeeping (q_cleared_*, q_dirty_rows) a 10 000-question re-rank must not disturb
   SetsState sets;
   GroupsState groups;
+  NeighborsState neighbors;
   CollapseState collapse;
   ~BfIndex() override {
     if (rows) (void)hipFree(rows);

@@ -111,8 +111,35 @@ constexpr int SETS_SCAN_MAX_ROWS = 8192;
 constexpr int GROUPS_MAX_ENTRIES = 4096;
 // bf_collapse.hip: one thread per list entry bounds a list at this many entries (= KMAX_WIDE, the deepest search)
 constexpr int COLLAPSE_MAX_SCAN = 256;
+// bf_neighbors.hip: one workgroup per question sorts its seeds * (2 * window + 1) entries in LDS, one thread per seed walks
+// the keys; the distance and the seed position of an entry share 16 bits (5 + 8)
+constexpr int NEIGHBORS_MAX_ENTRIES = 4096;
+constexpr int NEIGHBORS_MAX_SEEDS = 256;
+constexpr int NEIGHBORS_MAX_WINDOW = 16;
+constexpr int NEIGHBORS_MAX_M = 4096;
+
+// the padded size of a question that one workgroup sorts in LDS (bf_groups.hip, bf_neighbors.hip): the power of two >= n, >= 2
+__host__ __device__ inline int groups_pow2(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
 
 #if defined(__HIPCC__)
+// bitonic sort of perm[0 .. P) (P a power of two, distinct elements) under a strict total order; ends on a barrier
+template <class Less>
+__device__ inline void groups_sort(unsigned short* perm, int P, Less less) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+        const unsigned short a = perm[i], b = perm[l];
+        if (less((int)b, (int)a) == ((i & k) == 0)) { perm[i] = b; perm[l] = a; }
+      }
+      __syncthreads();
+    }
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -175,18 +175,24 @@ def corpus_norm_keys(rows: Sequence[Dict[str, Any]]):
     return np.asarray([rank[nid] for nid in nids], dtype=np.int32).reshape(-1), sorted_ids
 
 
-def batch_entries(text_docs, text_scores, text_n, dense_ids, dense_scores, norm_keys, pool=None):
+def batch_entries(text_docs, text_scores, text_n, dense_ids, dense_scores, norm_keys, pool=None, graph_rows=None,
+                  graph_scores=None, graph_n=None):
     """The entries of ``mrag_fuse_topk_batch`` from the result arrays of the two batched searches, without a Python
     object per entry: ``text_docs`` / ``text_scores`` [B][kt] with ``text_n`` [B] valid slots per question (BM25),
     ``dense_ids`` / ``dense_scores`` [B][kd] with id -1 = no row (dense), ``norm_keys`` from :func:`corpus_norm_keys`,
     ``pool`` [B] (optional) = how many leading slots of each list the question uses.  Returns ``(chan_ptr int32
-    [3B+1], keys int32, scores float64, payload int32)``: per question its text entries, no graph entries, its dense
-    entries, each in list order; key = the row's normalised-id rank, payload = the row, fp32 scores widened exactly."""
+    [3B+1], keys int32, scores float64, payload int32)``: per question its text entries, its graph entries, its dense
+    entries, each in list order; key = the row's normalised-id rank, payload = the row, fp32 scores widened exactly.
+    The graph channel (optional, all three or none) is ``graph_rows`` [B][kg] corpus rows, ``graph_scores`` [B][kg]
+    fp64 and ``graph_n`` [B] valid leading slots per question (``DenseIndex.expand_neighbors``); without it every
+    question has no graph entries and the result is what it was before the arguments existed."""
     import numpy as np
     text_docs, dense_ids = np.asarray(text_docs, dtype=np.int64), np.asarray(dense_ids, dtype=np.int64)
     B = text_docs.shape[0]
     if B == 0:
         return np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.int32)
+    if (graph_rows is None) != (graph_scores is None) or (graph_rows is None) != (graph_n is None):
+        raise ValueError("pass graph_rows, graph_scores and graph_n together or not at all")
     text_docs, dense_ids = text_docs.reshape(B, -1), dense_ids.reshape(B, -1)
     text_scores = np.asarray(text_scores, dtype=np.float64).reshape(B, -1)
     dense_scores = np.asarray(dense_scores).astype(np.float64).reshape(B, -1)
@@ -194,18 +200,29 @@ def batch_entries(text_docs, text_scores, text_n, dense_ids, dense_scores, norm_
     t_mask = np.arange(text_docs.shape[1])[None, :] < np.minimum(np.asarray(text_n, dtype=np.int64).reshape(B), lim)[:, None]
     d_mask = (np.arange(dense_ids.shape[1])[None, :] < lim[:, None]) & (dense_ids >= 0)
     tn, dn = t_mask.sum(axis=1), d_mask.sum(axis=1)
+    gn = np.zeros(B, dtype=tn.dtype)
+    if graph_rows is not None:
+        graph_rows = np.asarray(graph_rows, dtype=np.int64).reshape(B, -1)
+        graph_scores = np.asarray(graph_scores, dtype=np.float64).reshape(B, -1)
+        g_mask = ((np.arange(graph_rows.shape[1])[None, :] < np.minimum(np.asarray(graph_n, dtype=np.int64).reshape(B), lim)[:, None])
+                  & (graph_rows >= 0))
+        gn = g_mask.sum(axis=1)
     start = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(tn + dn, out=start[1:])
+    np.cumsum(tn + gn + dn, out=start[1:])
     if start[-1] > 2 ** 31 - 1:
         raise ValueError(f"{int(start[-1])} fusion entries in one batch exceed the int32 offsets of the call")
     chan_ptr = np.empty(3 * B + 1, dtype=np.int32)
     chan_ptr[0:3 * B:3] = start[:-1]
-    chan_ptr[1:3 * B:3] = chan_ptr[2:3 * B:3] = start[:-1] + tn
+    chan_ptr[1:3 * B:3] = start[:-1] + tn
+    chan_ptr[2:3 * B:3] = start[:-1] + tn + gn
     chan_ptr[3 * B] = start[-1]
     E = int(start[-1])
     keys, scores, payload = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.float64), np.empty(E, dtype=np.int32)
     norm_keys = np.asarray(norm_keys, dtype=np.int32)
-    for mask, first, rows, vals in ((t_mask, start[:-1], text_docs, text_scores), (d_mask, start[:-1] + tn, dense_ids, dense_scores)):
+    channels = [(t_mask, start[:-1], text_docs, text_scores), (d_mask, start[:-1] + tn + gn, dense_ids, dense_scores)]
+    if graph_rows is not None:
+        channels.insert(1, (g_mask, start[:-1] + tn, graph_rows, graph_scores))
+    for mask, first, rows, vals in channels:
         dest = (first[:, None] + np.cumsum(mask, axis=1) - 1)[mask]
         r = rows[mask]
         keys[dest], scores[dest], payload[dest] = norm_keys[r], vals[mask], r

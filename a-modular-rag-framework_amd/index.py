@@ -174,6 +174,19 @@ def collapse_scan_k(k: int, m: int, n: int) -> int:
     return max(k, min(256, int(n), max(k, (k - 1) * int(m) + 1)))
 
 
+NEIGHBORS_MAX_WINDOW, NEIGHBORS_MAX_SEEDS, NEIGHBORS_MAX_ENTRIES = 16, 256, 4096
+
+
+def reference_decay(window: int) -> np.ndarray:
+    """The reference's score of a sentence at hop distance ``0 .. window`` from a matching sentence (graph_utils.py:87-94)
+    -> fp64 ``[window + 1]``: 1.0, 0.7, 0.5, then ``max(0.5 - 0.1 * (d - 2), 0.1)``, computed in Python floats as the
+    reference computes them (0.19999999999999996 at d = 5, the 0.1 floor from d = 6 on).  No GPU is needed."""
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, numbers.Integral) or int(window) < 0:
+        raise ValueError(f"window must be a non-negative integer, got {window!r}")
+    first = (1.0, 0.7, 0.5)
+    return np.asarray([first[d] if d < 3 else max(0.5 - 0.1 * (d - 2), 0.1) for d in range(int(window) + 1)], dtype=np.float64)
+
+
 IVF_FILTER_PATHS = {"auto": N.IVF_FILTER_AUTO, "probe": N.IVF_FILTER_PROBE, "exact": N.IVF_FILTER_EXACT}
 _IVF_FILTER_NAMES = {N.IVF_FILTER_PROBE: "probe", N.IVF_FILTER_EXACT: "exact"}
 
@@ -657,6 +670,78 @@ class DenseIndex:
         N.check(self._lib.mrag_index_last_collapsed(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
         return {"scan_k": a.value, "redone_queries": b.value, "redo_rounds": c.value, "max_rows_per_key": d.value,
                 "distinct_keys": e.value}
+
+    def expand_neighbors(self, seeds, window: int, m: Optional[int] = None, decay=None, return_from: bool = False, stream=None,
+                         out=None):
+        """The rows around each question's seed rows inside the seeds' own documents (``mrag_index_expand_neighbors``;
+        :meth:`set_row_keys` first) -> (scores [nq,m] fp32, ids [nq,m] int64), with ``return_from=True`` also
+        (dist [nq,m] int32, seed [nq,m] int32).
+
+        ``seeds`` is [nq, s] int64 global ids, numpy or a CUDA tensor -- for example the leading columns of a
+        :meth:`search` result; an id of -1 or outside the index is skipped.  The *run* of a row is the maximal interval
+        of consecutive rows with its key, and a seed row r reaches the rows of its run within ``window`` of r.  Every
+        distinct reached row c gets ``dist`` = its smallest distance to a seed that reaches it, ``seed`` = the lowest
+        seed position (column) at that distance, and the score ``decay[dist]``; the rows come ordered by (dist asc, seed
+        position asc, row asc), the first ``m`` of them, then (-inf, -1, -1, -1).  ``decay`` (``window + 1`` finite,
+        non-increasing values, a host array) defaults to :func:`reference_decay` as fp32; ``m`` defaults to
+        ``s * (2 * window + 1)``, at most 4096.  ``window <= 16``, ``s <= 256``, ``s * (2 * window + 1) <= 4096``.
+
+        Host seeds give numpy results after one synchronisation; CUDA seeds give CUDA tensors written by one launch on
+        ``stream`` (default: torch's current stream) with no synchronisation; ``out=(scores, ids)`` or ``(scores, ids,
+        dist, seed)`` reuses buffers.  The sharded indexes and ``IVFFlatIndex`` have no neighbour expansion."""
+        if isinstance(window, (bool, np.bool_)) or not isinstance(window, numbers.Integral) or not 0 <= int(window) <= NEIGHBORS_MAX_WINDOW:
+            raise ValueError(f"window must be an integer in [0, {NEIGHBORS_MAX_WINDOW}], got {window!r}")
+        window = int(window)
+        is_dev = int(_is_torch(seeds) and seeds.is_cuda)
+        if is_dev:
+            import torch
+            if seeds.dim() != 2 or seeds.dtype != torch.int64:
+                raise ValueError(f"device seeds must be a 2-D int64 tensor, got {tuple(seeds.shape)} {seeds.dtype}")
+            if seeds.device.index != self.device:
+                raise ValueError(f"seeds are on {seeds.device}, the index on cuda:{self.device}")
+            keep = seeds.contiguous()
+            sptr = keep.data_ptr()
+        else:
+            a = np.asarray(seeds.numpy() if _is_torch(seeds) else seeds)
+            if a.ndim != 2 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+                raise ValueError(f"seeds must be 2-D integers, got shape {a.shape} dtype {a.dtype}")
+            keep = np.ascontiguousarray(a, dtype=np.int64)
+            sptr = keep.ctypes.data
+        nq, s = int(keep.shape[0]), int(keep.shape[1])
+        if s > NEIGHBORS_MAX_SEEDS or s * (2 * window + 1) > NEIGHBORS_MAX_ENTRIES:
+            raise ValueError(f"{s} seeds per question at window {window}: at most {NEIGHBORS_MAX_SEEDS} seeds and "
+                             f"{NEIGHBORS_MAX_ENTRIES} entries = seeds * (2 * window + 1)")
+        m = max(1, min(NEIGHBORS_MAX_ENTRIES, s * (2 * window + 1))) if m is None else _check_k(m, NEIGHBORS_MAX_ENTRIES)
+        dk = reference_decay(window).astype(np.float32) if decay is None else np.ascontiguousarray(decay, dtype=np.float32).reshape(-1)
+        if dk.shape[0] != window + 1:
+            raise ValueError(f"decay must hold window + 1 = {window + 1} values, got {dk.shape[0]}")
+        if not np.isfinite(dk).all() or (np.diff(dk) > 0).any():
+            raise ValueError("decay must be finite and must not increase")
+        if out is not None and len(out) not in (2, 4):
+            raise ValueError("out must be (scores, ids) or (scores, ids, dist, seed)")
+        if out is not None and return_from and len(out) != 4:
+            raise ValueError("return_from=True needs out=(scores, ids, dist, seed)")
+        extra = [None, None]
+        if out is not None and len(out) == 4:
+            extra = [out[2], out[3]]
+        elif return_from and is_dev:
+            import torch
+            extra = [torch.empty((nq, m), dtype=torch.int32, device=keep.device) for _ in range(2)]
+        elif return_from:
+            extra = [np.empty((nq, m), dtype=np.int32) for _ in range(2)]
+        eptr = [None if x is None else (x.data_ptr() if is_dev else x.ctypes.data) for x in extra]
+
+        def call(sc, ids, out_dev, st):
+            return self._lib.mrag_index_expand_neighbors(self._h, sptr if nq * s else None, nq, s, is_dev, window, dk.ctypes.data, m,
+                                                         sc, ids, eptr[0], eptr[1], out_dev, st)
+        sc, ids = _run_search(call, keep, nq, m, is_dev, self.device, stream, bool(is_dev),
+                              None if out is None else (out[0], out[1]))
+        return (sc, ids, extra[0], extra[1]) if return_from else (sc, ids)
+
+    def last_neighbors(self) -> dict:
+        """What the last :meth:`expand_neighbors` did (``mrag_index_last_neighbors``): ``{"questions", "max_entries": seeds
+        per question x (2 x window + 1), "window"}``."""
+        return self._last_record(self._lib.mrag_index_last_neighbors, "questions", "max_entries", "window")
 
     def last_fp8(self) -> dict:
         """Refine pool and regime of the last fp8 search on this index (``mrag_index_last_fp8``):

@@ -404,5 +404,6 @@ int mrag_fuse_topk(int device, const int32_t* keys, const double* scores, int n_
 #include "mrag_filter_batch.h"
 #include "mrag_search_groups.h"
 #include "mrag_search_collapsed.h"
+#include "mrag_neighbors.h"
 
 #endif /* MRAG_H_ */
