@@ -22,6 +22,8 @@ injected when declared).
 from __future__ import annotations
 
 import logging
+from collections import Counter
+from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional
 
 import numpy as np
@@ -228,108 +230,126 @@ class HipDenseReranker:
             return {}
 
 
+def _resolve_option(name: str, value, field: bool = False, required: bool = False):
+    """An option given as a callable, as a ``"pkg.mod:func"`` string (resolved like the reference's impl strings,
+    settings.yaml impl_kwargs) or, with ``field``, as a row field name (a string without a colon) -> the callable or the
+    field name; ``None`` passes unless ``required``."""
+    if isinstance(value, str) and (":" in value or not field):
+        from .adapter import import_from_string
+        value = import_from_string(value)
+    if (value is None and not required) or callable(value) or (field and isinstance(value, str)):
+        return value
+    kinds = "a row field name, a callable" if field else "callable"
+    raise TypeError(f"{name} must be {kinds} or a 'pkg.mod:func' string, got {type(value)}")
+
+
+@dataclass
+class _Dense:
+    """The dense channel of a batch, as every dense stage of ``run_batch`` leaves it: ``ids`` / ``sc`` [B, kd], (-1, -inf) where
+    a request has no row, and per request ``k_eff`` (its leading slots), ``error`` and ``filter`` (its search's ``last_filter``).
+    ``collapse``: the record of the batch's one collapsed search; ``hits``: the dense hits the re-ranker made from text hits."""
+    state: Optional[Dict[str, Any]]
+    ids: np.ndarray
+    sc: np.ndarray
+    k_eff: List[int]
+    error: List[Optional[str]]
+    filter: List[Any]
+    collapse: Optional[Dict[str, Any]] = None
+    hits: Optional[List[List[Dict[str, Any]]]] = None
+
+    @classmethod
+    def empty(cls, B: int, state=None, error: Optional[str] = None) -> "_Dense":
+        return cls(state, np.full((B, 0), -1, dtype=np.int64), np.full((B, 0), -np.inf, dtype=np.float32), [0] * B, [error] * B, [None] * B)
+
+
+@dataclass
+class _Graph:
+    """The device graph channel of a batch: per request its window, ``error`` or ``info`` (the ``graph_channel`` record) and
+    the leading ``n[g]`` slots of ``rows`` / ``dist`` [B, m].  ``on`` False: no such channel, every array empty."""
+    on: bool
+    win: List[int]
+    error: List[Optional[str]]
+    info: List[Any]
+    n: np.ndarray
+    rows: np.ndarray
+    dist: np.ndarray
+
+
 class DenseRetrievalBackend:
     """Corpus-wide dense retrieval behind ``run`` / ``retrieve`` (see module docstring)."""
 
-    def __init__(self, router, sink=None, index_path: str = "data/hotpotqa/docs.jsonl",
-                 alpha_text: float = 0.4, alpha_graph: float = 0.2, alpha_dense: float = 0.4,
-                 default_top_k: int = 20, dense_pool_k: int = 200, embed_batch: int = 256,
-                 cache_dir: Optional[str] = None, device: int = 0, index_dtype: str = "f16",
+    def __init__(self, router, sink=None, index_path: str = "data/hotpotqa/docs.jsonl", alpha_text: float = 0.4,
+                 alpha_graph: float = 0.2, alpha_dense: float = 0.4, default_top_k: int = 20, dense_pool_k: int = 200,
+                 embed_batch: int = 256, cache_dir: Optional[str] = None, device: int = 0, index_dtype: str = "f16",
                  text_search: Optional[Callable[..., List[Dict[str, Any]]]] = None,
-                 graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None,
-                 text_channel: Optional[str] = None, bm25_k1: float = 1.5, bm25_b: float = 0.75,
-                 fuse_on_device: bool = False, bulk_ingest: bool = True, bulk_batch: int = 4096,
-                 dense_row_filter: Optional[Any] = None, dense_mode: str = "search", dense_filter_batch: bool = False,
-                 query_expander: Optional[Any] = None, dense_expanded: bool = False,
-                 dense_collapse: Optional[Any] = None,
-                 graph_channel: Optional[str] = None, graph_window: int = 2, graph_seed_k: Optional[int] = None,
-                 graph_doc: Any = "title"):
+                 graph_expand: Optional[Callable[..., List[Dict[str, Any]]]] = None, text_channel: Optional[str] = None,
+                 bm25_k1: float = 1.5, bm25_b: float = 0.75, fuse_on_device: bool = False, bulk_ingest: bool = True,
+                 bulk_batch: int = 4096, dense_row_filter: Optional[Any] = None, dense_mode: str = "search",
+                 dense_filter_batch: bool = False, query_expander: Optional[Any] = None, dense_expanded: bool = False,
+                 dense_collapse: Optional[Any] = None, graph_channel: Optional[str] = None, graph_window: int = 2,
+                 graph_seed_k: Optional[int] = None, graph_doc: Any = "title"):
+        """``text_channel="bm25"``: the reference's BM25 channel (text_index.py, retrieval_backend.py:102-128) over the same
+        docs.jsonl, on the device (mrag_amd.text_index), built once per file and shared process-wide.  ``fuse_on_device``:
+        a7's arithmetic in one launch (mrag_fuse_topk_batch) instead of host Python.  ``bulk_ingest``: a provider that can
+        embed in bulk on the device (``embed_device``) builds the index from docs.jsonl in ``bulk_batch``-passage batches
+        (text_index.py:32-53); the router path stays as the fallback / error-policy reference.
+        ``dense_row_filter(req, rows) -> None | bool mask over the corpus rows | row positions``: the dense channel searches
+        only those rows (``DenseIndex.search(allow=...)``); ``dense_filter_batch``: see :meth:`_search_sets`.
+        ``dense_mode="rerank"``: the dense channel scores the text channel's candidates instead of searching the corpus --
+        the reference's step 4 (retrieval_backend.py:332-334) with max_pool = pool.
+        ``query_expander(query=, trace_id=) -> List[str]`` (the reference's LLMQueryExpander.expand): the Expand step,
+        queries = [req.query] + expanded (retrieval_backend.py:307-310).  The text channel always receives the list; the
+        dense channel searches all of it, max-merged per row (``DenseIndex.search_groups``), only with ``dense_expanded``.
+        ``dense_collapse`` (a row field name or a callable row -> hashable): the dense channel returns the best DOCUMENTS,
+        each by its best row (``DenseIndex.search_collapsed``), instead of the best rows.
+        ``graph_channel="neighbors"``: the reference's graph channel (retrieval_backend.py:134-182, graph_utils.py:58-129)
+        on the device (``DenseIndex.expand_neighbors``): the sentences within ``graph_window`` rows of the request's leading
+        ``graph_seed_k`` dense hits (None: its top_k), inside their own document.  ``graph_doc`` names every row's document
+        like ``dense_collapse``; the index holds ONE key array, so with ``dense_collapse`` both must name the same keys.
+        The filter, the expander, ``dense_collapse`` and ``graph_doc`` may each be a "pkg.mod:func" string."""
         self.router, self.sink = router, sink
         self.index_path = index_path
         self.alpha_text, self.alpha_graph, self.alpha_dense = float(alpha_text), float(alpha_graph), float(alpha_dense)
         self.default_top_k, self.dense_pool_k, self.embed_batch = int(default_top_k), int(dense_pool_k), int(embed_batch)
         self.cache_dir, self.device, self.index_dtype = cache_dir, int(device), index_dtype
         self.text_search, self.graph_expand = text_search, graph_expand
-        # text_channel="bm25": the reference's BM25 channel (text_index.py, retrieval_backend.py:102-128) over the same
-        # docs.jsonl, on the device (mrag_amd.text_index), built once per file and shared process-wide
         self.text_channel, self.bm25_k1, self.bm25_b = text_channel, float(bm25_k1), float(bm25_b)
-        self.fuse_on_device = bool(fuse_on_device)     # a7's arithmetic in one launch (mrag_fuse_topk_batch) instead of host Python
-        # corpus ingest: when the provider the router resolves can embed in bulk on the device (``embed_device``), the
-        # index is built from docs.jsonl through it in ``bulk_batch``-passage batches (text_index.py:32-53: the reference
-        # builds its index from the file in one go); the router path below stays as the fallback / error-policy reference
+        self.fuse_on_device = bool(fuse_on_device)
         self.bulk_ingest, self.bulk_batch = bool(bulk_ingest), int(bulk_batch)
         self.last_build: Dict[str, Any] = {}
-        # dense_row_filter(req, rows) -> None | bool mask over the corpus rows | row positions: the dense channel then
-        # searches only those rows (DenseIndex.search(allow=...)); a "pkg.mod:func" string (settings.yaml impl_kwargs)
-        # is resolved like the reference's impl strings
-        if isinstance(dense_row_filter, str):
-            from .adapter import import_from_string
-            dense_row_filter = import_from_string(dense_row_filter)
-        if dense_row_filter is not None and not callable(dense_row_filter):
-            raise TypeError(f"dense_row_filter must be callable or a 'pkg.mod:func' string, got {type(dense_row_filter)}")
-        self.dense_row_filter = dense_row_filter
-        # run_batch: the requests whose filter returns a set share ONE DenseIndex.search_sets call instead of one filtered
-        # search each (off by default: their diagnostics then name the path "sets", not the single search's)
-        self.dense_filter_batch = bool(dense_filter_batch)
+        self.dense_filter_batch, self.dense_expanded = bool(dense_filter_batch), bool(dense_expanded)
+        self.dense_mode, self.graph_channel, self.graph_window, self.graph_seed_k = dense_mode, graph_channel, graph_window, graph_seed_k
         self._own_text_search = None                     # the searcher _bm25_searcher() made over index_path, if any
+        self._state = None
+        # the four resolved options and every refusal, in one order: the first rule violated is the one reported
+        rerank = dense_mode == "rerank"
+        self.dense_row_filter = dense_row_filter = _resolve_option("dense_row_filter", dense_row_filter)
         if text_channel not in (None, "bm25"):
             raise ValueError(f"unknown text_channel {text_channel!r} (supported: 'bm25')")
-        # dense_mode="search": the dense channel is a corpus-wide top-k (above).  "rerank": it scores the text channel's
-        # candidates instead -- the reference's step 4 (retrieval_backend.py:332-334) with max_pool = pool
         if dense_mode not in ("search", "rerank"):
             raise ValueError(f"unknown dense_mode {dense_mode!r} (supported: 'search', 'rerank')")
-        if dense_mode == "rerank" and dense_row_filter is not None:
+        if rerank and dense_row_filter is not None:
             raise ValueError("dense_row_filter restricts the corpus-wide search: it has no meaning with dense_mode='rerank'")
-        self.dense_mode = dense_mode
-        # query_expander(query=, trace_id=) -> List[str] (the signature of the reference's LLMQueryExpander.expand): the
-        # reference's Expand step, queries = [req.query] + expanded (retrieval_backend.py:307-310); a "pkg.mod:func"
-        # string is resolved like dense_row_filter.  The text channel always receives the list; the dense channel embeds
-        # and searches all of it, max-merged per row (DenseIndex.search_groups), only with dense_expanded=True
-        if isinstance(query_expander, str):
-            from .adapter import import_from_string
-            query_expander = import_from_string(query_expander)
-        if query_expander is not None and not callable(query_expander):
-            raise TypeError(f"query_expander must be callable or a 'pkg.mod:func' string, got {type(query_expander)}")
-        self.query_expander = query_expander
-        self.dense_expanded = bool(dense_expanded)
-        if self.dense_expanded and dense_mode == "rerank":
+        self.query_expander = _resolve_option("query_expander", query_expander)
+        if self.dense_expanded and rerank:
             raise ValueError("dense_mode='rerank' scores the candidates with req.query alone (retrieval_backend.py:333): "
                              "it does not combine with dense_expanded=True")
-        # dense_collapse: the dense channel returns the best DOCUMENTS, each by its best row (DenseIndex.search_collapsed),
-        # instead of the best rows.  A row field name ("title"), a callable row -> hashable, or a "pkg.mod:func" string
-        # resolved like dense_row_filter gives every row its document
-        if isinstance(dense_collapse, str) and ":" in dense_collapse:
-            from .adapter import import_from_string
-            dense_collapse = import_from_string(dense_collapse)
-        if dense_collapse is not None and not isinstance(dense_collapse, str) and not callable(dense_collapse):
-            raise TypeError(f"dense_collapse must be a row field name, a callable or a 'pkg.mod:func' string, got {type(dense_collapse)}")
-        if dense_collapse is not None and (dense_mode == "rerank" or dense_row_filter is not None or self.dense_expanded):
+        self.dense_collapse = dense_collapse = _resolve_option("dense_collapse", dense_collapse, field=True)
+        if dense_collapse is not None and (rerank or dense_row_filter is not None or self.dense_expanded):
             raise ValueError("dense_collapse does not combine with dense_mode='rerank', dense_row_filter or dense_expanded=True")
-        self.dense_collapse = dense_collapse
-        # graph_channel="neighbors": the reference's graph channel (retrieval_backend.py:134-182, graph_utils.py:58-129)
-        # over the corpus rows, on the device (DenseIndex.expand_neighbors): the sentences within graph_window rows of the
-        # request's leading graph_seed_k dense hits (None: its top_k), inside their own document.  graph_doc names every
-        # row's document like dense_collapse does (a row field, a callable or a "pkg.mod:func" string); the index holds ONE
-        # key array, so with dense_collapse both must name the same keys
         if graph_channel not in (None, "neighbors"):
             raise ValueError(f"unknown graph_channel {graph_channel!r} (supported: 'neighbors')")
         if graph_channel is not None and graph_expand is not None:
             raise ValueError("graph_channel and an injected graph_expand both fill the graph channel: give one")
-        if graph_channel is not None and dense_mode == "rerank":
+        if graph_channel is not None and rerank:
             raise ValueError("graph_channel seeds from the corpus-wide dense search: it does not combine with dense_mode='rerank'")
-        if isinstance(graph_doc, str) and ":" in graph_doc:
-            from .adapter import import_from_string
-            graph_doc = import_from_string(graph_doc)
-        if not isinstance(graph_doc, str) and not callable(graph_doc):
-            raise TypeError(f"graph_doc must be a row field name, a callable or a 'pkg.mod:func' string, got {type(graph_doc)}")
+        self.graph_doc = graph_doc = _resolve_option("graph_doc", graph_doc, field=True, required=True)
         if graph_channel is not None and dense_collapse is not None and graph_doc != dense_collapse:
             raise ValueError("graph_doc and dense_collapse must name the same row keys: the index holds one key array")
         if isinstance(graph_window, bool) or not isinstance(graph_window, int) or graph_window < 0:
             raise ValueError(f"graph_window must be a non-negative integer, got {graph_window!r}")
         if graph_seed_k is not None and (isinstance(graph_seed_k, bool) or not isinstance(graph_seed_k, int) or graph_seed_k < 1):
             raise ValueError(f"graph_seed_k must be a positive integer or None, got {graph_seed_k!r}")
-        self.graph_channel, self.graph_window, self.graph_seed_k, self.graph_doc = graph_channel, graph_window, graph_seed_k, graph_doc
-        self._state = None
 
     def _row_keys(self, state, by):
         """The row keys ``by`` (a row field or a callable) gives the state's rows -> ``(keys, distinct keys, max rows per
@@ -344,20 +364,17 @@ class DenseRetrievalBackend:
             state["collapse_on_index"] = entry[0]
         return entry
 
-    def _collapse_keys(self, state):
-        """:meth:`_row_keys` of ``dense_collapse``"""
-        return self._row_keys(state, self.dense_collapse)
-
     # -- graph_channel="neighbors" ------------------------------------------------------------------------------------------
     def _graph_window_of(self, req) -> int:
         """the request's own integer ``graph_window``, else the backend's (retrieval_backend.py:318-324, :156)"""
         gw = getattr(req, "graph_window", None)
         return max(0, int(gw if isinstance(gw, int) else self.graph_window))
 
-    def _graph_seeds_of(self, top_k: int, window: int) -> int:
-        """how many leading dense hits seed the expansion: ``graph_seed_k`` or the request's ``top_k``, inside the call's limits"""
+    def _graph_seeds_of(self, top_k: int, window: int, n_dense: int = 256) -> int:
+        """how many leading dense hits seed the expansion: ``graph_seed_k`` or the request's ``top_k``, inside the call's limits
+        and never more than the ``n_dense`` its dense list holds"""
         k = top_k if self.graph_seed_k is None else self.graph_seed_k
-        return max(0, min(int(k), 256, 4096 // (2 * window + 1)))
+        return max(0, min(int(k), 256, 4096 // (2 * window + 1), n_dense))
 
     def _graph_expand_rows(self, state, seeds: np.ndarray, window: int, m: int):
         """ONE ``expand_neighbors`` call over the seed rows [n, s] -> (ids [n, m], dist [n, m]) under ``graph_doc``'s keys"""
@@ -477,27 +494,22 @@ class DenseRetrievalBackend:
         state["index"], state["dim"] = ix, dim
         # raw hit id (retrieval_backend.py:116-119) -> corpus row, for the re-ranker's lookup by id; ids that
         # occur twice (duplicate doc_id lines) are ambiguous and left out: such candidates are embedded as before
-        seen: Dict[str, int] = {}
-        for r in rows:
-            hid = _fusion.raw_hit_id(r)
-            seen[hid] = seen.get(hid, 0) + 1
-        row_of: Dict[str, int] = {}
-        for i, r in enumerate(rows):
-            hid = _fusion.raw_hit_id(r)
-            if seen[hid] == 1:
-                row_of[hid] = i
-        state["row_of"] = row_of
+        hids = [_fusion.raw_hit_id(r) for r in rows]
+        seen = Counter(hids)
+        state["row_of"] = {hid: i for i, hid in enumerate(hids) if seen[hid] == 1}
         self.last_build = {"rows": len(rows), "dim": dim, "ingest": state.get("ingest", "cache"),
                            "seconds": time.perf_counter() - t_start}
         return state
 
+    def _file_signature(self) -> str:
+        try:
+            return _corpus.file_signature(self.index_path)
+        except OSError:
+            return f"{self.index_path}|missing"
+
     def _bm25_searcher(self):
         from .text_index import HipBM25Index, HipBM25TextSearcher
-        try:
-            sig = _corpus.file_signature(self.index_path)
-        except OSError:
-            sig = f"{self.index_path}|missing"
-        key = f"bm25-index|{sig}|{self.device}|{self.bm25_k1}|{self.bm25_b}"
+        key = f"bm25-index|{self._file_signature()}|{self.device}|{self.bm25_k1}|{self.bm25_b}"
         ix = _corpus.shared(key, lambda: HipBM25Index(self.index_path, k1=self.bm25_k1, b=self.bm25_b, device=self.device))
         self._own_text_search = HipBM25TextSearcher(ix)    # run_batch reads its document positions as corpus rows
         return self._own_text_search
@@ -508,11 +520,7 @@ class DenseRetrievalBackend:
     def _get_state(self, model_hint: str, trace_id: str):
         if self._state is None:
             import time
-            try:
-                sig = _corpus.file_signature(self.index_path)
-            except OSError:
-                sig = f"{self.index_path}|missing"
-            key = f"dense-index|{sig}|{model_hint}|{self.device}|{self.index_dtype}"
+            key = f"dense-index|{self._file_signature()}|{model_hint}|{self.device}|{self.index_dtype}"
             bad = DenseRetrievalBackend._failed.get(key)
             if bad and time.monotonic() < bad[0]:
                 raise RuntimeError(f"corpus index build failed {self._FAIL_BACKOFF_S:.0f}s ago or less: {bad[1]}")
@@ -524,7 +532,7 @@ class DenseRetrievalBackend:
             DenseRetrievalBackend._failed.pop(key, None)
         return self._state
 
-    # -- the backend protocol ---------------------------------------------------------------------
+    # -- the backend protocol: leaves that run and run_batch share --------------------------------------------------------
     def _expand(self, req, trace_id: str):
         """The reference's Expand step (retrieval_backend.py:307-310) -> (``[req.query] + expanded``, error text or None).
         Without a ``query_expander`` there is no step and no span; an expander that raises is logged and the request
@@ -539,108 +547,96 @@ class DenseRetrievalBackend:
                 logger.error("[DenseRetrievalBackend] query expansion failed: %s", e)
                 return [req.query], repr(e)
 
+    def _graph_expand_hits(self, req, pool: int, trace_id: str) -> List[Dict[str, Any]]:
+        """one request's hits of an injected ``graph_expand``"""
+        if self.graph_expand is None:
+            return []
+        with span("Backend/GraphExpand", self.sink, trace_id):
+            return list(self.graph_expand(query=req.query, graph_id=getattr(req, "graph_id", "") or "", top_k=pool) or [])
+
+    def _ensure_text_search(self) -> Optional[str]:
+        """``text_channel="bm25"`` without a searcher yet: make it (:meth:`_bm25_searcher`) -> ``text_error``.  A failure
+        degrades like the dense channel: it is reported and the other channels keep serving."""
+        if self.text_search is None and self.text_channel == "bm25":
+            try:
+                self.text_search = self._bm25_searcher()
+            except Exception as e:
+                logger.error("[DenseRetrievalBackend] BM25 channel unavailable: %s", e)
+                return repr(e)
+        return None
+
+    @staticmethod
+    def _dense_hits(rows, scores, ids) -> List[Dict[str, Any]]:
+        """one result row of a dense search as the dense channel's hits; the (-inf, -1) slots are left out"""
+        return [{"id": _fusion.raw_hit_id(rows[int(i)]), "score": float(s), "meta": _fusion.row_meta(rows[int(i)], "dense")}
+                for s, i in zip(scores, ids) if i >= 0]
+
+    def _search_one(self, ix, Q, k: int, allow=None):
+        """The search of ONE request over its query rows ``Q`` -- all of its queries max-merged per row with
+        ``dense_expanded`` -- inside ``allow`` if given -> ``(scores [1, k], ids [1, k], last_filter record or None)``."""
+        kw = {} if allow is None else {"allow": allow}
+        sc, ids = ix.search_groups(Q, k, sizes=[len(Q)], **kw) if self.dense_expanded else ix.search(Q, k, **kw)
+        return sc, ids, (ix.last_filter() if allow is not None else None)
+
+    def _search_collapsed(self, state, Q, k: int):
+        """ONE ``search_collapsed`` -- the best documents, each by its best row -> ``(scores, ids, the dense_collapse record
+        of the diagnostics)``"""
+        _, n_keys, m = self._row_keys(state, self.dense_collapse)
+        sc, ids = state["index"].search_collapsed(Q, k, return_keys=False)
+        lc = state["index"].last_collapsed()
+        return sc, ids, {"keys": n_keys, "max_rows_per_key": m, "scan_k": lc["scan_k"], "redone": lc["redone_queries"]}
+
+    @staticmethod
+    def _graph_record(n_seeds: int, window: int) -> Dict[str, int]:
+        return {"seeds": n_seeds, "window": window, "max_entries": n_seeds * (2 * window + 1)}
+
+    @staticmethod
+    def _fuse_overlay(fused, dense_norm, top_k: int):
+        """dense-only ids carry their own meta -> the leading ``top_k`` of ``fused``"""
+        for h in fused:
+            if not h["meta"].get("text") and h["id"] in dense_norm:
+                meta = dict(dense_norm[h["id"]]["meta"])
+                meta.update({k: v for k, v in h["meta"].items() if k.startswith("score_")})
+                h["meta"] = meta
+        return fused[:top_k]
+
+    def _diagnostics(self, queries, counts, top_k: int, k_eff: int, model_hint: str, dense_error, text_error, **optional):
+        """One request's diagnostics.  ``counts``: the (text, graph, dense) candidates.  ``optional``: the keys that exist only
+        when they say something (None: left out) -- ``batch_size``, ``dense_filter``, ``dense_collapse``, ``expand_error``,
+        ``graph_window_used``, ``graph_channel``, ``graph_error``; ``dense_mode`` is added here."""
+        d = {
+            "queries": queries,
+            "bm25_candidates": counts[0],
+            "graph_candidates": counts[1],
+            "dense_scored": counts[2],
+            "weights": self._alphas(),
+            "pool": {"dense_pool_k": self.dense_pool_k, "final_top_k": top_k, "dense_pool_k_effective": k_eff},
+            "resolved_embed_model": model_hint,
+            "dense_backend": "mrag_amd.DenseIndex",
+            "dense_error": dense_error,
+            "text_error": text_error,
+        }
+        if self.dense_mode == "rerank":
+            d["dense_mode"] = "rerank"
+        d.update({key: v for key, v in optional.items() if v is not None})
+        return d
+
+    # -- run: one request.  Its text, dense and graph steps stay its own (DESIGN.md "Backend orchestration") -------------
     def run(self, req) -> Dict[str, Any]:
         trace_id = getattr(req, "trace_id", None) or "trace-demo"                       # :304
         top_k = int(getattr(req, "top_k", None) or self.default_top_k)                  # :305
         model_hint = resolve_embed_model(self.router)
         pool = max(top_k, self.dense_pool_k)
         queries, expand_error = self._expand(req, trace_id)
-
-        t_hits: List[Dict[str, Any]] = []
-        g_hits: List[Dict[str, Any]] = []
-        text_error = None
-        if self.text_search is None and self.text_channel == "bm25":
-            try:
-                self.text_search = self._bm25_searcher()
-            except Exception as e:     # degrade like the dense channel: report, keep serving the other channels
-                text_error = repr(e)
-                logger.error("[DenseRetrievalBackend] BM25 channel unavailable: %s", e)
-        rerank = self.dense_mode == "rerank"
-        own = rerank and self._is_own_searcher()
-        t_docs: List[int] = []                           # rerank over the own searcher: the hits' document positions
-        if self.text_search is not None:
-            with span("Backend/TextSearch", self.sink, trace_id):
-                if own:
-                    ranked = (self.text_search.index.search(queries, top_k=pool, alpha_merge="max")
-                              if self.text_search.index.N > 0 else [])
-                    t_docs = [int(d) for d, _ in ranked]
-                    t_hits = self.text_search._hits(ranked)
-                else:
-                    t_hits = list(self.text_search(queries=queries, top_k=pool) or [])
-        if self.graph_expand is not None:
-            with span("Backend/GraphExpand", self.sink, trace_id):
-                g_hits = list(self.graph_expand(query=req.query, graph_id=getattr(req, "graph_id", "") or "",
-                                                top_k=pool) or [])
-
-        dense_hits: List[Dict[str, Any]] = []
-        dense_error = None
-        dense_filter = None
-        dense_collapse = None
-        dense_rows = None                                # the dense list's row ids, the seeds of graph_channel="neighbors"
-        state = None
-        k_eff = 0
+        text_error = self._ensure_text_search()
+        t_hits, t_docs = self._run_text(queries, pool, trace_id)
+        g_hits = self._graph_expand_hits(req, pool, trace_id)
         with span("Backend/DenseRerank", self.sink, trace_id):      # same span name as :332
-            try:
-                state = None if rerank else self._get_state(model_hint, trace_id)
-                if rerank and t_hits:
-                    dense_hits = self._rerank_one(req, t_hits[:pool], t_docs[:pool] if own else None, pool, model_hint, trace_id)
-                    k_eff = len(dense_hits)
-                if state is not None and state["index"] is not None and self.dense_expanded:
-                    # every query of the request, max-merged per row on the device: one group
-                    Qv = self._embed_texts(queries, model_hint, trace_id, dim=state["dim"])
-                    k_eff = min(pool, len(state["rows"]), state["index"].max_k(1))
-                    allow = self.dense_row_filter(req, state["rows"]) if self.dense_row_filter is not None else None
-                    sc, ids = state["index"].search_groups(Qv, k_eff, sizes=[len(queries)], allow=allow)
-                    if allow is not None:
-                        dense_filter = state["index"].last_filter()
-                    dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
-                    dense_rows = ids[0]
-                elif state is not None and state["index"] is not None:
-                    qv = np.asarray(_vectors(self.router.embed(model_hint=model_hint, texts=[req.query],
-                                                               require={"trace_id": trace_id}))[0], dtype=np.float32)
-                    if qv.shape[0] != state["dim"]:
-                        raise ValueError(f"query embedding has dim {qv.shape[0]}, corpus has {state['dim']}")
-                    # the reference scores its whole pool (retrieval_backend.py:218,245); the index serves
-                    # k up to max_k() (256) -- anything beyond is reported, never silently dropped
-                    k = min(pool, len(state["rows"]))
-                    k_eff = min(k, state["index"].max_k(1))
-                    allow = self.dense_row_filter(req, state["rows"]) if self.dense_row_filter is not None else None
-                    if self.dense_collapse is not None:      # the best documents, each by its best row
-                        _, n_keys, m = self._collapse_keys(state)
-                        k_eff = min(pool, n_keys, state["index"].max_k(1))
-                        sc, ids = state["index"].search_collapsed(qv[None, :], k_eff, return_keys=False)
-                        lc = state["index"].last_collapsed()
-                        dense_collapse = {"keys": n_keys, "max_rows_per_key": m, "scan_k": lc["scan_k"], "redone": lc["redone_queries"]}
-                    elif allow is None:
-                        sc, ids = state["index"].search(qv[None, :], k_eff)
-                    else:
-                        sc, ids = state["index"].search(qv[None, :], k_eff, allow=allow)
-                        dense_filter = state["index"].last_filter()
-                    dense_hits = self._dense_hits(state["rows"], sc[0], ids[0])
-                    dense_rows = ids[0]
-            except Exception as e:     # reference policy: degrade, never raise out of run() (:229-231)
-                dense_error = repr(e)
-                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
-
-        # the device graph channel: the neighbours of the leading dense hits inside their documents (after the dense search,
-        # which gives the seeds; the reference's step 3, retrieval_backend.py:317-329)
-        graph_error = None
-        graph_info = None
+            state, dense_hits, dense_rows, k_eff, dense_error, dense_filter, dense_collapse = self._run_dense(
+                req, queries, pool, t_hits, t_docs, model_hint, trace_id)
+        graph = {}
         if self.graph_channel is not None:
-            window = self._graph_window_of(req)
-            with span("Backend/GraphExpand", self.sink, trace_id):
-                try:
-                    if dense_error is not None:
-                        raise RuntimeError(f"no seeds, the dense channel failed: {dense_error}")
-                    n_seeds = min(self._graph_seeds_of(top_k, window), len(dense_rows)) if dense_rows is not None else 0
-                    if n_seeds > 0:
-                        g_ids, g_dist = self._graph_expand_rows(state, np.asarray(dense_rows[:n_seeds])[None, :], window, min(pool, 4096))
-                        g_hits = self._graph_hits(state["rows"], g_ids[0], g_dist[0], window)
-                    graph_info = {"seeds": n_seeds, "window": window, "max_entries": n_seeds * (2 * window + 1)}
-                except Exception as e:
-                    graph_error = repr(e)
-                    g_hits = []
-                    logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
+            g_hits, graph = self._run_graph(req, state, dense_rows, dense_error, top_k, pool, trace_id)
 
         # dense hits double as candidates (their meta gives the normalised id); scores fused per :350-372
         dense_norm_hits = _fusion.dedupe_by_norm_id(dense_hits)
@@ -650,45 +646,79 @@ class DenseRetrievalBackend:
             fuse = lambda *a, **kw: _fusion.fuse_channels_device(*a, device=self.device, **kw)    # noqa: E731
         fused = fuse(t_hits, g_hits, dense_scores, alpha_text=self.alpha_text,
                      alpha_graph=self.alpha_graph, alpha_dense=self.alpha_dense, top_k=10 ** 9)
-        for h in fused:                                   # dense-only ids carry their own meta
-            if not h["meta"].get("text") and h["id"] in dense_norm_hits:
-                meta = dict(dense_norm_hits[h["id"]]["meta"])
-                meta.update({k: v for k, v in h["meta"].items() if k.startswith("score_")})
-                h["meta"] = meta
-        fused = fused[:top_k]
-        diagnostics = {
-            "queries": queries,
-            "bm25_candidates": len(t_hits),
-            "graph_candidates": len(g_hits),
-            "dense_scored": len(dense_scores),
-            "weights": {"alpha_text": self.alpha_text, "alpha_graph": self.alpha_graph, "alpha_dense": self.alpha_dense},
-            "pool": {"dense_pool_k": self.dense_pool_k, "final_top_k": top_k, "dense_pool_k_effective": k_eff},
-            "resolved_embed_model": model_hint,
-            "dense_backend": "mrag_amd.DenseIndex",
-            "dense_error": dense_error,
-            "text_error": text_error,
-        }
-        if rerank:
-            diagnostics["dense_mode"] = "rerank"
-        if dense_filter is not None:
-            diagnostics["dense_filter"] = dense_filter
-        if dense_collapse is not None:
-            diagnostics["dense_collapse"] = dense_collapse
-        if expand_error is not None:
-            diagnostics["expand_error"] = expand_error
-        if self.graph_channel is not None:
-            diagnostics["graph_window_used"] = window
-            if graph_info is not None:
-                diagnostics["graph_channel"] = graph_info
-            if graph_error is not None:
-                diagnostics["graph_error"] = graph_error
-        return {"hits": fused, "diagnostics": diagnostics}
+        hits = self._fuse_overlay(fused, dense_norm_hits, top_k)
+        return {"hits": hits, "diagnostics": self._diagnostics(
+            queries, (len(t_hits), len(g_hits), len(dense_scores)), top_k, k_eff, model_hint, dense_error, text_error,
+            dense_filter=dense_filter, dense_collapse=dense_collapse, expand_error=expand_error, **graph)}
 
-    @staticmethod
-    def _dense_hits(rows, scores, ids) -> List[Dict[str, Any]]:
-        """one result row of a dense search as the dense channel's hits; the (-inf, -1) slots are left out"""
-        return [{"id": _fusion.raw_hit_id(rows[int(i)]), "score": float(s), "meta": _fusion.row_meta(rows[int(i)], "dense")}
-                for s, i in zip(scores, ids) if i >= 0]
+    def _run_text(self, queries, pool: int, trace_id: str):
+        """:meth:`run`'s text channel -> (hits, their document positions).  The positions are kept only in rerank mode over
+        the backend's own searcher, where they are the dense state's rows."""
+        if self.text_search is None:
+            return [], []
+        with span("Backend/TextSearch", self.sink, trace_id):
+            if self.dense_mode == "rerank" and self._is_own_searcher():
+                ranked = (self.text_search.index.search(queries, top_k=pool, alpha_merge="max")
+                          if self.text_search.index.N > 0 else [])
+                return self.text_search._hits(ranked), [int(d) for d, _ in ranked]
+            return list(self.text_search(queries=queries, top_k=pool) or []), []
+
+    def _run_dense(self, req, queries, pool: int, t_hits, t_docs, model_hint: str, trace_id: str):
+        """:meth:`run`'s dense channel -> ``(state, hits, row ids or None, k_eff, error, dense_filter, dense_collapse)``.  The
+        reference's policy: degrade, never raise out of run() (:229-231); what was known before a failure is reported."""
+        rerank = self.dense_mode == "rerank"
+        state, hits, ids, k_eff, error, dense_filter, dense_collapse = None, [], None, 0, None, None, None
+        try:
+            state = None if rerank else self._get_state(model_hint, trace_id)
+            if rerank and t_hits:
+                own = self._is_own_searcher()
+                hits = self._rerank_one(req, t_hits[:pool], t_docs[:pool] if own else None, pool, model_hint, trace_id)
+                k_eff = len(hits)
+            if state is not None and state["index"] is not None:
+                ix, rows = state["index"], state["rows"]
+                if self.dense_expanded:                  # every query of the request, max-merged per row on the device
+                    Q = self._embed_texts(queries, model_hint, trace_id, dim=state["dim"])
+                else:
+                    qv = np.asarray(_vectors(self.router.embed(model_hint=model_hint, texts=[req.query],
+                                                               require={"trace_id": trace_id}))[0], dtype=np.float32)
+                    if qv.shape[0] != state["dim"]:
+                        raise ValueError(f"query embedding has dim {qv.shape[0]}, corpus has {state['dim']}")
+                    Q = qv[None, :]
+                # the reference scores its whole pool (:218,245); the index serves k up to max_k() (256): the rest is reported
+                k_one = ix.max_k(1)
+                k_eff = min(pool, len(rows), k_one)
+                allow = self.dense_row_filter(req, rows) if self.dense_row_filter is not None else None
+                if self.dense_collapse is not None:
+                    k_eff = min(pool, self._row_keys(state, self.dense_collapse)[1], k_one)      # never more than there are documents
+                    sc, ids, dense_collapse = self._search_collapsed(state, Q, k_eff)
+                else:
+                    sc, ids, dense_filter = self._search_one(ix, Q, k_eff, allow)
+                ids = ids[0]
+                hits = self._dense_hits(rows, sc[0], ids)
+        except Exception as e:
+            error = repr(e)
+            logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+        return state, hits, ids, k_eff, error, dense_filter, dense_collapse
+
+    def _run_graph(self, req, state, dense_rows, dense_error, top_k: int, pool: int, trace_id: str):
+        """:meth:`run`'s device graph channel: the neighbours of the leading dense hits inside their documents (after the
+        dense search, which gives the seeds; the reference's step 3, retrieval_backend.py:317-329) -> ``(graph hits, its
+        keys of the diagnostics)``"""
+        window = self._graph_window_of(req)
+        g_hits, info, error = [], None, None
+        with span("Backend/GraphExpand", self.sink, trace_id):
+            try:
+                if dense_error is not None:
+                    raise RuntimeError(f"no seeds, the dense channel failed: {dense_error}")
+                n_seeds = self._graph_seeds_of(top_k, window, len(dense_rows)) if dense_rows is not None else 0
+                if n_seeds > 0:
+                    g_ids, g_dist = self._graph_expand_rows(state, np.asarray(dense_rows[:n_seeds])[None, :], window, min(pool, 4096))
+                    g_hits = self._graph_hits(state["rows"], g_ids[0], g_dist[0], window)
+                info = self._graph_record(n_seeds, window)
+            except Exception as e:
+                error, g_hits = repr(e), []
+                logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
+        return g_hits, {"graph_window_used": window, "graph_channel": info, "graph_error": error}
 
     # -- dense_mode="rerank": the dense channel scores the text channel's candidates ------------------------------------
     def _is_own_searcher(self) -> bool:
@@ -717,47 +747,22 @@ class DenseRetrievalBackend:
             if self._rows_are_docs(state):
                 qv = self._embed_texts([req.query], model_hint, trace_id, dim=state["dim"])[0]      # validated as run_batch's
                 sc = state["index"].score_rows(qv, np.asarray(docs, dtype=np.int64))
-                rows = state["rows"]
-                return [{"id": _fusion.raw_hit_id(rows[d]), "score": float(s), "meta": _fusion.row_meta(rows[d], "dense")}
-                        for d, s in zip(docs, sc)]
+                return self._dense_hits(state["rows"], sc, docs)
         rr = HipDenseReranker(self.router, max_pool=pool, embed_batch=self.embed_batch, device=self.device, corpus=self)
         return self._scored_hits(cands, rr.score(query=req.query, candidates=cands, trace_id=trace_id))
 
-    def retrieve(self, req) -> RetrievalOut:
-        result = self.run(req)
-        hits = [Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]]
-        return RetrievalOut(hits=hits, diagnostics=result.get("diagnostics", {}))
-
-    # -- the same protocol for a list of requests: one dense search, one BM25 batch search, one fusion launch ------------
-    def _norm_keys(self, state):
-        """``fusion.corpus_norm_keys`` of the state's rows, built once per state and kept in it."""
-        if "norm_keys" not in state:
-            state["norm_keys"] = _fusion.corpus_norm_keys(state["rows"])
-        return state["norm_keys"]
-
+    # -- run_batch: the same protocol for a list of requests, as a sequence of stages -----------------------------------
     def run_batch(self, reqs) -> List[Dict[str, Any]]:
-        """:meth:`run` for every request of ``reqs``, in order, with the device work of the whole list in three calls:
-        one ``DenseIndex.search`` over all query embeddings, one ``HipBM25Index.search_batch`` (``text_channel="bm25"``)
-        and one ``mrag_fuse_topk_batch``.  ``top_k``, ``trace_id`` and the pool are each request's own: the searches run
-        at the list's largest pool and every question uses the leading part of its lists that its own pool covers (both
-        searches are exact with a declared order, so a prefix is the smaller search's answer).  Requests for which
-        ``dense_row_filter`` returns a set are searched one by one with their ``allow`` -- or, with
-        ``dense_filter_batch=True``, all together in one ``DenseIndex.search_sets`` call in which sets of equal content
-        are shared and whose diagnostics read ``dense_filter = {"path": "sets", "allowed": m}``; an injected ``text_search`` and
-        ``graph_expand`` are called once per request.  Like :meth:`run` it degrades and never raises out of the dense
-        channel.  Diagnostics are :meth:`run`'s plus ``batch_size``.  With ``dense_mode="rerank"`` the dense search is
-        replaced by one ``DenseIndex.score_rows_batch`` over every question's leading text candidates (own BM25 searcher)
-        or one ``HipDenseReranker.score_batch`` (injected searcher): :meth:`_rerank_batch`.  With a ``query_expander``
-        every request is expanded first (``Backend/Expand``) and the text channel receives each request's list; with
-        ``dense_expanded=True`` the dense channel embeds all of those queries and makes ONE ``DenseIndex.search_groups``
-        call over the unfiltered requests and one per filtered request (``dense_filter_batch`` then has no effect).
-        With ``dense_collapse`` the dense search is ONE ``DenseIndex.search_collapsed`` over all requests at the list's
-        largest pool -- one hit per document, a prefix per request -- and ``diagnostics["dense_collapse"]`` describes
-        that call.  With ``graph_channel="neighbors"`` the graph channel is ONE ``DenseIndex.expand_neighbors`` call per
-        distinct ``graph_window`` of the list (normally one) over every request's leading dense hits, and the array
-        path carries its rows into the fusion launch."""
-        from .index import pack_sets
-        from .text_index import HipBM25TextSearcher
+        """:meth:`run` for every request of ``reqs``, in order; the diagnostics are :meth:`run`'s plus ``batch_size``.  The
+        device work of the whole list is a few calls, made by these stages (each one's docstring has its detail): every
+        request is expanded (:meth:`_expand`); the text channel, one batched BM25 search, and an injected ``graph_expand``
+        (:meth:`_text_batch`); the dense channel (:meth:`_dense_batch`), one search over all query embeddings or with
+        ``dense_mode="rerank"`` one scoring of every request's text candidates; the device graph channel
+        (:meth:`_graph_batch`); fusion in one launch over arrays (:meth:`_fuse_arrays`) where :meth:`_array_entries` can
+        build them, else over hit dicts (:meth:`_fuse_hits`); one :meth:`_diagnostics` each.  ``top_k``, ``trace_id`` and
+        the pool are each request's own: the searches run at the list's largest pool and a request uses the leading part
+        of its lists that its own pool covers (exact searches with a declared order: a prefix is the smaller search's
+        answer).  Like :meth:`run` it degrades and never raises out of the dense channel."""
         reqs = list(reqs)
         B = len(reqs)
         if not B:
@@ -766,319 +771,181 @@ class DenseRetrievalBackend:
         trace = [getattr(r, "trace_id", None) or "trace-demo" for r in reqs]
         top_k = [int(getattr(r, "top_k", None) or self.default_top_k) for r in reqs]
         pool = [max(k, self.dense_pool_k) for k in top_k]
-        pool_max = max(pool)
         expanded = [self._expand(r, trace[g]) for g, r in enumerate(reqs)]
         queries = [e[0] for e in expanded]
-
-        # ---- text and graph channels
-        text_error = None
-        if self.text_search is None and self.text_channel == "bm25":
-            try:
-                self.text_search = self._bm25_searcher()
-            except Exception as e:
-                text_error = repr(e)
-                logger.error("[DenseRetrievalBackend] BM25 channel unavailable: %s", e)
-        bm25 = self.text_channel == "bm25" and isinstance(self.text_search, HipBM25TextSearcher)
-        # only the searcher made here over index_path numbers its documents as the dense state numbers its rows (both read
-        # the file's non-empty lines in order); an injected one, even of the same length, is fused by id strings
-        own = bm25 and self.text_search is self._own_text_search
-        t_arrays = None                                  # bm25: (docs [B][k], scores [B][k], n [B]) of the batch search
-        t_hits: List[List[Dict[str, Any]]] = [[] for _ in reqs]
-        g_hits: List[List[Dict[str, Any]]] = [[] for _ in reqs]
-        if bm25:
-            with span("Backend/TextSearch", self.sink, trace[0]):
-                if self.text_search.index.N > 0:
-                    t_arrays = self.text_search.index.search_batch_arrays(queries, top_k=pool_max,
-                                                                          alpha_merge="max")
-        elif self.text_search is not None:
-            for g, r in enumerate(reqs):
-                with span("Backend/TextSearch", self.sink, trace[g]):
-                    t_hits[g] = list(self.text_search(queries=queries[g], top_k=pool[g]) or [])
-        if self.graph_expand is not None:
-            for g, r in enumerate(reqs):
-                with span("Backend/GraphExpand", self.sink, trace[g]):
-                    g_hits[g] = list(self.graph_expand(query=r.query, graph_id=getattr(r, "graph_id", "") or "",
-                                                       top_k=pool[g]) or [])
-
-        # ---- dense channel: d_ids / d_sc [B][kd], (-1, -inf) where a request has no row
-        dense_error: List[Optional[str]] = [None] * B
-        dense_filter: List[Any] = [None] * B
-        dense_collapse = None
-        k_eff = [0] * B
-        state = None
-        d_ids = np.full((B, 0), -1, dtype=np.int64)
-        d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
-        rerank = self.dense_mode == "rerank"
-        rr_hits: Optional[List[List[Dict[str, Any]]]] = None      # rerank through HipDenseReranker: the dense hits per request
-        with span("Backend/DenseRerank", self.sink, trace[0]):
-            try:
-                if rerank:
-                    state, d_ids, d_sc, k_eff, dense_error, rr_hits = self._rerank_batch(reqs, pool, trace, model_hint,
-                                                                                         t_arrays, t_hits)
-                else:
-                    state = self._get_state(model_hint, trace[0])
-                if not rerank and state["index"] is not None:
-                    ix, rows = state["index"], state["rows"]
-                    if self.dense_expanded:              # every query of every request: request g owns Q[qp[g]:qp[g + 1]]
-                        qp = np.zeros(B + 1, dtype=np.int64)
-                        np.cumsum([len(q) for q in queries], out=qp[1:])
-                        Q = self._embed_texts([q for qs in queries for q in qs], model_hint, trace[0], dim=state["dim"])
-                    else:
-                        Q = self._embed_texts([r.query for r in reqs], model_hint, trace[0], dim=state["dim"])
-                    k_one, k_many = ix.max_k(1), ix.max_k(B)
-                    d_ids = np.full((B, max(min(pool_max, len(rows)), 0)), -1, dtype=np.int64)
-                    d_sc = np.full(d_ids.shape, -np.inf, dtype=np.float32)
-                    plain = []
-                    in_sets: List[int] = []                  # dense_filter_batch: the requests that share the search_sets call
-                    set_index: Dict[bytes, int] = {}         # ... the distinct sets by content -> position in set_list
-                    set_list: List[np.ndarray] = []
-                    set_of: List[int] = []
-                    for g, r in enumerate(reqs):
-                        try:
-                            allow = self.dense_row_filter(r, rows) if self.dense_row_filter is not None else None
-                            if allow is None:
-                                plain.append(g)
-                                continue
-                            k_eff[g] = min(pool[g], len(rows), k_one)
-                            if self.dense_expanded:          # one grouped search per filtered request, as run()
-                                sc, ids = ix.search_groups(Q[qp[g]:qp[g + 1]], k_eff[g], sizes=[len(queries[g])], allow=allow)
-                                dense_filter[g] = ix.last_filter()
-                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
-                                continue
-                            if self.dense_filter_batch:
-                                set_rows = pack_sets([allow], len(rows))[1]
-                                key = set_rows.tobytes()
-                                if key not in set_index:
-                                    set_index[key] = len(set_list)
-                                    set_list.append(set_rows)
-                                in_sets.append(g)
-                                set_of.append(set_index[key])
-                                continue
-                            sc, ids = ix.search(Q[g:g + 1], k_eff[g], allow=allow)
-                            dense_filter[g] = ix.last_filter()
-                            d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
-                        except Exception as e:
-                            dense_error[g] = repr(e)
-                            d_ids[g] = -1
-                            logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
-                    if in_sets:
-                        try:
-                            sc, ids = ix.search_sets(Q[in_sets], max(k_eff[g] for g in in_sets), set_list,
-                                                     set_of=np.asarray(set_of, dtype=np.int32))
-                            for j, g in enumerate(in_sets):
-                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
-                                dense_filter[g] = {"path": "sets", "allowed": int(set_list[set_of[j]].shape[0])}
-                        except Exception as e:
-                            for g in in_sets:
-                                dense_error[g] = repr(e)
-                                d_ids[g] = -1
-                            logger.error("[DenseRetrievalBackend] dense channel failed for the filtered requests: %s", e)
-                    if plain and self.dense_expanded:
-                        # ONE grouped search at the largest pool; a request whose queries x that pool exceed the merge's
-                        # 4096 entries is searched alone at its own pool, where run() would succeed or fail as well
-                        k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
-                        alone = [g for g in plain if len(queries[g]) * k_batch > 4096]
-                        plain = [g for g in plain if len(queries[g]) * k_batch <= 4096]
-                        for g in alone:
-                            try:
-                                k_eff[g] = min(pool[g], len(rows), k_one)
-                                sc, ids = ix.search_groups(Q[qp[g]:qp[g + 1]], k_eff[g], sizes=[len(queries[g])])
-                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[0], ids[0]
-                            except Exception as e:
-                                dense_error[g] = repr(e)
-                                d_ids[g] = -1
-                                logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
-                        if plain:
-                            try:
-                                rows_of = np.concatenate([np.arange(qp[g], qp[g + 1]) for g in plain])
-                                sc, ids = ix.search_groups(Q[rows_of], k_batch, sizes=[len(queries[g]) for g in plain])
-                                for j, g in enumerate(plain):
-                                    k_eff[g] = min(pool[g], k_batch)
-                                    d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
-                            except Exception as e:
-                                for g in plain:
-                                    dense_error[g] = repr(e)
-                                    d_ids[g] = -1
-                                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
-                    elif plain:
-                        try:
-                            k_batch = min(max(pool[g] for g in plain), len(rows), k_many)
-                            if self.dense_collapse is not None:      # ONE collapsed search at the largest pool, a prefix each
-                                _, n_keys, m = self._collapse_keys(state)
-                                k_batch = min(max(pool[g] for g in plain), n_keys, k_many)
-                                sc, ids = ix.search_collapsed(Q, k_batch, return_keys=False)
-                                lc = ix.last_collapsed()
-                                dense_collapse = {"keys": n_keys, "max_rows_per_key": m, "scan_k": lc["scan_k"],
-                                                  "redone": lc["redone_queries"]}
-                            else:
-                                sc, ids = ix.search(Q[plain] if len(plain) < B else Q, k_batch)
-                            for j, g in enumerate(plain):
-                                k_eff[g] = min(pool[g], k_batch)
-                                d_sc[g, :k_eff[g]], d_ids[g, :k_eff[g]] = sc[j, :k_eff[g]], ids[j, :k_eff[g]]
-                        except Exception as e:
-                            for g in plain:
-                                dense_error[g] = repr(e)
-                                d_ids[g] = -1
-                            logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
-            except Exception as e:     # reference policy: degrade, never raise out of run() (:229-231)
-                dense_error = [repr(e)] * B
-                d_ids = np.full((B, 0), -1, dtype=np.int64)
-                d_sc = np.full((B, 0), -np.inf, dtype=np.float32)
-                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
-
-        # ---- device graph channel: ONE expand_neighbors call per distinct window of the batch (normally one); a request's
-        # seed row is padded with -1 beyond its own seeds, which changes nothing of its result
-        graph_on = self.graph_channel is not None
-        g_win = [self._graph_window_of(r) for r in reqs] if graph_on else [0] * B
-        g_error: List[Optional[str]] = [None] * B
-        g_info: List[Any] = [None] * B
-        g_n = np.zeros(B, dtype=np.int64)                # graph hits per request: the leading slots of g_rows / g_dist
-        g_rows = np.full((B, min(pool_max, 4096) if graph_on else 0), -1, dtype=np.int64)
-        g_dist = np.full(g_rows.shape, -1, dtype=np.int32)
-        if graph_on:
-            with span("Backend/GraphExpand", self.sink, trace[0]):
-                have = state is not None and state["index"] is not None and d_ids.shape[1] > 0
-                n_seeds = [0] * B
-                for g in range(B):
-                    if dense_error[g] is not None:
-                        g_error[g] = repr(RuntimeError(f"no seeds, the dense channel failed: {dense_error[g]}"))
-                    elif have:
-                        n_seeds[g] = min(self._graph_seeds_of(top_k[g], g_win[g]), k_eff[g])
-                for w in sorted({g_win[g] for g in range(B) if n_seeds[g] > 0}):
-                    grp = [g for g in range(B) if n_seeds[g] > 0 and g_win[g] == w]
-                    try:
-                        seeds = np.full((len(grp), max(n_seeds[g] for g in grp)), -1, dtype=np.int64)
-                        for j, g in enumerate(grp):
-                            seeds[j, :n_seeds[g]] = d_ids[g, :n_seeds[g]]
-                        ids, dist = self._graph_expand_rows(state, seeds, w, min(max(pool[g] for g in grp), 4096))
-                        for j, g in enumerate(grp):
-                            c = min(pool[g], 4096)       # the request's own m: a prefix of the call's (strict declared order)
-                            g_rows[g, :c], g_dist[g, :c] = ids[j, :c], dist[j, :c]
-                            g_n[g] = int((ids[j, :c] >= 0).sum())
-                    except Exception as e:
-                        for g in grp:
-                            g_error[g] = repr(e)
-                            g_rows[g], g_dist[g], g_n[g] = -1, -1, 0
-                        logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
-                for g in range(B):
-                    if g_error[g] is None:
-                        g_info[g] = {"seeds": n_seeds[g], "window": g_win[g], "max_entries": n_seeds[g] * (2 * g_win[g] + 1)}
-
-        alphas = dict(alpha_text=self.alpha_text, alpha_graph=self.alpha_graph, alpha_dense=self.alpha_dense)
-        fast = (own and self.graph_expand is None and state is not None and state["index"] is not None
-                and (t_arrays is None or len(self.text_search.index.docs) == len(state["rows"])))
-        if fast:
-            norm_keys, sorted_ids = self._norm_keys(state)
-            if t_arrays is None:
-                t_arrays = (np.full((B, 0), -1, dtype=np.int64), np.zeros((B, 0), dtype=np.float64), np.zeros(B, dtype=np.int32))
-            graph_arrays = {}
-            if graph_on:                                 # the reference's own fp64 decay values, looked up by distance
-                from .index import reference_decay
-                g_sc = np.zeros(g_rows.shape, dtype=np.float64)
-                for g in range(B):
-                    g_sc[g, :g_n[g]] = reference_decay(g_win[g])[g_dist[g, :g_n[g]]]
-                graph_arrays = dict(graph_rows=g_rows, graph_scores=g_sc, graph_n=g_n)
-            chan_ptr, keys, scores, payload = _fusion.batch_entries(t_arrays[0], t_arrays[1], t_arrays[2], d_ids, d_sc, norm_keys,
-                                                                    pool=pool, **graph_arrays)
-            sizes = chan_ptr[3::3] - chan_ptr[0:-1:3]
-            fast = int(sizes.max()) <= _fusion.FUSE_MAX_ENTRIES
-        results = []
-        if fast:
-            rows = state["rows"]
-            ok, osc, nt, ng, nd, op, n_out = _fusion.fuse_entries_device_batch(chan_ptr, keys, scores, payload, top_k=top_k,
-                                                                              device=self.device, **alphas)
-            for g in range(B):
-                hits = []
-                dist_of = dict(zip(g_rows[g, :g_n[g]].tolist(), g_dist[g, :g_n[g]].tolist())) if g_n[g] else {}
-                for i in range(int(n_out[g])):
-                    rt, rg, rd = int(op[g, i, 0]), int(op[g, i, 1]), int(op[g, i, 2])
-                    meta = _fusion.row_meta(rows[rt], "bm25") if rt >= 0 else {}
-                    if rg >= 0:                                    # the graph meta overlays the text meta, as fuse_channels does
-                        meta.update(_fusion.row_meta(rows[rg], "graph"), distance=dist_of[rg])
-                    if not meta.get("text") and rd >= 0:           # dense-only ids carry their own meta
-                        meta = _fusion.row_meta(rows[rd], "dense")
-                    meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[g, i]), float(ng[g, i]), float(nd[g, i])
-                    hits.append({"id": sorted_ids[int(ok[g, i])], "score": float(osc[g, i]), "meta": meta})
-                dk = keys[chan_ptr[3 * g + 2]:chan_ptr[3 * g + 3]]
-                results.append((hits, int(chan_ptr[3 * g + 1] - chan_ptr[3 * g]), int(np.unique(dk).shape[0])))
+        text_error = self._ensure_text_search()
+        t_arrays, t_hits, g_hits = self._text_batch(reqs, queries, pool, trace)
+        dense = self._dense_batch(reqs, queries, pool, trace, model_hint, t_arrays, t_hits)
+        graph = self._graph_batch(reqs, dense, top_k, pool, trace)
+        entries = self._array_entries(dense, graph, t_arrays, pool)
+        if entries is not None:
+            results = self._fuse_arrays(entries, dense.state, graph, top_k)
         else:
-            if t_arrays is not None:
-                dl, sl, nl = t_arrays[0].tolist(), t_arrays[1].tolist(), t_arrays[2].tolist()
-                for g in range(B):
-                    c = min(nl[g], pool[g])
-                    t_hits[g] = self.text_search._hits(list(zip(dl[g][:c], sl[g][:c])))
-            dense_norm, questions = [], []
-            for g in range(B):
-                if g_n[g]:
-                    g_hits[g] = self._graph_hits(state["rows"], g_rows[g, :g_n[g]], g_dist[g, :g_n[g]], g_win[g])
-                dense_hits = []
-                if rr_hits is not None:
-                    dense_hits = rr_hits[g]
-                elif state is not None:
-                    for s, i in zip(d_sc[g].tolist(), d_ids[g].tolist()):
-                        if i < 0:
-                            continue
-                        row = state["rows"][i]
-                        dense_hits.append({"id": _fusion.raw_hit_id(row), "score": float(s), "meta": _fusion.row_meta(row, "dense")})
-                dn = _fusion.dedupe_by_norm_id(dense_hits)
-                dense_norm.append(dn)
-                questions.append((t_hits[g], g_hits[g], {nid: h["score"] for nid, h in dn.items()}))
-            if self.fuse_on_device:
-                fused_all = _fusion.fuse_channels_device_batch(questions, top_k=10 ** 9, device=self.device, **alphas)
-            else:
-                fused_all = [_fusion.fuse_channels(*q, top_k=10 ** 9, **alphas) for q in questions]
-            for g, fused in enumerate(fused_all):
-                for h in fused:                               # dense-only ids carry their own meta
-                    if not h["meta"].get("text") and h["id"] in dense_norm[g]:
-                        meta = dict(dense_norm[g][h["id"]]["meta"])
-                        meta.update({k: v for k, v in h["meta"].items() if k.startswith("score_")})
-                        h["meta"] = meta
-                results.append((fused[:top_k[g]], len(t_hits[g]), len(dense_norm[g])))
-
+            results = self._fuse_hits(dense, graph, t_arrays, t_hits, g_hits, pool, top_k)
         out = []
         for g, (hits, n_text, n_dense) in enumerate(results):
-            diagnostics = {
-                "queries": queries[g],
-                "bm25_candidates": n_text,
-                "graph_candidates": int(g_n[g]) if graph_on else len(g_hits[g]),
-                "dense_scored": n_dense,
-                "weights": dict(alphas),
-                "pool": {"dense_pool_k": self.dense_pool_k, "final_top_k": top_k[g], "dense_pool_k_effective": k_eff[g]},
-                "resolved_embed_model": model_hint,
-                "dense_backend": "mrag_amd.DenseIndex",
-                "dense_error": dense_error[g],
-                "text_error": text_error,
-                "batch_size": B,
-            }
-            if rerank:
-                diagnostics["dense_mode"] = "rerank"
-            if dense_filter[g] is not None:
-                diagnostics["dense_filter"] = dense_filter[g]
-            if dense_collapse is not None and dense_error[g] is None:
-                diagnostics["dense_collapse"] = dense_collapse
-            if expanded[g][1] is not None:
-                diagnostics["expand_error"] = expanded[g][1]
-            if graph_on:
-                diagnostics["graph_window_used"] = g_win[g]
-                if g_info[g] is not None:
-                    diagnostics["graph_channel"] = g_info[g]
-                if g_error[g] is not None:
-                    diagnostics["graph_error"] = g_error[g]
-            out.append({"hits": hits, "diagnostics": diagnostics})
+            n_graph = int(graph.n[g]) if graph.on else len(g_hits[g])
+            of_graph = dict(graph_window_used=graph.win[g], graph_channel=graph.info[g], graph_error=graph.error[g]) if graph.on else {}
+            out.append({"hits": hits, "diagnostics": self._diagnostics(
+                queries[g], (n_text, n_graph, n_dense), top_k[g], dense.k_eff[g], model_hint, dense.error[g], text_error,
+                batch_size=B, dense_filter=dense.filter[g], dense_collapse=dense.collapse if dense.error[g] is None else None,
+                expand_error=expanded[g][1], **of_graph)})
         return out
 
-    def _rerank_batch(self, reqs, pool, trace, model_hint: str, t_arrays, t_hits):
-        """The dense channel of :meth:`run_batch` in rerank mode: ``(state, d_ids, d_sc, k_eff, dense_error, rr_hits)``.
-        Own searcher: every question's leading ``min(n, pool[g])`` documents of the batch search are scored as corpus rows
-        in ONE ``score_rows_batch`` after one ``_embed_texts`` of the queries (d_ids = those documents, d_sc = their
-        scores, for the ``batch_entries`` path).  Otherwise one ``HipDenseReranker.score_batch`` over the requests' text
-        hits (``rr_hits``: its scores as dense hits).  The choice is :meth:`_rerank_one`'s.  Requests without candidates
-        have an empty dense channel and no error; a failure is reported for the others and never raised."""
+    def _text_batch(self, reqs, queries, pool, trace):
+        """The text channel and an injected graph channel of a batch -> ``(t_arrays, t_hits, g_hits)``.  A BM25 searcher answers
+        every request in ONE ``search_batch_arrays`` at the list's largest pool: ``t_arrays = (docs [B][k], scores [B][k],
+        n [B])``, None when its index is empty.  Any other ``text_search``, and ``graph_expand``, are called per request."""
+        from .text_index import HipBM25TextSearcher
+        t_arrays = None
+        t_hits: List[List[Dict[str, Any]]] = [[] for _ in reqs]
+        if self.text_channel == "bm25" and isinstance(self.text_search, HipBM25TextSearcher):
+            with span("Backend/TextSearch", self.sink, trace[0]):
+                if self.text_search.index.N > 0:
+                    t_arrays = self.text_search.index.search_batch_arrays(queries, top_k=max(pool), alpha_merge="max")
+        elif self.text_search is not None:
+            for g in range(len(reqs)):
+                with span("Backend/TextSearch", self.sink, trace[g]):
+                    t_hits[g] = list(self.text_search(queries=queries[g], top_k=pool[g]) or [])
+        return t_arrays, t_hits, [self._graph_expand_hits(r, pool[g], trace[g]) for g, r in enumerate(reqs)]
+
+    def _text_hits(self, t_arrays, pool) -> List[List[Dict[str, Any]]]:
+        """the batched BM25 search's arrays as hits: per request the leading part that its own pool covers"""
+        docs, scores, n = (a.tolist() for a in t_arrays)
+        return [self.text_search._hits(list(zip(docs[g][:min(n[g], p)], scores[g][:min(n[g], p)]))) for g, p in enumerate(pool)]
+
+    def _dense_batch(self, reqs, queries, pool, trace, model_hint: str, t_arrays, t_hits) -> _Dense:
+        """The dense channel of a batch under its one ``Backend/DenseRerank`` span.  An exception that escapes its stage fails
+        every request, is logged and never raised (the reference's policy, :229-231)."""
+        dense = _Dense.empty(len(reqs))
+        with span("Backend/DenseRerank", self.sink, trace[0]):
+            try:
+                if self.dense_mode == "rerank":
+                    dense = self._rerank_batch(reqs, pool, trace, model_hint, t_arrays, t_hits)
+                else:
+                    dense.state = self._get_state(model_hint, trace[0])
+                    if dense.state["index"] is not None:
+                        self._search_batch(dense, reqs, queries, pool, trace, model_hint)
+            except Exception as e:
+                dense = _Dense.empty(len(reqs), dense.state, repr(e))
+                logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
+        return dense
+
+    @staticmethod
+    def _search_requests(dense: _Dense, who, caps, call, label: str = ""):
+        """ONE index call for the requests ``who``.  ``call() -> (scores, ids, info)``: row j of the result is request
+        ``who[j]``'s, which takes its leading ``k_eff = min(caps[j], the result's width)`` slots -> ``info``.  If the
+        call raises, exactly those requests report the error and lose their rows, it is logged once, and None returns."""
+        try:
+            sc, ids, info = call()
+            for j, g in enumerate(who):
+                dense.k_eff[g] = k = min(caps[j], sc.shape[1])
+                dense.sc[g, :k], dense.ids[g, :k] = sc[j, :k], ids[j, :k]
+            return info
+        except Exception as e:
+            DenseRetrievalBackend._fail(dense, who, e, label)
+            return None
+
+    def _search_batch(self, dense: _Dense, reqs, queries, pool, trace, model_hint: str) -> None:
+        """The corpus-wide dense search of a batch, into ``dense``.  One :meth:`_embed_texts` embeds all queries -- with
+        ``dense_expanded`` every query of every request -- and the requests are searched in three classes, in this order,
+        each call through :meth:`_search_requests`.  *Filtered* (``dense_row_filter`` gave a set): one :meth:`_search_one`
+        each with its ``allow`` at its own pool; with ``dense_filter_batch`` and without ``dense_expanded``, all in
+        :meth:`_search_sets`.  *Alone* (``dense_expanded``: its queries x the batch's k exceed the merge's 4096 entries): one
+        grouped search at its own pool, where :meth:`run` would succeed or fail as well.  *Together*, the others, in ONE call
+        at their largest pool, a prefix each: ``search_groups``, :meth:`_search_collapsed` (``dense.collapse`` describes
+        it) or ``search``.  A request whose own search fails still reports its ``k_eff``; those of a failed shared call report 0."""
+        state, ix, rows = dense.state, dense.state["index"], dense.state["rows"]
+        B, n = len(reqs), len(rows)
+        sizes = [len(q) for q in queries] if self.dense_expanded else [1] * B
+        texts = [q for qs in queries for q in qs] if self.dense_expanded else [r.query for r in reqs]
+        Q = self._embed_texts(texts, model_hint, trace[0], dim=state["dim"])
+        qp = np.zeros(B + 1, dtype=np.int64)             # request g owns Q[qp[g]:qp[g + 1]]
+        np.cumsum(sizes, out=qp[1:])
+        k_one, k_many = ix.max_k(1), ix.max_k(B)
+        dense.ids = np.full((B, max(min(max(pool), n), 0)), -1, dtype=np.int64)
+        dense.sc = np.full(dense.ids.shape, -np.inf, dtype=np.float32)
+        own_k = [min(p, n, k_one) for p in pool]
+        in_sets = self.dense_filter_batch and not self.dense_expanded
+
+        def alone(g, allow=None):                        # one request at its own pool
+            dense.k_eff[g] = k = own_k[g]
+            return self._search_requests(dense, [g], [k], lambda: self._search_one(ix, Q[qp[g]:qp[g + 1]], k, allow),
+                                         f" for request {g}")
+        allow = self._allow_sets(dense, reqs, rows, own_k, packed=in_sets)
+        if allow and in_sets:
+            self._search_sets(dense, Q, allow)
+        else:
+            for g, a in allow.items():
+                dense.filter[g] = alone(g, a)
+        plain = [g for g in range(B) if g not in allow and dense.error[g] is None]
+        k_batch = min(max((pool[g] for g in plain), default=0), n, k_many)
+        if self.dense_expanded:
+            for g in [g for g in plain if sizes[g] * k_batch > 4096]:
+                alone(g)
+            plain = [g for g in plain if sizes[g] * k_batch <= 4096]
+
+            def call():
+                mine = np.concatenate([np.arange(qp[g], qp[g + 1]) for g in plain])
+                return (*ix.search_groups(Q[mine], k_batch, sizes=[sizes[g] for g in plain]), None)
+        elif self.dense_collapse is not None:
+            def call():
+                return self._search_collapsed(state, Q, min(max(pool[g] for g in plain), self._row_keys(state, self.dense_collapse)[1], k_many))
+        else:
+            def call():
+                return (*ix.search(Q[plain] if len(plain) < B else Q, k_batch), None)
+        if plain:
+            dense.collapse = self._search_requests(dense, plain, [pool[g] for g in plain], call)
+
+    @staticmethod
+    def _fail(dense: _Dense, who, e: Exception, label: str = "") -> None:
+        """the requests ``who`` report ``e`` and lose their rows; one log line"""
+        for g in who:
+            dense.error[g] = repr(e)
+            dense.ids[g] = -1
+        logger.error("[DenseRetrievalBackend] dense channel failed%s: %s", label, e)
+
+    def _allow_sets(self, dense: _Dense, reqs, rows, own_k, packed: bool) -> Dict[int, Any]:
+        """``dense_row_filter`` for every request of a batch -> ``{g: its allow-set}`` for those it restricts, which are then
+        searched at their own ``k_eff = own_k[g]``; ``packed``: the sets as sorted row positions (``pack_sets``).  The
+        callbacks do not touch the index; one that raises, or whose set cannot be packed, fails its own request only."""
+        from .index import pack_sets
+        allow: Dict[int, Any] = {}
+        for g, r in enumerate(reqs if self.dense_row_filter is not None else []):
+            try:
+                got = self.dense_row_filter(r, rows)
+                if got is not None:
+                    dense.k_eff[g] = own_k[g]
+                    allow[g] = pack_sets([got], len(rows))[1] if packed else got
+            except Exception as e:
+                self._fail(dense, [g], e, f" for request {g}")
+        return allow
+
+    def _search_sets(self, dense: _Dense, Q, packed: Dict[int, np.ndarray]) -> None:
+        """``dense_filter_batch``: ONE ``search_sets`` for the filtered requests, at the largest of their ``k_eff``; sets of
+        equal content are shared, and the diagnostics read ``dense_filter = {"path": "sets", "allowed": m}``."""
+        who, set_of, set_list, index_of = list(packed), [], [], {}      # index_of: a set's content -> its position in set_list
+        for g in who:
+            at = index_of.setdefault(packed[g].tobytes(), len(set_list))
+            if at == len(set_list):
+                set_list.append(packed[g])
+            set_of.append(at)
+        caps = [dense.k_eff[g] for g in who]
+
+        def call():
+            return (*dense.state["index"].search_sets(Q[who], max(caps), set_list, set_of=np.asarray(set_of, dtype=np.int32)), True)
+        if self._search_requests(dense, who, caps, call, " for the filtered requests"):
+            for j, g in enumerate(who):
+                dense.filter[g] = {"path": "sets", "allowed": int(set_list[set_of[j]].shape[0])}
+
+    def _rerank_batch(self, reqs, pool, trace, model_hint: str, t_arrays, t_hits) -> _Dense:
+        """The dense channel of a batch in rerank mode.  Own searcher: every question's leading ``min(n, pool[g])`` documents
+        of the batch search are scored as corpus rows in ONE ``score_rows_batch`` after one ``_embed_texts`` of the queries
+        (``ids`` = those documents, ``sc`` = their scores, for the array fusion).  Otherwise one ``HipDenseReranker.score_batch``
+        over the requests' text hits (``hits``: its scores as dense hits).  The choice is :meth:`_rerank_one`'s.  Requests
+        without candidates have an empty dense channel and no error; a failure is reported for the others, never raised."""
         B = len(reqs)
-        state, rr_hits = None, None
-        d_ids, d_sc = np.full((B, 0), -1, dtype=np.int64), np.full((B, 0), -np.inf, dtype=np.float32)
-        k_eff: List[int] = [0] * B
-        dense_error: List[Optional[str]] = [None] * B
+        dense = _Dense.empty(B)
         own = self._is_own_searcher()
         if t_arrays is not None:                     # a batched BM25 search: the backend's own searcher or an injected one
             n_c = [min(int(n), pool[g]) for g, n in enumerate(t_arrays[2].tolist())]
@@ -1088,54 +955,186 @@ class DenseRetrievalBackend:
             n_c = [len(t_hits[g][:pool[g]]) for g in range(B)]
         live = [g for g in range(B) if n_c[g] > 0]
         if not live:
-            return state, d_ids, d_sc, k_eff, dense_error, rr_hits
+            return dense
         try:
             by_row = False
             if own:
-                state = self._get_state(model_hint, trace[0])
-                by_row = self._rows_are_docs(state)
+                dense.state = self._get_state(model_hint, trace[0])
+                by_row = self._rows_are_docs(dense.state)
             if by_row:
-                try:
-                    Q = self._embed_texts([reqs[g].query for g in live], model_hint, trace[0], dim=state["dim"])
-                except Exception:                        # one bad vector fails its chunk: find out whose, as run() would
-                    good, vecs = [], []
-                    for g in live:
-                        try:
-                            vecs.append(self._embed_texts([reqs[g].query], model_hint, trace[g], dim=state["dim"])[0])
-                            good.append(g)
-                        except Exception as e:
-                            dense_error[g] = repr(e)
-                            logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
-                    live, Q = good, np.asarray(vecs, dtype=np.float32).reshape(len(good), state["dim"])
-                ptr = np.zeros(len(live) + 1, dtype=np.int64)
-                np.cumsum([n_c[g] for g in live], out=ptr[1:])
-                flat = np.concatenate([t_arrays[0][g, :n_c[g]] for g in live]) if live else np.zeros(0, dtype=np.int64)
-                _, sc = state["index"].score_rows_batch(Q, (ptr, flat))
-                ids_out = np.full(t_arrays[0].shape, -1, dtype=np.int64)
-                sc_out = np.full(t_arrays[0].shape, -np.inf, dtype=np.float32)
-                for j, g in enumerate(live):
-                    ids_out[g, :n_c[g]], sc_out[g, :n_c[g]] = flat[ptr[j]:ptr[j + 1]], sc[ptr[j]:ptr[j + 1]]
-                    k_eff[g] = n_c[g]
-                d_ids, d_sc = ids_out, sc_out
+                self._rerank_rows(dense, reqs, live, n_c, t_arrays, trace, model_hint)
             else:
                 if t_arrays is not None:                 # an injected BM25 searcher, or documents that are not the state's
-                    dl, sl = t_arrays[0].tolist(), t_arrays[1].tolist()      # rows: the hits, scored by id and text
-                    for g in range(B):
-                        t_hits[g] = self.text_search._hits(list(zip(dl[g][:n_c[g]], sl[g][:n_c[g]])))
+                    t_hits[:] = self._text_hits(t_arrays, pool)              # rows: the hits, scored by id and text
                 cands = [t_hits[g][:pool[g]] for g in range(B)]
                 rr = HipDenseReranker(self.router, max_pool=max(pool), embed_batch=self.embed_batch, device=self.device,
                                       corpus=self)
                 scores = rr.score_batch(queries=[r.query for r in reqs], candidates=cands, trace_ids=trace)
-                rr_hits = [self._scored_hits(c, s) for c, s in zip(cands, scores)]
-                k_eff = [len(h) for h in rr_hits]
+                dense.hits = [self._scored_hits(c, s) for c, s in zip(cands, scores)]
+                dense.k_eff = [len(h) for h in dense.hits]
         except Exception as e:
-            state, rr_hits = None, None
-            d_ids, d_sc = np.full((B, 0), -1, dtype=np.int64), np.full((B, 0), -np.inf, dtype=np.float32)
-            k_eff = [0] * B
-            for g in live:
-                dense_error[g] = repr(e)
+            error = [repr(e) if g in live and err is None else err for g, err in enumerate(dense.error)]
+            dense = _Dense.empty(B)                      # what single requests reported before stays
+            dense.error = error
             logger.error("[DenseRetrievalBackend] dense channel failed: %s", e)
-        return state, d_ids, d_sc, k_eff, dense_error, rr_hits
+        return dense
+
+    def _rerank_rows(self, dense: _Dense, reqs, live, n_c, t_arrays, trace, model_hint: str) -> None:
+        """the own searcher's documents ``t_arrays[0][g, :n_c[g]]`` of the requests ``live``, scored as corpus rows, into ``dense``"""
+        state = dense.state
+        try:
+            Q = self._embed_texts([reqs[g].query for g in live], model_hint, trace[0], dim=state["dim"])
+        except Exception:                                # one bad vector fails its chunk: find out whose, as run() would
+            good, vecs = [], []
+            for g in live:
+                try:
+                    vecs.append(self._embed_texts([reqs[g].query], model_hint, trace[g], dim=state["dim"])[0])
+                    good.append(g)
+                except Exception as e:
+                    dense.error[g] = repr(e)
+                    logger.error("[DenseRetrievalBackend] dense channel failed for request %d: %s", g, e)
+            live, Q = good, np.asarray(vecs, dtype=np.float32).reshape(len(good), state["dim"])
+        ptr = np.zeros(len(live) + 1, dtype=np.int64)
+        np.cumsum([n_c[g] for g in live], out=ptr[1:])
+        flat = np.concatenate([t_arrays[0][g, :n_c[g]] for g in live]) if live else np.zeros(0, dtype=np.int64)
+        _, sc = state["index"].score_rows_batch(Q, (ptr, flat))
+        dense.ids = np.full(t_arrays[0].shape, -1, dtype=np.int64)
+        dense.sc = np.full(t_arrays[0].shape, -np.inf, dtype=np.float32)
+        for j, g in enumerate(live):
+            dense.ids[g, :n_c[g]], dense.sc[g, :n_c[g]] = flat[ptr[j]:ptr[j + 1]], sc[ptr[j]:ptr[j + 1]]
+            dense.k_eff[g] = n_c[g]
+
+    def _graph_batch(self, reqs, dense: _Dense, top_k, pool, trace) -> _Graph:
+        """The device graph channel of a batch (``graph_channel="neighbors"``), after the dense stage that gives the seeds: ONE
+        ``expand_neighbors`` call per distinct window of the batch (normally one) over every request's leading dense hits.  A
+        seed row is padded with -1 beyond the request's own seeds, which changes nothing of its result, and the request takes
+        its own ``m = min(pool, 4096)`` as a prefix of the call's (strict declared order).  A request whose dense channel
+        failed has no seeds and reports that; a failing call is reported by the requests of its window."""
+        B, on = len(reqs), self.graph_channel is not None
+        rows = np.full((B, min(max(pool), 4096) if on else 0), -1, dtype=np.int64)
+        graph = _Graph(on, [self._graph_window_of(r) for r in reqs] if on else [0] * B, [None] * B, [None] * B,
+                       np.zeros(B, dtype=np.int64), rows, np.full(rows.shape, -1, dtype=np.int32))
+        if not on:
+            return graph
+        win = graph.win
+        with span("Backend/GraphExpand", self.sink, trace[0]):
+            have = dense.state is not None and dense.state["index"] is not None and dense.ids.shape[1] > 0
+            n_seeds = [0] * B
+            for g in range(B):
+                if dense.error[g] is not None:
+                    graph.error[g] = repr(RuntimeError(f"no seeds, the dense channel failed: {dense.error[g]}"))
+                elif have:
+                    n_seeds[g] = self._graph_seeds_of(top_k[g], win[g], dense.k_eff[g])
+            for w in sorted({win[g] for g in range(B) if n_seeds[g] > 0}):
+                grp = [g for g in range(B) if n_seeds[g] > 0 and win[g] == w]
+                try:
+                    seeds = np.full((len(grp), max(n_seeds[g] for g in grp)), -1, dtype=np.int64)
+                    for j, g in enumerate(grp):
+                        seeds[j, :n_seeds[g]] = dense.ids[g, :n_seeds[g]]
+                    ids, dist = self._graph_expand_rows(dense.state, seeds, w, min(max(pool[g] for g in grp), 4096))
+                    for j, g in enumerate(grp):
+                        c = min(pool[g], 4096)
+                        graph.rows[g, :c], graph.dist[g, :c] = ids[j, :c], dist[j, :c]
+                        graph.n[g] = int((ids[j, :c] >= 0).sum())
+                except Exception as e:
+                    for g in grp:
+                        graph.error[g] = repr(e)
+                        graph.rows[g], graph.dist[g], graph.n[g] = -1, -1, 0
+                    logger.error("[DenseRetrievalBackend] graph channel failed: %s", e)
+            graph.info = [self._graph_record(n_seeds[g], win[g]) if graph.error[g] is None else None for g in range(B)]
+        return graph
+
+    # -- fusion of a batch ------------------------------------------------------------------------------------------------
+    def _norm_keys(self, state):
+        """``fusion.corpus_norm_keys`` of the state's rows, built once per state and kept in it."""
+        if "norm_keys" not in state:
+            state["norm_keys"] = _fusion.corpus_norm_keys(state["rows"])
+        return state["norm_keys"]
+
+    def _alphas(self) -> Dict[str, float]:
+        return dict(alpha_text=self.alpha_text, alpha_graph=self.alpha_graph, alpha_dense=self.alpha_dense)
+
+    def _array_entries(self, dense: _Dense, graph: _Graph, t_arrays, pool):
+        """The choice between the two fusion paths -> the entries of the array path (``fusion.batch_entries``), or None for
+        the hit-dict path.  Arrays need every channel as corpus rows: the text channel is the searcher this backend made
+        over ``index_path`` (only it numbers its documents as the dense state numbers its rows; an injected one, even of
+        the same length, is fused by id strings), there is no injected ``graph_expand``, the dense index exists, and no
+        request has more than ``FUSE_MAX_ENTRIES`` entries.  ``fuse_on_device`` plays no part in this choice."""
+        state = dense.state
+        if not (self._is_own_searcher() and self.graph_expand is None and state is not None and state["index"] is not None
+                and (t_arrays is None or len(self.text_search.index.docs) == len(state["rows"]))):
+            return None
+        B = len(pool)
+        if t_arrays is None:
+            t_arrays = (np.full((B, 0), -1, dtype=np.int64), np.zeros((B, 0), dtype=np.float64), np.zeros(B, dtype=np.int32))
+        graph_arrays = {}
+        if graph.on:                                     # the reference's own fp64 decay values, looked up by distance
+            from .index import reference_decay
+            g_sc = np.zeros(graph.rows.shape, dtype=np.float64)
+            for g in range(B):
+                g_sc[g, :graph.n[g]] = reference_decay(graph.win[g])[graph.dist[g, :graph.n[g]]]
+            graph_arrays = dict(graph_rows=graph.rows, graph_scores=g_sc, graph_n=graph.n)
+        entries = _fusion.batch_entries(t_arrays[0], t_arrays[1], t_arrays[2], dense.ids, dense.sc, self._norm_keys(state)[0],
+                                        pool=pool, **graph_arrays)
+        chan_ptr = entries[0]
+        sizes = chan_ptr[3::3] - chan_ptr[0:-1:3]
+        return entries if int(sizes.max()) <= _fusion.FUSE_MAX_ENTRIES else None
+
+    def _fuse_arrays(self, entries, state, graph: _Graph, top_k):
+        """ONE ``mrag_fuse_topk_batch`` launch over :meth:`_array_entries` -> per request ``(hits, text candidates, dense
+        candidates)``.  The meta comes from the corpus rows the payload names, overlaid as ``run`` overlays the channels."""
+        chan_ptr, keys, scores, payload = entries
+        rows, sorted_ids = state["rows"], self._norm_keys(state)[1]
+        ok, osc, nt, ng, nd, op, n_out = _fusion.fuse_entries_device_batch(chan_ptr, keys, scores, payload, top_k=top_k,
+                                                                          device=self.device, **self._alphas())
+        results = []
+        for g in range(len(top_k)):
+            hits = []
+            n_g = graph.n[g]
+            dist_of = dict(zip(graph.rows[g, :n_g].tolist(), graph.dist[g, :n_g].tolist())) if n_g else {}
+            for i in range(int(n_out[g])):
+                rt, rg, rd = int(op[g, i, 0]), int(op[g, i, 1]), int(op[g, i, 2])
+                meta = _fusion.row_meta(rows[rt], "bm25") if rt >= 0 else {}
+                if rg >= 0:                                    # the graph meta overlays the text meta, as fuse_channels does
+                    meta.update(_fusion.row_meta(rows[rg], "graph"), distance=dist_of[rg])
+                if not meta.get("text") and rd >= 0:           # dense-only ids carry their own meta
+                    meta = _fusion.row_meta(rows[rd], "dense")
+                meta["score_text_norm"], meta["score_graph_norm"], meta["score_dense_norm"] = float(nt[g, i]), float(ng[g, i]), float(nd[g, i])
+                hits.append({"id": sorted_ids[int(ok[g, i])], "score": float(osc[g, i]), "meta": meta})
+            dk = keys[chan_ptr[3 * g + 2]:chan_ptr[3 * g + 3]]
+            results.append((hits, int(chan_ptr[3 * g + 1] - chan_ptr[3 * g]), int(np.unique(dk).shape[0])))
+        return results
+
+    def _fuse_hits(self, dense: _Dense, graph: _Graph, t_arrays, t_hits, g_hits, pool, top_k):
+        """Fusion over hit dicts, as :meth:`run` fuses -> per request ``(hits, text candidates, dense candidates)``.  What
+        the stages left as arrays becomes hits first (``t_hits`` / ``g_hits`` are filled in place); then one
+        ``fuse_channels_device_batch`` with ``fuse_on_device``, else ``fuse_channels`` per request."""
+        B, state = len(top_k), dense.state
+        if t_arrays is not None:
+            t_hits[:] = self._text_hits(t_arrays, pool)
+        dense_norm, questions = [], []
+        for g in range(B):
+            n_g = graph.n[g]
+            if n_g:
+                g_hits[g] = self._graph_hits(state["rows"], graph.rows[g, :n_g], graph.dist[g, :n_g], graph.win[g])
+            if dense.hits is not None:
+                dense_hits = dense.hits[g]
+            else:
+                dense_hits = self._dense_hits(state["rows"], dense.sc[g].tolist(), dense.ids[g].tolist()) if state is not None else []
+            dn = _fusion.dedupe_by_norm_id(dense_hits)
+            dense_norm.append(dn)
+            questions.append((t_hits[g], g_hits[g], {nid: h["score"] for nid, h in dn.items()}))
+        if self.fuse_on_device:
+            fused_all = _fusion.fuse_channels_device_batch(questions, top_k=10 ** 9, device=self.device, **self._alphas())
+        else:
+            fused_all = [_fusion.fuse_channels(*q, top_k=10 ** 9, **self._alphas()) for q in questions]
+        return [(self._fuse_overlay(fused, dense_norm[g], top_k[g]), len(t_hits[g]), len(dense_norm[g]))
+                for g, fused in enumerate(fused_all)]
+
+    def retrieve(self, req) -> RetrievalOut:
+        result = self.run(req)
+        hits = [Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]]
+        return RetrievalOut(hits=hits, diagnostics=result.get("diagnostics", {}))
 
     def retrieve_batch(self, reqs) -> List[RetrievalOut]:
         return [RetrievalOut(hits=[Hit(id=h["id"], score=h["score"], meta=h.get("meta") or {}) for h in result["hits"]],
