@@ -137,13 +137,6 @@ int filter_choose_path(int64_t nq, int k, int64_t n, int64_t m, int ld) {
 }
 
 // ---- filtered search over prepared operands (mrag_index_search_filtered, and the exact path of mrag_ivf_search_filtered)
-void FilterWork::release() {
-  fbits.release(); fwork.release(); fcomp.release();
-  if (ev_fbits) (void)hipEventDestroy(ev_fbits);
-  if (h_fbits) (void)hipHostFree(h_fbits);
-  ev_fbits = nullptr; h_fbits = nullptr; h_fbits_words = 0;
-}
-
 // layout of FilterWork::fwork: allowed count (word 0) | per-block counts at byte 256 | ascending allowed rows
 static int64_t filter_nwords(int64_t n) { return round_up(std::max<int64_t>(n, 1), TM) / 32; }   // bitset padded to whole tiles (the kernels read 8 words per tile)
 static int filter_nblk(int64_t n) { return (int)((filter_nwords(n) + FW_BLOCK - 1) / FW_BLOCK); }
@@ -174,16 +167,10 @@ int filter_upload(FilterWork& w, const void* allow, int64_t n, int allow_format,
     m = 0;
   } else if (!allow_is_device) {
     // host allow-set: packed and counted here, no read-back
-    if (!w.ev_fbits) MRAG_HIP(hipEventCreateWithFlags(&w.ev_fbits, hipEventDisableTiming));
+    if (!w.ev_fbits) MRAG_TRY(w.ev_fbits.create(false));
     else MRAG_HIP(hipEventSynchronize(w.ev_fbits));       // the previous copy out of the staging buffer is done
-    if (w.h_fbits_words < (size_t)nwords) {
-      if (w.h_fbits) MRAG_HIP(hipHostFree(w.h_fbits));
-      w.h_fbits = nullptr;
-      w.h_fbits_words = 0;
-      MRAG_HIP(hipHostMalloc((void**)&w.h_fbits, (size_t)nwords * 4, hipHostMallocDefault));
-      w.h_fbits_words = (size_t)nwords;
-    }
-    uint32_t* hb = w.h_fbits;
+    MRAG_TRY(w.h_fbits.ensure((size_t)nwords * 4));
+    uint32_t* hb = (uint32_t*)w.h_fbits.p;
     memset(hb, 0, (size_t)nwords * 4);
     if (allow_format == MRAG_ALLOW_BITS32) {
       memcpy(hb, allow, (size_t)in_words * 4);

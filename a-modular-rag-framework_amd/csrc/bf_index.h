@@ -1,6 +1,6 @@
 // The host side of the dense index, for the bf_*.hip sources that hold an mrag_index_* entry point: the BfIndex object, the
 // DenseSearch call object, the two internal searches over an index pointer (bf_index.hip) and the small pieces the composite
-// searches are built from -- argument checks, run_synced, ListScratch, OutTriple, scatter_rows, LastCall.  Host only; the
+// searches are built from -- argument checks, ListScratch, OutTriple, scatter_rows, LastCall.  Host only; the
 // kernels' shared declarations are in bf_kernels.h.
 #pragma once
 #include "bf_kernels.h"
@@ -8,10 +8,6 @@
 namespace mrag {
 
 // ---- argument checks ----
-static inline size_t dtype_size(int dt) {
-  switch (dt) { case MRAG_F32: return 4; case MRAG_F16: case MRAG_BF16: return 2; case MRAG_F64: return 8; default: return 0; }
-}
-
 // nq and k of the exact dense searches
 static inline int check_nq_k(int64_t nq, int k) {
   if (nq < 0) return fail(MRAG_ERR_INVALID, "nq < 0");
@@ -40,19 +36,6 @@ static inline int check_csr(const int64_t* ptr, int64_t n, const char* name, con
 }
 
 // ---- pieces of a call ----
-// Runs `enqueue` and synchronises the stream whatever it returns: asynchronous copies that read host vectors or the
-// caller's host buffers have finished before those go out of scope.  Returns the first failure.
-template <class F>
-static inline int run_synced(hipStream_t stream, F&& enqueue) {
-  const int status = enqueue();
-  if (status != MRAG_OK) {
-    (void)hipStreamSynchronize(stream);
-    return status;
-  }
-  MRAG_HIP(hipStreamSynchronize(stream));
-  return MRAG_OK;
-}
-
 // n (id, score) list entries in one device buffer, laid out (int64 ids | float scores)
 struct ListScratch {
   int64_t* ids = nullptr;
@@ -138,7 +121,6 @@ struct SetsState {
   DevBuf rows;       // the scanned sets' rows
   DevBuf S;          // the score segments
   LastCall last;     // scanned questions, routed questions, descriptors
-  ~SetsState() { q.release(); plan.release(); rows.release(); S.release(); }
 };
 
 // grouped queries (mrag_index_search_groups, bf_groups.hip)
@@ -148,7 +130,6 @@ struct GroupsState {
   DevBuf out;                   // the merged rows of a call with host outputs (ids | scores | which)
   std::vector<int64_t> host;
   LastCall last;                // queries, questions, entries of the largest question
-  ~GroupsState() { in.release(); ptr.release(); out.release(); }
 };
 
 // neighbour expansion (mrag_index_expand_neighbors, bf_neighbors.hip); its row keys are CollapseState's
@@ -157,7 +138,6 @@ struct NeighborsState {
   DevBuf out;                   // the rows of a call with host outputs (ids | scores | dist | seed) ...
   std::vector<char> host;       // ... and their host copy, downloaded in one piece
   LastCall last;                // questions, entries of the largest question, window
-  ~NeighborsState() { seeds.release(); out.release(); }
 };
 
 // collapsed search (mrag_index_search_collapsed, bf_collapse.hip)
@@ -171,26 +151,25 @@ struct CollapseState {
   std::vector<int32_t> host;
   DevBuf out;                             // the [nq][k] results (ids | scores | keys) the caller's buffers do not hold
   LastCall last;                          // scan_k, redone queries, redo searches
-  ~CollapseState() { keys.release(); in.release(); redo.release(); mask.release(); words.release(); out.release(); }
 };
 
 struct BfIndex : Object {
   int dim = 0, ld = 0, metric = 0, dtype = MRAG_F16;
   int64_t n = 0, cap_rows = 0, id_base = 0;
-  uint16_t* rows = nullptr;
+  DevArray<uint16_t> rows;                  // [cap_rows][ld]
   DevBuf qbuf, lists, counts, stage_in, out_sc, out_id, clock;
   DevBuf rslots, out_cnt;                   // range search: per-(workgroup, query) count slots; counts for host outputs
   FilterWork fw;                            // filtered search: allow bitset, counts, compacted rows
   int last_fpath = -1;                      // path of the last filtered search (MRAG_FILTER_MASK / _COMPACT), -1 = none
   int64_t last_fallowed = -1;               // its allowed-row count; -1 = still on the device (fwork word 0, read on demand)
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev[4];
   bool timed = false, want_clock = false;
   void* q_cleared_buf = nullptr;            // query buffer bookkeeping: rows [q_dirty_rows, q_cleared_rows) are known to be zero
   int64_t q_cleared_rows = 0, q_dirty_rows = 0;
   // fp8 scan copy (mrag_index_enable_fp8): rows8 [cap_rows][ld8], kept in step with `rows` by add / reserve
   bool fp8 = false;
   int ld8 = 0;
-  uint8_t* rows8 = nullptr;
+  DevArray<uint8_t> rows8;
   DevBuf qbuf8, cand;                       // quantised queries [nq padded][ld8]; candidates (fp8 scores | local rows)
   int last_refine = -1, last_regime = -1;   // of the last mrag_index_search_fp8
   DevBuf rr_q;                              // batched re-rank: its prepared queries [n_questions][ld] -- not qbuf, whose zero-padding
@@ -199,15 +178,6 @@ struct BfIndex : Object {
   GroupsState groups;
   NeighborsState neighbors;
   CollapseState collapse;
-  ~BfIndex() override {
-    if (rows) (void)hipFree(rows);
-    if (rows8) (void)hipFree(rows8);
-    qbuf8.release(); cand.release(); rr_q.release();
-    qbuf.release(); lists.release(); counts.release(); stage_in.release(); out_sc.release(); out_id.release(); clock.release();
-    rslots.release(); out_cnt.release();
-    fw.release();   // (the destroy path synchronised the device)
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  }
 };
 
 // One call of a dense search entry point: the plumbing bf_search, search_allowed and mrag_index_search_fp8 share around

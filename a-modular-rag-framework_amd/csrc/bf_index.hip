@@ -33,29 +33,22 @@ static int grow_rows(BfIndex* ix, int64_t need_rows, hipStream_t stream) {
   if (need_rows <= ix->cap_rows) return MRAG_OK;
   int64_t cap = std::max<int64_t>(need_rows, ix->cap_rows + ix->cap_rows / 2);
   cap = round_up(std::max<int64_t>(cap, TM), TM);
-  uint16_t* nr = nullptr;
+  // the new owners, filled and settled, then moved into place: a failure part-way leaves the index as it was
+  DevArray<uint16_t> nr;
+  DevArray<uint8_t> nr8;
   const size_t bytes = (size_t)cap * ix->ld * 2;
-  hipError_t e = hipMalloc((void**)&nr, bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for corpus rows failed: %s", bytes, hipGetErrorString(e)); }
+  MRAG_TRY(nr.alloc(bytes, "corpus rows"));
   MRAG_HIP(hipMemsetAsync(nr, 0, bytes, stream));
   if (ix->rows && ix->n > 0) MRAG_HIP(hipMemcpyAsync(nr, ix->rows, (size_t)ix->n * ix->ld * 2, hipMemcpyDeviceToDevice, stream));
-  uint8_t* nr8 = nullptr;
   if (ix->fp8) {   // the fp8 copy grows with the rows
     const size_t bytes8 = (size_t)cap * ix->ld8;
-    e = hipMalloc((void**)&nr8, bytes8);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(stream);
-      (void)hipFree(nr);
-      return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for the fp8 rows failed: %s", bytes8, hipGetErrorString(e));
-    }
+    MRAG_TRY(nr8.alloc(bytes8, "the fp8 rows"));
     MRAG_HIP(hipMemsetAsync(nr8, 0, bytes8, stream));
     if (ix->rows8 && ix->n > 0) MRAG_HIP(hipMemcpyAsync(nr8, ix->rows8, (size_t)ix->n * ix->ld8, hipMemcpyDeviceToDevice, stream));
   }
-  if (ix->rows) { MRAG_HIP(hipStreamSynchronize(stream)); (void)hipFree(ix->rows); }
-  if (ix->rows8) (void)hipFree(ix->rows8);   // (synchronised above: rows8 exists only next to rows)
-  ix->rows = nr;
-  ix->rows8 = nr8;
+  if (ix->rows) MRAG_HIP(hipStreamSynchronize(stream));   // (the old rows are freed behind the copies out of them)
+  ix->rows.swap(nr);
+  ix->rows8.swap(nr8);
   ix->cap_rows = cap;
   return MRAG_OK;
 }
@@ -412,21 +405,15 @@ int mrag_index_create(int dim, int metric, int storage_dtype, int device, mrag_h
   ix->ld8 = (int)round_up(dim, FP8_K);
   ix->metric = metric;
   ix->dtype = storage_dtype;
-  for (auto& e : ix->ev) {
-    if (hipEventCreate(&e) != hipSuccess) { delete ix; return fail(MRAG_ERR_HIP, "hipEventCreate failed"); }
-  }
+  int st = MRAG_OK;
+  for (auto& e : ix->ev)
+    if (st == MRAG_OK) st = e.create(true);
+  if (st != MRAG_OK) { delete ix; return st; }
   *out = register_object(ix);
   return MRAG_OK;
 }
 
-int mrag_index_destroy(mrag_handle h) {
-  Object* o = take(h, KIND_BF_INDEX);
-  if (!o) return MRAG_ERR_INVALID;
-  (void)hipSetDevice(o->device);
-  (void)hipDeviceSynchronize();
-  delete o;
-  return MRAG_OK;
-}
+int mrag_index_destroy(mrag_handle h) { return destroy_object(h, KIND_BF_INDEX); }
 
 int mrag_index_reserve(mrag_handle h, int64_t n_rows) {
   BfIndex* ix = (BfIndex*)lookup(h, KIND_BF_INDEX);
@@ -602,8 +589,7 @@ int mrag_index_enable_fp8(mrag_handle h) {
     // rows already stored (adds on any stream): settle them, build the copy on the null stream, finish it here (a one-off)
     MRAG_HIP(hipDeviceSynchronize());
     const size_t bytes8 = (size_t)ix->cap_rows * ix->ld8;
-    hipError_t e = hipMalloc((void**)&ix->rows8, bytes8);
-    if (e != hipSuccess) { (void)hipGetLastError(); ix->rows8 = nullptr; return fail(MRAG_ERR_OOM, "hipMalloc(%zu) for the fp8 rows failed: %s", bytes8, hipGetErrorString(e)); }
+    MRAG_TRY(ix->rows8.alloc(bytes8, "the fp8 rows"));
     MRAG_HIP(hipMemsetAsync(ix->rows8, 0, bytes8, nullptr));
     MRAG_TRY(quant_rows_fp8(ix, 0, ix->n, nullptr));
     MRAG_HIP(hipStreamSynchronize(nullptr));
@@ -660,7 +646,7 @@ int mrag_index_search_fp8(mrag_handle h, const void* queries, int64_t nq, int q_
     int64_t* c_id = (int64_t*)ix->cand.p;
     float* c_sc = (float*)(c_id + (size_t)nq * refine);
     BfLaunch a = s.launch(refine, c_sc, c_id);
-    a.corpus = (const uint16_t*)ix->rows8;
+    a.corpus = (const uint16_t*)ix->rows8.p;
     a.queries = (const uint16_t*)ix->qbuf8.p;
     a.ld = ix->ld8 / 2;              // in 16-bit units: the kernels address rows of ld8 bytes
     a.dtype = MRAG_DT_FP8;

@@ -54,17 +54,13 @@ constexpr unsigned BM25_GRID_YZ = 65535;     // HIP's limit of gridDim.y / gridD
 struct Bm25Index : Object {
   int64_t n_docs = 0, n_terms = 0, nnz = 0;
   double k1p1 = 2.5;
-  int64_t* indptr = nullptr;     // [n_terms + 1]
-  int32_t* post_doc = nullptr;   // [nnz]
-  int32_t* post_tf = nullptr;    // [nnz]
-  double* doc_norm = nullptr;    // [n_docs]  k1 * (1 - b + b * dl / avgdl)
+  DevArray<int64_t> indptr;      // [n_terms + 1]
+  DevArray<int32_t> post_doc;    // [nnz]
+  DevArray<int32_t> post_tf;     // [nnz]
+  DevArray<double> doc_norm;     // [n_docs]  k1 * (1 - b + b * dl / avgdl)
   std::vector<int64_t> h_indptr; // host copy: posting counts size the launches
   int64_t scratch_limit = BM25_DEFAULT_SCRATCH;
   DevBuf scores, plan, hist, sel, out, allow;   // one call in flight per handle
-  ~Bm25Index() override {
-    for (void* p : {(void*)indptr, (void*)post_doc, (void*)post_tf, (void*)doc_norm}) if (p) (void)hipFree(p);
-    for (DevBuf* b : {&scores, &plan, &hist, &sel, &out, &allow}) b->release();
-  }
 };
 
 struct Bm25Job { int64_t lo, hi; double idf; int32_t query; int32_t pad; };   // one (score row, token position) posting range
@@ -394,29 +390,22 @@ int mrag_bm25_create(int device, int64_t n_docs, int64_t n_terms, const int64_t*
   ix->kind = KIND_BM25; ix->device = device;
   ix->n_docs = n_docs; ix->n_terms = n_terms; ix->nnz = nnz; ix->k1p1 = k1_plus_1;
   ix->h_indptr.assign(indptr, indptr + (n_terms ? n_terms + 1 : 0));
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
+  auto up = [&](DevBuf& dst, const void* src, size_t bytes) -> int {
     if (!bytes) return MRAG_OK;
-    if (hipMalloc(dst, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MRAG_ERR_OOM, "hipMalloc(%zu) failed", bytes); }
-    MRAG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    MRAG_TRY(dst.alloc(bytes));
+    MRAG_HIP(hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice));
     return MRAG_OK;
   };
-  int st = up((void**)&ix->indptr, indptr, (size_t)(n_terms ? n_terms + 1 : 0) * 8);
-  if (st == MRAG_OK) st = up((void**)&ix->post_doc, post_doc, (size_t)nnz * 4);
-  if (st == MRAG_OK) st = up((void**)&ix->post_tf, post_tf, (size_t)nnz * 4);
-  if (st == MRAG_OK) st = up((void**)&ix->doc_norm, doc_norm, (size_t)n_docs * 8);
+  int st = up(ix->indptr, indptr, (size_t)(n_terms ? n_terms + 1 : 0) * 8);
+  if (st == MRAG_OK) st = up(ix->post_doc, post_doc, (size_t)nnz * 4);
+  if (st == MRAG_OK) st = up(ix->post_tf, post_tf, (size_t)nnz * 4);
+  if (st == MRAG_OK) st = up(ix->doc_norm, doc_norm, (size_t)n_docs * 8);
   if (st != MRAG_OK) { delete ix; return st; }
   *out = register_object(ix);
   return MRAG_OK;
 }
 
-int mrag_bm25_destroy(mrag_handle h) {
-  Object* o = take(h, KIND_BM25);
-  if (!o) return MRAG_ERR_INVALID;
-  (void)hipSetDevice(o->device);
-  (void)hipDeviceSynchronize();
-  delete o;
-  return MRAG_OK;
-}
+int mrag_bm25_destroy(mrag_handle h) { return destroy_object(h, KIND_BM25); }
 
 int mrag_bm25_set_scratch_limit(mrag_handle h, int64_t bytes) {
   Bm25Index* ix = (Bm25Index*)lookup(h, KIND_BM25);

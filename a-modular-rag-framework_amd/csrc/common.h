@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <mutex>
+#include <utility>
 #include <unordered_map>
 #include <string>
 #include <vector>
@@ -46,15 +47,75 @@ struct Object {
 
 mrag_handle register_object(Object* o);
 Object* lookup(mrag_handle h, HandleKind kind);  // nullptr + error set when invalid
-Object* take(mrag_handle h, HandleKind kind);    // removes from the registry
+// removes the handle from the registry and deletes its object behind the device's queued work: the owners' destructors
+// must not free what a kernel still reads
+int destroy_object(mrag_handle h, HandleKind kind);
 
-// growable device buffer
+// ---- owners of device resources --------------------------------------------------------------------------------------
+// Each frees what it holds in its destructor, moves and does not copy.  They are members of handles and locals of entry
+// points, never parameters (launch structs keep plain DevBuf* and raw views), and never static or at namespace scope: a
+// destructor that runs after the HIP runtime has shut down can crash.  hipFree waits for the device, so a local buffer
+// that dies on an early return behind queued work is safe; host memory that an async copy reads is not owned here and
+// still needs its synchronisation.
+#define MRAG_MOVE_ONLY(T)                          \
+  T() = default;                                   \
+  T(const T&) = delete;                            \
+  T& operator=(const T&) = delete;                 \
+  T(T&& o) noexcept { swap(o); }                   \
+  T& operator=(T&& o) noexcept { swap(o); return *this; }
+
+// device buffer
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
-  int ensure(size_t need);  // grows (contents NOT preserved); returns status
-  void release();
+  MRAG_MOVE_ONLY(DevBuf)
+  ~DevBuf();
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+  int ensure(size_t need);   // grows with 25 % head-room, the exact size if that fails (contents NOT preserved)
+  // storage that is sized once: exactly n bytes, replacing what was held; `what` names it in the refusal ("hipMalloc(n) for <what> failed")
+  int alloc(size_t n, const char* what = nullptr);
 };
+// an exact-size DevBuf that reads as its T*
+template <typename T>
+struct DevArray : DevBuf {
+  operator T*() const { return (T*)p; }
+};
+
+struct Event {
+  hipEvent_t e = nullptr;
+  MRAG_MOVE_ONLY(Event)
+  ~Event();
+  void swap(Event& o) { std::swap(e, o.e); }
+  int create(bool timing);   // once: a no-op on an event that exists
+  operator hipEvent_t() const { return e; }
+};
+
+// pinned host staging
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  MRAG_MOVE_ONLY(PinnedBuf)
+  ~PinnedBuf();
+  void swap(PinnedBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+  int ensure(size_t need);   // grows to exactly `need` (contents NOT preserved)
+};
+
+static inline size_t dtype_size(int dt) {
+  switch (dt) { case MRAG_F32: return 4; case MRAG_F16: case MRAG_BF16: return 2; case MRAG_F64: return 8; default: return 0; }
+}
+
+// Runs `enqueue` and synchronises the stream whatever it returns: asynchronous copies that read host vectors or the
+// caller's host buffers have finished before those go out of scope.  Returns the first failure.
+template <class F>
+static inline int run_synced(hipStream_t stream, F&& enqueue) {
+  const int status = enqueue();
+  if (status != MRAG_OK) {
+    (void)hipStreamSynchronize(stream);
+    return status;
+  }
+  MRAG_HIP(hipStreamSynchronize(stream));
+  return MRAG_OK;
+}
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -139,11 +200,9 @@ struct FilterWork {
   DevBuf fbits;                       // allow-set bitset over the corpus rows, padded with zero words to whole 256-row tiles
   DevBuf fwork;                       // allowed count (int, word 0) | per-block counts | ascending allowed rows
   DevBuf fcomp;                       // path C: the compacted corpus
-  uint32_t* h_fbits = nullptr;        // pinned staging of a host allow-set (pageable copies cost ~25 us per 1M rows)
-  size_t h_fbits_words = 0;
-  hipEvent_t ev_fbits = nullptr;      // recorded after the last copy out of h_fbits (it is rewritten only after it)
+  PinnedBuf h_fbits;                  // pinned staging of a host allow-set (pageable copies cost ~25 us per 1M rows)
+  Event ev_fbits;                     // recorded after the last copy out of h_fbits (it is rewritten only after it)
   bool counted = false;               // fwork holds the counts of the current allow-set
-  void release();
 };
 // the allow-set arguments of a filtered search over n rows: allow_rows == n, a known format, a known path of the
 // MRAG_FILTER_* / MRAG_IVF_FILTER_* enum (`kind` names it in the message: "filter" / "IVF filter")

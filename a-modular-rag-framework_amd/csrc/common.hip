@@ -58,44 +58,62 @@ Object* lookup(mrag_handle h, HandleKind kind) {
   return it->second;
 }
 
-Object* take(mrag_handle h, HandleKind kind) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_objs.find(h);
-  if (it == g_objs.end() || it->second->kind != kind) {
-    set_error("invalid handle 0x%llx", (unsigned long long)h);
-    return nullptr;
+int destroy_object(mrag_handle h, HandleKind kind) {
+  Object* o = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_objs.find(h);
+    if (it == g_objs.end() || it->second->kind != kind) return fail(MRAG_ERR_INVALID, "invalid handle 0x%llx", (unsigned long long)h);
+    o = it->second;
+    g_objs.erase(it);
   }
-  Object* o = it->second;
-  g_objs.erase(it);
-  return o;
+  (void)hipSetDevice(o->device);
+  (void)hipDeviceSynchronize();
+  delete o;
+  return MRAG_OK;
+}
+
+DevBuf::~DevBuf() {
+  if (p) (void)hipFree(p);
 }
 
 int DevBuf::ensure(size_t need) {
   if (need <= bytes) return MRAG_OK;
-  if (p) {
-    (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  size_t want = need + need / 4;
-  hipError_t e = hipMalloc(&p, want);
+  if (alloc(need + need / 4) == MRAG_OK) return MRAG_OK;
+  return alloc(need);
+}
+
+int DevBuf::alloc(size_t n, const char* what) {
+  DevBuf().swap(*this);
+  const hipError_t e = hipMalloc(&p, n);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    want = need;
-    e = hipMalloc(&p, want);
-  }
-  if (e != hipSuccess) {
     p = nullptr;
-    return fail(MRAG_ERR_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    return fail(MRAG_ERR_OOM, "hipMalloc(%zu)%s%s failed: %s", n, what ? " for " : "", what ? what : "", hipGetErrorString(e));
   }
-  bytes = want;
+  bytes = n;
   return MRAG_OK;
 }
 
-void DevBuf::release() {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  bytes = 0;
+Event::~Event() {
+  if (e) (void)hipEventDestroy(e);
+}
+
+int Event::create(bool timing) {
+  if (!e) MRAG_HIP(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
+  return MRAG_OK;
+}
+
+PinnedBuf::~PinnedBuf() {
+  if (p) (void)hipHostFree(p);
+}
+
+int PinnedBuf::ensure(size_t need) {
+  if (need <= bytes) return MRAG_OK;
+  PinnedBuf().swap(*this);
+  MRAG_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+  bytes = need;
+  return MRAG_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -88,20 +88,17 @@ extern "C" int mrag_cosine_adjacent_f64(int device, const double* x, int64_t n, 
   if (!x || !out) return fail(MRAG_ERR_INVALID, "NULL buffer");
   MRAG_TRY(use_device(device));
   hipStream_t stream = (hipStream_t)stream_;
-  void* tmp = nullptr;
   const size_t xb = (size_t)n * dim * 8, ob = (size_t)(n - 1) * 8;
-  MRAG_HIP(hipMalloc(&tmp, xb + ob));
-  hipError_t e = hipMemcpyAsync(tmp, x, xb, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(cosine_adjacent_f64_kernel, dim3((unsigned)((n + 2) / 4)), dim3(256), 0, stream, (const double*)tmp, n, dim, eps,
-                       (double*)((char*)tmp + xb));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, (char*)tmp + xb, ob, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "cosine_adjacent_f64 failed: %s", hipGetErrorString(e));
-  return MRAG_OK;
+  DevBuf tmp;
+  MRAG_TRY(tmp.alloc(xb + ob));
+  double* dout = (double*)((char*)tmp.p + xb);
+  return run_synced(stream, [&]() -> int {
+    MRAG_HIP(hipMemcpyAsync(tmp.p, x, xb, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(cosine_adjacent_f64_kernel, dim3((unsigned)((n + 2) / 4)), dim3(256), 0, stream, (const double*)tmp.p, n, dim, eps, dout);
+    MRAG_HIP(hipGetLastError());
+    MRAG_HIP(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  });
 }
 
 extern "C" int mrag_cosine_matrix_f64(int device, const double* x, int64_t n, int dim, double* out, int is_device, void* stream_) {
@@ -112,23 +109,21 @@ extern "C" int mrag_cosine_matrix_f64(int device, const double* x, int64_t n, in
   hipStream_t stream = (hipStream_t)stream_;
   const double* dx = x;
   double* dout = out;
-  void* tmp = nullptr;
   const size_t xb = (size_t)n * dim * 8, ob = (size_t)n * n * 8;
+  DevBuf tmp;
   if (!is_device) {
-    MRAG_HIP(hipMalloc(&tmp, xb + ob));
-    if (hipMemcpyAsync(tmp, x, xb, hipMemcpyHostToDevice, stream) != hipSuccess) { (void)hipFree(tmp); return fail(MRAG_ERR_HIP, "H2D copy failed"); }
-    dx = (const double*)tmp;
-    dout = (double*)((char*)tmp + xb);
+    MRAG_TRY(tmp.alloc(xb + ob));
+    dx = (const double*)tmp.p;
+    dout = (double*)((char*)tmp.p + xb);
   }
-  hipLaunchKernelGGL(cosine_matrix_f64_kernel, dim3((unsigned)((n * n + 3) / 4)), dim3(256), 0, stream, dx, n, dim, dout);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && !is_device) {
-    e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  if (tmp) (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "cosine_matrix_f64 failed: %s", hipGetErrorString(e));
-  return MRAG_OK;
+  auto enqueue = [&]() -> int {
+    if (!is_device) MRAG_HIP(hipMemcpyAsync(tmp.p, x, xb, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(cosine_matrix_f64_kernel, dim3((unsigned)((n * n + 3) / 4)), dim3(256), 0, stream, dx, n, dim, dout);
+    MRAG_HIP(hipGetLastError());
+    if (!is_device) MRAG_HIP(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  };
+  return is_device ? enqueue() : run_synced(stream, enqueue);   // (device buffers: asynchronous on `stream`)
 }
 
 
@@ -141,25 +136,24 @@ extern "C" int mrag_cosine_f64(int device, const double* query, const double* ca
   hipStream_t stream = (hipStream_t)stream_;
   const double *dq = query, *dc = cands;
   double* dout = out_scores;
-  void* tmp = nullptr;
+  const size_t qb = (size_t)dim * 8, cb = (size_t)n * dim * 8, ob = (size_t)n * 8;
+  DevBuf tmp;
   if (!is_device) {
-    const size_t qb = (size_t)dim * 8, cb = (size_t)n * dim * 8, ob = (size_t)n * 8;
-    MRAG_HIP(hipMalloc(&tmp, qb + cb + ob));
-    char* base = (char*)tmp;
-    hipError_t e1 = hipMemcpyAsync(base, query, qb, hipMemcpyHostToDevice, stream);
-    hipError_t e2 = hipMemcpyAsync(base + qb, cands, cb, hipMemcpyHostToDevice, stream);
-    if (e1 != hipSuccess || e2 != hipSuccess) { (void)hipFree(tmp); return fail(MRAG_ERR_HIP, "H2D copy failed"); }
+    MRAG_TRY(tmp.alloc(qb + cb + ob));
+    char* base = (char*)tmp.p;
     dq = (const double*)base;
     dc = (const double*)(base + qb);
     dout = (double*)(base + qb + cb);
   }
-  hipLaunchKernelGGL(cosine_f64_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, dq, dc, n, dim, dout);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && !is_device) {
-    e = hipMemcpyAsync(out_scores, dout, (size_t)n * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  if (tmp) (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "cosine_f64 failed: %s", hipGetErrorString(e));
-  return MRAG_OK;
+  auto enqueue = [&]() -> int {
+    if (!is_device) {
+      MRAG_HIP(hipMemcpyAsync(tmp.p, query, qb, hipMemcpyHostToDevice, stream));
+      MRAG_HIP(hipMemcpyAsync((char*)tmp.p + qb, cands, cb, hipMemcpyHostToDevice, stream));
+    }
+    hipLaunchKernelGGL(cosine_f64_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, dq, dc, n, dim, dout);
+    MRAG_HIP(hipGetLastError());
+    if (!is_device) MRAG_HIP(hipMemcpyAsync(out_scores, dout, ob, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  };
+  return is_device ? enqueue() : run_synced(stream, enqueue);   // (device buffers: asynchronous on `stream`)
 }

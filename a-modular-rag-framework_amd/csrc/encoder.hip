@@ -51,24 +51,20 @@ struct Encoder : Object {
   float *word = nullptr, *pos = nullptr, *type = nullptr, *eln_g = nullptr, *eln_b = nullptr;
   std::vector<Layer> layers;
   std::vector<Param> params;               // every parameter a forward needs, in state-dict order (build_params)
-  std::vector<void*> allocs;
+  std::vector<DevBuf> allocs;              // the parameters' storage
   DevBuf ids, mask, x, y, qkv, ctx, ffn, out, stage;
   DevBuf y2, partials, st1, st2;           // fused-LayerNorm flow: second pre-LayerNorm buffer, partial sums, (mu, rstd) per token
   bool folded = false;                     // fold_layernorms done for the current parameters
-  hipEvent_t ev[2] = {nullptr, nullptr};   // device work of the last forward (embeddings .. pooling), on its stream
+  Event ev[2];                             // device work of the last forward (embeddings .. pooling), on its stream
   bool timed = false;
-  ~Encoder() override {
-    for (auto& v : ev) if (v) (void)hipEventDestroy(v);
-    for (void* p : allocs) (void)hipFree(p);
-    for (DevBuf* b : {&ids, &mask, &x, &y, &qkv, &ctx, &ffn, &out, &stage, &y2, &partials, &st1, &st2}) b->release();
-  }
 };
 
 static int dev_alloc(Encoder* e, void** p, size_t bytes) {
-  hipError_t err = hipMalloc(p, bytes);
-  if (err != hipSuccess) return fail(MRAG_ERR_OOM, "hipMalloc(%zu) failed", bytes);
-  (void)hipMemset(*p, 0, bytes);
-  e->allocs.push_back(*p);
+  DevBuf b;
+  MRAG_TRY(b.alloc(bytes));
+  (void)hipMemset(b.p, 0, bytes);
+  *p = b.p;
+  e->allocs.push_back(std::move(b));
   return MRAG_OK;
 }
 
@@ -342,14 +338,7 @@ int mrag_encoder_create(const mrag_encoder_config* cfg, int device, mrag_handle*
   return MRAG_OK;
 }
 
-int mrag_encoder_destroy(mrag_handle h) {
-  Object* o = take(h, KIND_ENCODER);
-  if (!o) return MRAG_ERR_INVALID;
-  (void)hipSetDevice(o->device);
-  (void)hipDeviceSynchronize();
-  delete o;
-  return MRAG_OK;
-}
+int mrag_encoder_destroy(mrag_handle h) { return destroy_object(h, KIND_ENCODER); }
 
 int mrag_encoder_set_param(mrag_handle h, const char* name, const float* data, int64_t numel, int is_device, void* stream_) {
   Encoder* e = (Encoder*)lookup(h, KIND_ENCODER);
@@ -405,7 +394,7 @@ int mrag_encoder_forward(mrag_handle h, const int32_t* ids, const int32_t* mask,
   if (!io_is_device) { MRAG_TRY(e->out.ensure((size_t)B * e->cfg.hidden * 4)); d_out = (float*)e->out.p; }
   e->timed = false;
   for (auto& v : e->ev)
-    if (!v) MRAG_HIP(hipEventCreate(&v));
+    MRAG_TRY(v.create(true));
   MRAG_HIP(hipEventRecord(e->ev[0], stream));
   MRAG_TRY(forward(e, B, S, d_out, pool, normalize, stream));
   MRAG_HIP(hipEventRecord(e->ev[1], stream));

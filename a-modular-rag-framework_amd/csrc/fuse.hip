@@ -272,23 +272,21 @@ int fuse_questions(int device, int n_questions, const int32_t* chan_ptr, const i
   if (lds > 65536)    // above HIP's default limit of dynamic LDS the kernel's own limit is raised (a process-wide, idempotent setting)
     MRAG_HIP(hipFuncSetAttribute((const void*)fuse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)fuse_lds_bytes(FUSE_MAX, 1024)));
-  char* d = nullptr;
-  MRAG_HIP(hipMalloc((void**)&d, in_bytes + out_bytes));
-  char* d_out = d + in_bytes;
-  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
+  DevBuf block;
+  MRAG_TRY(block.alloc(in_bytes + out_bytes));
+  char *d = (char*)block.p, *d_out = d + in_bytes;
+  // (run_synced: the staging vectors are in use until the stream has settled, also after a failure)
+  MRAG_TRY(run_synced(stream, [&]() -> int {
+    MRAG_HIP(hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)n_questions), dim3((unsigned)T), lds, stream, (const int32_t*)(d + i_ptr),
                        (const int32_t*)(d + i_keys), (const double*)(d + i_scores), payload ? (const int32_t*)(d + i_pay) : nullptr,
                        (const int32_t*)(d + i_topk), alpha_text, alpha_graph, alpha_dense, out_stride, (int32_t*)(d_out + o_key),
                        (double*)(d_out + o_fused), (double*)(d_out + o_nt), (double*)(d_out + o_ng), (double*)(d_out + o_nd),
                        payload ? (int32_t*)(d_out + o_pay) : nullptr, (int32_t*)(d_out + o_n));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, stream);
-  const hipError_t es = hipStreamSynchronize(stream);    // the staging buffers are in use until here, also after a failure
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(MRAG_ERR_HIP, "fuse_topk failed: %s", hipGetErrorString(e));
+    MRAG_HIP(hipGetLastError());
+    MRAG_HIP(hipMemcpyAsync(h_out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    return MRAG_OK;
+  }));
   memcpy(out_scores, h_out.data() + o_fused, n_out * 8);
   memcpy(out_text_norm, h_out.data() + o_nt, n_out * 8);
   memcpy(out_graph_norm, h_out.data() + o_ng, n_out * 8);

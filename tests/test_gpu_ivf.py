@@ -239,7 +239,7 @@ def test_synced_plan_fits_falls_back_or_refuses():
                            cwd=os.path.dirname(os.path.dirname(__file__)), timeout=600)
             res[mode] = dict(np.load(path))
     dflt, small = res["default"], res["small"]
-    # the preconditions, by the arithmetic of the chunking rule and of the score plan (csrc/ivf.hip)
+    # the preconditions, by the arithmetic of the chunking rule and of the score plan (csrc/ivf_search.hip)
     counts = small["counts"]
     pitch = (counts + 31) // 32 * 32
     assert counts[int(small["L"])] >= 8000 and counts.max() == counts[int(small["L"])]
